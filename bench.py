@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the SRGAN G+D+E train step on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 from a bare shell: the parent starts N fresh rank processes (``python -m torch.distributed.run``, one per GPU,
 RCCL) BEFORE touching the GPU itself, forwards rank 0's JSON line and exits with their status.  Already under
@@ -10,8 +10,12 @@ torch.distributed.run (WORLD_SIZE set): runs as that rank.
 A "step" = one ``SRGAN_training.train`` call (k=5 D updates + the two-phase G/E update) on one synthetic
 CelebA-shaped batch.  Workload at N=1 = BASELINE.json configs[1]: SRGAN-nopretrain, 128x128, bs=32/GPU, fp32,
 notebook hyper-parameters (05-train cells 13/16).  Weak scaling: 32 images per GPU, global batch 32*N.
-Prints ONE JSON line on rank 0 with ``roofline`` (dominant kernel, HIP-event timed) and, at N=1, ``cpu_baseline``
-(the CPU oracle timed on the host cores on a bounded sample) and ``micro_gd`` (north_star's G+D forward-backward target).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline; with
+``--dump-outputs DIR`` it also writes what the last timed step computed (its losses and a fixed sample of the trained
+parameters) as DIR/<name>.npy.  ``--full`` adds everything else to the line: the first step checked against the CPU
+oracle's fixture, ``roofline`` (dominant kernel, HIP-event timed) and, at N=1, ``micro_gd`` (north_star's G+D
+forward-backward target), the ``bf16`` sub-record and ``cpu_baseline`` (the CPU oracle timed on the host cores on a
+bounded sample).
 """
 import argparse
 import ctypes
@@ -284,7 +288,8 @@ def bf16_sub_record(args):
     fraction of the bf16 matrix peak, whole-step issued fraction}: the bf16 mode next to the fp32 headline, timed by the same run."""
     log("bf16 mode: the same workload through --dtype bf16 (child process)")
     cmd = [sys.executable, os.path.abspath(__file__), "--dtype", "bf16", "--steps", "20", "--warmup", "5", "--size", str(args.size),
-           "--batch-per-gpu", str(args.batch_per_gpu), "--k", str(args.k), "--graph", args.graph, "--no-cpu-baseline", "--no-micro"]
+           "--batch-per-gpu", str(args.batch_per_gpu), "--k", str(args.k), "--graph", args.graph, "--full", "--no-cpu-baseline",
+           "--no-micro"]
     if args.pretrained_e:
         cmd.append("--pretrained-e")
     try:
@@ -389,6 +394,128 @@ def _trainer_has_graph():
     return hasattr(SRGAN_training, "enable_graph")
 
 
+DUMP_SAMPLE = 1 << 18        # elements kept of a larger parameter tensor: ~29 MB written in all at 128x128
+
+
+def dump_outputs(out_dir, sg, last):
+    """--dump-outputs: what the last timed step computed -- the [errG, errD, errE] train() returned (losses.npy, float64) and the
+    parameters of G, D and E it left behind (<net>.<name>.npy, float32).  A tensor of more than DUMP_SAMPLE elements is written
+    as a fixed sample: the flat elements at sorted indices drawn by a generator seeded with the parameter's position, so the
+    same arguments give the same sample in every run.  Returns the number of bytes written."""
+    from srgan_amd import dp
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"losses": np.asarray([float(v) for v in last], dtype=np.float64)}
+    for tag, net in (("G", sg.G), ("D", sg.D), ("E", sg.E)):
+        for name, p in dp.unwrap(net).named_parameters():
+            arrays[f"{tag}.{name}"] = p.detach().float().cpu().numpy().reshape(-1)
+    total = 0
+    for i, (name, a) in enumerate(arrays.items()):
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(i).choice(a.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        total += a.nbytes
+    return total
+
+
+def kernel_totals(lib):
+    """Per-kernel totals of the library's HIP-event brackets -> (GEMM-class kernels, HBM-bound kernels, the GEMM-class kernel
+    with the largest total time as (name, ms, launches, flops))."""
+    from srgan_amd import _lib
+    kernels = {}
+    hbm = {}
+    best = None
+    for kid in range(lib.srgan_prof_num_kernels()):
+        ms, n, fl = ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double()
+        _lib.check(lib.srgan_prof_collect(kid, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(fl)), "prof_collect")
+        if n.value == 0:
+            continue
+        name = lib.srgan_prof_kernel_name(kid).decode()
+        if is_hbm_kernel(name):
+            hbm[name] = {"launches": n.value, "total_ms": round(ms.value, 3), "avg_us": round(1e3 * ms.value / n.value, 2),
+                         "algorithmic_mb_per_launch": round(fl.value / n.value / 1e6, 2),
+                         "achieved_tb_s": round(fl.value / (ms.value * 1e-3) / 1e12, 3), "_ms": ms.value, "_bytes": fl.value}
+            continue
+        div = executed_divisor(name)
+        kernels[name] = {"launches": n.value, "total_ms": round(ms.value, 3), "avg_us": round(1e3 * ms.value / n.value, 2),
+                         "algorithmic_tflops": round(fl.value / (ms.value * 1e-3) / 1e12, 2),
+                         "executed_tflops": round(fl.value / div / (ms.value * 1e-3) / 1e12, 2),
+                         "_ms": ms.value, "_fl": fl.value}
+        if fl.value > 0 and (best is None or ms.value > best[1]):
+            best = (name, ms.value, n.value, fl.value)
+    return kernels, hbm, best
+
+
+def add_roofline(out, args, kernels, hbm, best, prof_steps, prof_live, step_ms_mean):
+    """--full: the launched-FLOP figures of out["config"], out["roofline"] (the dominant GEMM-class kernel against the MFMA peak)
+    and out["roofline_hbm"] (the largest HBM-bound kernel) from the per-kernel totals of `prof_steps` steps."""
+    peak = PEAK_TFLOPS["f32" if args.dtype == "f32" else "bf16"]
+    name, ms, n, fl = best
+    div = executed_divisor(name)
+    algorithmic = fl / (ms * 1e-3) / 1e12
+    executed = algorithmic / div
+    # the layer a Winograd F(4x4,3x3) multiply belongs to also runs its HBM-bound transform kernel
+    partner = {"wino43_kernel": "wino43_input_kernel", "wino43_wgrad_kernel": "wino43_dy_kernel"}.get(name)
+    layer = None
+    if partner and partner in kernels:
+        lms = ms + kernels[partner]["_ms"]
+        layer = {"kernels": [partner, name], "total_ms": round(lms, 3),
+                 "executed_tflops": round(fl / div / (lms * 1e-3) / 1e12, 2),
+                 "frac": round(fl / div / (lms * 1e-3) / 1e12 / peak, 4),
+                 "algorithmic_tflops": round(fl / (lms * 1e-3) / 1e12, 2)}
+    step_exec = sum(kk["_fl"] / executed_divisor(nm) for nm, kk in kernels.items()) / prof_steps      # FLOPs per step
+    step_alg_launched = sum(kk["_fl"] for kk in kernels.values()) / prof_steps       # algorithmic FLOPs the launches carry
+    gemm_ms = sum(kk["_ms"] for kk in kernels.values()) / prof_steps
+    for kk in kernels.values():
+        kk.pop("_ms"), kk.pop("_fl")
+    traffic, traffic_src, traffic_current = pmc_traffic(name, args.dtype)
+    out["config"]["step_tflop_algorithmic_launched"] = round(step_alg_launched / 1e12, 3)
+    out["config"]["step_tflops_algorithmic_launched"] = round(step_alg_launched / 1e12 / (step_ms_mean * 1e-3), 2)
+    out["roofline"] = {"bound": "mfma", "kernel": name, "achieved": round(executed, 2), "peak": peak, "unit": "TFLOP/s",
+                       "frac": round(executed / peak, 4),
+                       "traffic": traffic if traffic_current else None,
+                       "traffic_replayed": None if traffic_current else traffic,
+                       "traffic_note": "no PMC entry for this kernel under profiles/" if traffic is None else
+                                       (f"HBM bytes per launch (2*FETCH_SIZE + WRITE_SIZE, rocprofv3 PMC) from {traffic_src}, collected "
+                                        "over this same command in separate --pmc passes" +
+                                        (" ON THIS BUILD (the summary records this tree's kernel_source_sha)" if traffic_current else
+                                         " on an EARLIER build (kernel_source_sha differs): replayed, not this build's traffic")),
+                       "achieved_note": "achieved / frac = MFMA FLOPs this kernel actually ISSUES (algorithmic conv FLOPs / "
+                                        f"{div:g}) / HIP-event duration, against the dense matrix peak: the utilisation of the matrix pipe",
+                       "algorithmic_tflops": round(algorithmic, 2), "algorithmic_over_peak": round(algorithmic / peak, 4),
+                       "algorithmic_note": "direct-convolution FLOPs (2*N*Ho*Wo*O*kh*kw*I, SURVEY 8d) of this kernel's launches / "
+                                           "their duration; exceeds the peak for the Winograd kernels because they skip multiplies",
+                       "launches": n, "avg_launch_us": round(1e3 * ms / n, 2),
+                       "layer": layer,
+                       "step": {"executed_mfma_tflop_per_step": round(step_exec / 1e12, 3),
+                                "executed_frac": round(step_exec / (step_ms_mean * 1e-3) / 1e12 / peak, 4),
+                                "executed_frac_over_gemm_kernel_time": round(step_exec / (gemm_ms * 1e-3) / 1e12 / peak, 4),
+                                "gemm_kernel_ms_per_step": round(gemm_ms, 3),
+                                "note": "all GEMM-class launches of a step: issued MFMA FLOPs / step time (and / their own "
+                                        "summed duration) / peak"},
+                       "measured_over": (f"{prof_steps} eager steps after the timed region (HIP events cannot bracket kernels "
+                                         "inside a hipGraph replay; same kernels and shapes)") if not prof_live else
+                                        "the timed region (HIP events on the launch stream, rank 0)",
+                       "all_gemm_kernels": kernels}
+    if hbm:
+        # the largest HBM-bound kernel of the step (VERDICT r3 item 6): algorithmic bytes per launch / duration / 8 TB/s
+        top = max(hbm, key=lambda k_: hbm[k_]["_ms"])
+        tot_ms = sum(v["_ms"] for v in hbm.values())
+        tot_b = sum(v["_bytes"] for v in hbm.values())
+        for v in hbm.values():
+            v.pop("_ms"), v.pop("_bytes")
+        out["roofline_hbm"] = {"bound": "hbm", "kernel": top, "achieved": round(1e3 * hbm[top]["achieved_tb_s"], 1), "peak": 1e3 * HBM_PEAK_TBS,
+                               "unit": "GB/s", "frac": round(hbm[top]["achieved_tb_s"] / HBM_PEAK_TBS, 4),
+                               "launches": hbm[top]["launches"], "avg_launch_us": hbm[top]["avg_us"],
+                               "algorithmic_mb_per_launch": hbm[top]["algorithmic_mb_per_launch"],
+                               "instance_norm_passes": {"ms_per_step": round(tot_ms / prof_steps, 3),
+                                                        "achieved_tb_s": round(tot_b / (tot_ms * 1e-3) / 1e12, 3),
+                                                        "note": "all instance-norm passes: the two-pass and slab kernels of csrc/norm.hip and (round 5) the "
+                                                                "fused norm + Winograd-transform kernels of the trunk (in_fwd_slab_v, in_bwd_slab_vz: "
+                                                                "tensor read(s) + 2.25x transform image(s) written): bytes each pass must move / "
+                                                                "summed duration"},
+                               "measured_over": out["roofline"]["measured_over"], "kernels": hbm}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -411,6 +538,13 @@ def main():
                          "instead of the full train step")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous only: every rank reports in, rank 0 prints a JSON line, nobody touches the GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's losses and a fixed sample of the trained parameters "
+                         "as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the first step's check against the CPU oracle fixture, "
+                         "the per-kernel roofline record and, at N=1, the G+D micro-benchmark, the bf16 sub-record and the "
+                         "CPU baseline (the --no-* switches still drop single parts)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -457,7 +591,7 @@ def main():
     use_graph = args.graph != "off" and _trainer_has_graph()
     if args.graph == "on" and not use_graph:
         raise SystemExit("--graph on: this trainer has no hipGraph mode")
-    warm = max(args.warmup, 2 if use_graph else 1)      # step 0 is the oracle-checked one; a graph needs one more to be captured
+    warm = max(args.warmup, 2 if use_graph else 1)      # step 0 runs eagerly (oracle-checked with --full); a graph needs one more to be captured
     batches = []
     for s in range(args.steps + warm):
         x, src, tgt = synthetic_batch(B, args.size, 4, seed=10_000 * (rank + 1) + s)
@@ -469,8 +603,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # step 0 (eager, un-warmed): checked against the CPU oracle's losses for the same seeds
-    log(f"rank {rank}/{world}: inputs resident; first step (checked against the oracle fixture)")
+    # step 0 (eager, un-warmed): with --full, checked against the CPU oracle's losses for the same seeds
+    log(f"rank {rank}/{world}: inputs resident; first step" + (" (checked against the oracle fixture)" if args.full else ""))
     if use_graph:
         try:
             sg.enable_graph()            # step 0 still runs eagerly (it creates optimiser state / packed operands); step 1 captures
@@ -480,7 +614,14 @@ def main():
             log(f"hipGraph mode not available here, running eagerly: {e}")
             use_graph = False
     first = [float(v) for v in sg.train(*batches[0])]
-    check = first_step_check(first, args, world) if rank == 0 else None
+    if rank != 0:
+        check = None
+    elif args.full:
+        check = first_step_check(first, args, world)
+    elif not all(np.isfinite(first)) and not _lib.ab("SRGAN_BENCH_NO_CHECK"):
+        raise SystemExit(f"bench: non-finite losses in the first step: {first}")
+    else:
+        check = {"hip": [round(v, 5) for v in first], "oracle": None, "check": "with --full"}
     log(f"warm-up x{args.warmup}" + (" (captures the hipGraph)" if use_graph else ""))
     for s in range(1, warm):
         sg.train(*batches[s])
@@ -499,7 +640,7 @@ def main():
         raise SystemExit("bench: hipGraph mode was requested and available, but the warm-up did not leave a recorded step behind "
                          "(the trainer fell back to eager launches); run with --graph off to measure that")
     barrier()
-    prof_live = not graphed                   # HIP events cannot bracket kernels inside a graph replay
+    prof_live = args.full and not graphed     # HIP events cannot bracket kernels inside a graph replay
     if prof_live:
         lib.srgan_prof_enable(1)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
@@ -520,70 +661,32 @@ def main():
         t = torch.tensor([elapsed, median_ms], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, median_ms = float(t[0].item()), float(t[1].item())
+    if rank == 0 and args.dump_outputs:
+        # before anything else runs a step: the parameters are the ones the last timed step left
+        log(f"outputs of the last timed step: {dump_outputs(args.dump_outputs, sg, last) / 1e6:.1f} MB to {args.dump_outputs}")
     last = [float(v) for v in last]
     if not all(np.isfinite(last)):
         raise SystemExit(f"bench: non-finite losses after the timed region: {last}")
 
-    prof_steps = args.steps
-    if not prof_live:
-        # same kernels, same shapes, eager launches: per-kernel HIP-event durations for the roofline record
-        prof_steps = min(args.steps, 3)
-        if hasattr(sg, "disable_graph"):
-            sg.disable_graph()
-        torch.cuda.synchronize()
-        lib.srgan_prof_enable(1)
-        for s in range(prof_steps):
-            sg.train(*batches[1 + s])
-        torch.cuda.synchronize()
-        lib.srgan_prof_enable(0)
-
-    # per-kernel totals of the HIP-event brackets
-    kernels = {}
-    hbm = {}
-    best = None
-    for kid in range(lib.srgan_prof_num_kernels()):
-        ms, n, fl = ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double()
-        _lib.check(lib.srgan_prof_collect(kid, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(fl)), "prof_collect")
-        if n.value == 0:
-            continue
-        name = lib.srgan_prof_kernel_name(kid).decode()
-        if is_hbm_kernel(name):
-            hbm[name] = {"launches": n.value, "total_ms": round(ms.value, 3), "avg_us": round(1e3 * ms.value / n.value, 2),
-                         "algorithmic_mb_per_launch": round(fl.value / n.value / 1e6, 2),
-                         "achieved_tb_s": round(fl.value / (ms.value * 1e-3) / 1e12, 3), "_ms": ms.value, "_bytes": fl.value}
-            continue
-        div = executed_divisor(name)
-        kernels[name] = {"launches": n.value, "total_ms": round(ms.value, 3), "avg_us": round(1e3 * ms.value / n.value, 2),
-                         "algorithmic_tflops": round(fl.value / (ms.value * 1e-3) / 1e12, 2),
-                         "executed_tflops": round(fl.value / div / (ms.value * 1e-3) / 1e12, 2),
-                         "_ms": ms.value, "_fl": fl.value}
-        if fl.value > 0 and (best is None or ms.value > best[1]):
-            best = (name, ms.value, n.value, fl.value)
+    if args.full:
+        prof_steps = args.steps
+        if not prof_live:
+            # same kernels, same shapes, eager launches: per-kernel HIP-event durations for the roofline record
+            prof_steps = min(args.steps, 3)
+            if hasattr(sg, "disable_graph"):
+                sg.disable_graph()
+            torch.cuda.synchronize()
+            lib.srgan_prof_enable(1)
+            for s in range(prof_steps):
+                sg.train(*batches[1 + s])
+            torch.cuda.synchronize()
+            lib.srgan_prof_enable(0)
+        kernels, hbm, best = kernel_totals(lib)
 
     if rank == 0:
         images = B * world * args.steps
         value = images / elapsed
-        peak = PEAK_TFLOPS["f32" if args.dtype == "f32" else "bf16"]
-        name, ms, n, fl = best
-        div = executed_divisor(name)
-        algorithmic = fl / (ms * 1e-3) / 1e12
-        executed = algorithmic / div
-        # the layer a Winograd F(4x4,3x3) multiply belongs to also runs its HBM-bound transform kernel
-        partner = {"wino43_kernel": "wino43_input_kernel", "wino43_wgrad_kernel": "wino43_dy_kernel"}.get(name)
-        layer = None
-        if partner and partner in kernels:
-            lms = ms + kernels[partner]["_ms"]
-            layer = {"kernels": [partner, name], "total_ms": round(lms, 3),
-                     "executed_tflops": round(fl / div / (lms * 1e-3) / 1e12, 2),
-                     "frac": round(fl / div / (lms * 1e-3) / 1e12 / peak, 4),
-                     "algorithmic_tflops": round(fl / (lms * 1e-3) / 1e12, 2)}
-        step_exec = sum(kk["_fl"] / executed_divisor(nm) for nm, kk in kernels.items()) / prof_steps      # FLOPs per step
-        step_alg_launched = sum(kk["_fl"] for kk in kernels.values()) / prof_steps       # algorithmic FLOPs the launches carry
-        gemm_ms = sum(kk["_ms"] for kk in kernels.values()) / prof_steps
         step_ms_mean = 1e3 * elapsed / args.steps
-        for kk in kernels.values():
-            kk.pop("_ms"), kk.pop("_fl")
-        traffic, traffic_src, traffic_current = pmc_traffic(name, args.dtype)
         switches = _lib.active_switches()
         gflop_img = (GFLOP_PER_IMAGE_FROZEN_E if args.pretrained_e else GFLOP_PER_IMAGE).get(args.size)
         out = {
@@ -620,65 +723,21 @@ def main():
                        # the contract's figure counts every convolution of the reference's step; the launches carry less because
                        # phase 1 shares one E(source) trunk pass (result-preserving): both are stated
                        "step_tflop_algorithmic_contract": round(B * (gflop_img or 0) / 1e3, 3),
-                       "step_tflop_algorithmic_launched": round(step_alg_launched / 1e12, 3),
-                       "step_tflops_algorithmic_launched": round(step_alg_launched / 1e12 / (step_ms_mean * 1e-3), 2),
                        "losses_first_step_vs_oracle": check,
                        "losses_last_step": [round(v, 4) for v in last]},
-            "roofline": {"bound": "mfma", "kernel": name, "achieved": round(executed, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(executed / peak, 4),
-                         "traffic": traffic if traffic_current else None,
-                         "traffic_replayed": None if traffic_current else traffic,
-                         "traffic_note": "no PMC entry for this kernel under profiles/" if traffic is None else
-                                         (f"HBM bytes per launch (2*FETCH_SIZE + WRITE_SIZE, rocprofv3 PMC) from {traffic_src}, collected "
-                                          "over this same command in separate --pmc passes" +
-                                          (" ON THIS BUILD (the summary records this tree's kernel_source_sha)" if traffic_current else
-                                           " on an EARLIER build (kernel_source_sha differs): replayed, not this build's traffic")),
-                         "achieved_note": "achieved / frac = MFMA FLOPs this kernel actually ISSUES (algorithmic conv FLOPs / "
-                                          f"{div:g}) / HIP-event duration, against the dense matrix peak: the utilisation of the matrix pipe",
-                         "algorithmic_tflops": round(algorithmic, 2), "algorithmic_over_peak": round(algorithmic / peak, 4),
-                         "algorithmic_note": "direct-convolution FLOPs (2*N*Ho*Wo*O*kh*kw*I, SURVEY 8d) of this kernel's launches / "
-                                             "their duration; exceeds the peak for the Winograd kernels because they skip multiplies",
-                         "launches": n, "avg_launch_us": round(1e3 * ms / n, 2),
-                         "layer": layer,
-                         "step": {"executed_mfma_tflop_per_step": round(step_exec / 1e12, 3),
-                                  "executed_frac": round(step_exec / (step_ms_mean * 1e-3) / 1e12 / peak, 4),
-                                  "executed_frac_over_gemm_kernel_time": round(step_exec / (gemm_ms * 1e-3) / 1e12 / peak, 4),
-                                  "gemm_kernel_ms_per_step": round(gemm_ms, 3),
-                                  "note": "all GEMM-class launches of a step: issued MFMA FLOPs / step time (and / their own "
-                                          "summed duration) / peak"},
-                         "measured_over": (f"{prof_steps} eager steps after the timed region (HIP events cannot bracket kernels "
-                                           "inside a hipGraph replay; same kernels and shapes)") if not prof_live else
-                                          "the timed region (HIP events on the launch stream, rank 0)",
-                         "all_gemm_kernels": kernels},
         }
-        if hbm:
-            # the largest HBM-bound kernel of the step: algorithmic bytes per launch / duration / 8 TB/s
-            top = max(hbm, key=lambda k_: hbm[k_]["_ms"])
-            tot_ms = sum(v["_ms"] for v in hbm.values())
-            tot_b = sum(v["_bytes"] for v in hbm.values())
-            for v in hbm.values():
-                v.pop("_ms"), v.pop("_bytes")
-            out["roofline_hbm"] = {"bound": "hbm", "kernel": top, "achieved": round(1e3 * hbm[top]["achieved_tb_s"], 1), "peak": 1e3 * HBM_PEAK_TBS,
-                                   "unit": "GB/s", "frac": round(hbm[top]["achieved_tb_s"] / HBM_PEAK_TBS, 4),
-                                   "launches": hbm[top]["launches"], "avg_launch_us": hbm[top]["avg_us"],
-                                   "algorithmic_mb_per_launch": hbm[top]["algorithmic_mb_per_launch"],
-                                   "instance_norm_passes": {"ms_per_step": round(tot_ms / prof_steps, 3),
-                                                            "achieved_tb_s": round(tot_b / (tot_ms * 1e-3) / 1e12, 3),
-                                                            "note": "all instance-norm passes: the two-pass and slab kernels of csrc/norm.hip and (round 5) the "
-                                                                    "fused norm + Winograd-transform kernels of the trunk (in_fwd_slab_v, in_bwd_slab_vz: "
-                                                                    "tensor read(s) + 2.25x transform image(s) written): bytes each pass must move / "
-                                                                    "summed duration"},
-                                   "measured_over": out["roofline"]["measured_over"], "kernels": hbm}
-        if world == 1 and not args.no_micro and args.size in GD_GFLOP_PER_IMAGE:
+        if args.full:
+            add_roofline(out, args, kernels, hbm, best, prof_steps, prof_live, step_ms_mean)
+        if args.full and world == 1 and not args.no_micro and args.size in GD_GFLOP_PER_IMAGE:
             log("micro benchmark: G+D forward-backward")
             del sg
             torch.cuda.empty_cache()
             out["micro_gd"] = micro_gd_run(args.size, B, args.dtype, 10, 3, device)
-        if world == 1 and args.dtype == "f32" and not args.no_bf16 and not args.no_micro and not switches:
+        if args.full and world == 1 and args.dtype == "f32" and not args.no_bf16 and not args.no_micro and not switches:
             # the bf16 mode (BASELINE configs[2]-[4]) measured by the driver's own command -- the same workload
             # through `--dtype bf16` in a child process (its own 5 + 20 steps, graph replay), reduced to the numbers that matter
             out["bf16"] = bf16_sub_record(args)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.size, args.k, B)
         print(json.dumps(out))
         if switches:

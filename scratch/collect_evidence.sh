@@ -6,11 +6,11 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 E=$R/gpurun_out/${EV_OUT:-ev}
 rm -rf $E && mkdir -p $E
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py $EV_FLAGS --steps 20 --warmup 5 > $E/bench_plain.json 2> $E/bench_plain.err || exit 1
+python3 $R/bench.py $EV_FLAGS --full --steps 20 --warmup 5 > $E/bench_plain.json 2> $E/bench_plain.err || exit 1
 echo "plain done"
-python3 $R/bench.py $EV_FLAGS --steps 20 --warmup 5 --graph off --no-cpu-baseline --no-micro > $E/bench_eager.json 2> $E/bench_eager.err || exit 1
+python3 $R/bench.py $EV_FLAGS --full --steps 20 --warmup 5 --graph off --no-cpu-baseline --no-micro > $E/bench_eager.json 2> $E/bench_eager.err || exit 1
 echo "eager done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $E/stats -- python3 $R/bench.py $EV_FLAGS --steps 5 --warmup 2 --no-cpu-baseline --no-micro > $E/bench_under_rocprof.json 2> $E/stats.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $E/stats -- python3 $R/bench.py $EV_FLAGS --full --steps 5 --warmup 2 --no-cpu-baseline --no-micro > $E/bench_under_rocprof.json 2> $E/stats.err || exit 1
 echo "stats done"
 # Round 6: the counter passes run SERIALISED (AMD_SERIALIZE_KERNEL=3) and under a time limit.  An eager bench.py enqueues every step
 # without synchronising; past ~8000 outstanding dispatches rocprofv3's counter-collecting queue aborts with

@@ -242,3 +242,35 @@ def test_non_mse_class_criterion_leaves_the_fused_paths():
         with pytest.raises(NotImplementedError, match="nn.MSELoss"):
             hl.get_domainloss_D([torch.zeros(2, 4)], torch.zeros(2, 4), crit)
     assert ok._noise_kinds() == ["randn"] + ["normal"] * 2 + ["normal"] * 3
+
+
+def test_bench_dump_outputs_is_a_fixed_bounded_float_sample(tmp_path):
+    """bench.py --dump-outputs: the last step's losses (float64) and the G / D / E parameters of the benchmarked networks
+    (float32; a larger tensor as a fixed seeded sample) -- the same files in every run, under 64 MB in all."""
+    import importlib.util
+    import types
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    G, D, E = bench.build_nets(128, "cpu")
+    sg = types.SimpleNamespace(G=G, D=D, E=E)
+    last = [torch.tensor(1.25), torch.tensor(-0.5), torch.tensor(3.0)]
+    n1 = bench.dump_outputs(str(tmp_path / "a"), sg, last)
+    n2 = bench.dump_outputs(str(tmp_path / "b"), sg, last)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert n1 == n2 <= 64 << 20 and names == sorted(os.listdir(tmp_path / "b"))
+    assert len(names) == 1 + 78 + 16 + 24 and "losses.npy" in names
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "losses.npy"), np.array([1.25, -0.5, 3.0]))
+    total = 0
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+        total += a.nbytes
+    assert total == n1
+    big_name, big = max(E.named_parameters(), key=lambda kv: kv[1].numel())
+    small_name, small = min(G.named_parameters(), key=lambda kv: kv[1].numel())
+    assert big.numel() > bench.DUMP_SAMPLE
+    sample = np.load(tmp_path / "a" / f"E.{big_name}.npy")
+    assert sample.shape == (bench.DUMP_SAMPLE,) and np.isin(sample, big.detach().numpy()).all()
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / f"G.{small_name}.npy"), small.detach().numpy().reshape(-1))
