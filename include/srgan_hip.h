@@ -172,6 +172,41 @@ int srgan_instnorm_bwd(const float* x, const float* dy, const float* scale, cons
                        float* dshift, int N, int HW, int C, int act, float slope,
                        void* ws, size_t ws_bytes, void* stream);
 
+/* Batch normalisation + activation (+ residual), norm_type="batch" (model.py:173-176).  NHWC fp32, C % 4 == 0.
+ *   BN  (nn.BatchNorm2d(C, affine=True), model.py:175; the encoder blocks' norm1 / norm2, model.py:404-408, and the
+ *        generator's up-path norms, model.py:236-246):  y = act((x - mu_c) * r_c * weight + bias)
+ *   CBB (CBBNorm2d, model.py:75-171; F.batch_norm then out - avgpool(out) + tanh(Linear(c)), model.py:118-140):
+ *        y = act((x - mu_nc) * r_c * scale[n,c] + shift[n,c]) (+ res), scale / shift from srgan_cbin_affine_fwd
+ * mu_c / var_c: biased batch statistics over (n, h, w); mu_nc: the image's channel mean; r_c = (var_c + eps)^-1/2.
+ * training != 0: batch statistics; with running_mean / running_var given they are updated on the device
+ *   (running = (1 - f) * running + f * stat, the variance unbiased by M / (M - 1), M = N * HW) and num_batches_tracked
+ *   (int64, may be null unless cumulative) is advanced; f = momentum, or 1 / num_batches_tracked when cumulative
+ *   (momentum=None), read on the device.  training == 0: running_mean / running_var stand in (required).  M <= 1 in
+ *   training is an error ("Expected more than 1 value per channel when training", F.batch_norm).
+ * Outputs kept for the backward: mean / rstd [C] (the statistics used), m / a / b [N*C] (y = act((x - m) * a + b)).
+ * Deterministic: fixed-order reductions, no atomics.  ws: srgan_batchnorm_workspace(N, HW, C) bytes (forward and backward). */
+size_t srgan_batchnorm_workspace(int N, int HW, int C);
+int srgan_batchnorm_fwd(const float* x, const float* weight, const float* bias, float* y, float* mean, float* rstd,
+                        float* m, float* a, float* b, float* running_mean, float* running_var,
+                        long long* num_batches_tracked, int N, int HW, int C, int training, float momentum,
+                        int cumulative, float eps, int act, float slope, void* ws, size_t ws_bytes, void* stream);
+int srgan_cbbnorm_fwd(const float* x, const float* scale, const float* shift, const float* res, float* y, float* mean,
+                      float* rstd, float* m, float* a, float* b, float* running_mean, float* running_var,
+                      long long* num_batches_tracked, int N, int HW, int C, int training, float momentum,
+                      int cumulative, float eps, int act, float slope, void* ws, size_t ws_bytes, void* stream);
+/* Backward from the forward's mean / rstd / m / a / b (the activation mask is rebuilt from x): dx, and dweight / dbias [C]
+ * (BN) or dscale / dshift [N*C] (CBB, into srgan_cbin_affine_bwd).  training: the forward used batch statistics
+ * (autograd of F.batch_norm, model.py:130-132 and nn.BatchNorm2d); otherwise r_c is a constant.  dres is dy itself.
+ * BN: `weight` (may be null: 1) is read when the backward RUNS -- nn.BatchNorm2d's autograd holds it by reference, so a
+ * backward through a graph recorded before an optimiser step sees the updated weight (the reference's train step does this,
+ * util_notebook.py:664-690); CBB's scale is the forward-time affine (model.py:136-138 multiplies by a weight.repeat copy). */
+int srgan_batchnorm_bwd(const float* x, const float* dy, const float* weight, const float* mean, const float* rstd,
+                        const float* m, const float* a, const float* b, float* dx, float* dweight, float* dbias, int N,
+                        int HW, int C, int training, int act, float slope, void* ws, size_t ws_bytes, void* stream);
+int srgan_cbbnorm_bwd(const float* x, const float* dy, const float* scale, const float* mean, const float* rstd,
+                      const float* m, const float* a, const float* b, float* dx, float* dscale, float* dshift, int N,
+                      int HW, int C, int training, int act, float slope, void* ws, size_t ws_bytes, void* stream);
+
 /* Central-biasing affine of _CBINorm.forward (model.py:54-67): t = tanh(c W^T + b);
  * scale[n,ch] = gamma[ch]; shift[n,ch] = t*gamma + beta.  c:[N,num_con] W:[C,num_con]. */
 int srgan_cbin_affine_fwd(const float* c, const float* W, const float* b, const float* gamma,

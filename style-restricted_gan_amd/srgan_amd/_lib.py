@@ -97,6 +97,11 @@ SIGNATURES = {
     "srgan_instnorm_workspace": (c_size_t, [c_int, c_int, c_int]),
     "srgan_instnorm_fwd": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_float, c_int, c_float, P, c_size_t, P]),
     "srgan_instnorm_bwd": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, c_size_t, P]),
+    "srgan_batchnorm_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "srgan_batchnorm_fwd": (c_int, [P] * 12 + [c_int, c_int, c_int, c_int, c_float, c_int, c_float, c_int, c_float, P, c_size_t, P]),
+    "srgan_cbbnorm_fwd": (c_int, [P] * 13 + [c_int, c_int, c_int, c_int, c_float, c_int, c_float, c_int, c_float, P, c_size_t, P]),
+    "srgan_batchnorm_bwd": (c_int, [P] * 11 + [c_int, c_int, c_int, c_int, c_int, c_float, P, c_size_t, P]),
+    "srgan_cbbnorm_bwd": (c_int, [P] * 11 + [c_int, c_int, c_int, c_int, c_int, c_float, P, c_size_t, P]),
     "srgan_cbin_affine_fwd": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, P]),
     "srgan_cbin_affine_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, P, c_size_t, P]),
     "srgan_cbin_rec_bytes": (c_size_t, []),

@@ -21,7 +21,7 @@ import torch.nn as nn
 from . import _lib, ops
 from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, PAD_REFLECT, PAD_ZERO
 
-__all__ = ["CBINorm2d", "get_norm_layer", "SingleResidualBlock", "SingleGenerator",
+__all__ = ["CBINorm2d", "CBBNorm2d", "BatchNorm2d", "get_norm_layer", "per_sample", "SingleResidualBlock", "SingleGenerator",
            "SingleDiscriminator_original", "SingleDiscriminator_original_multi", "SingleDiscriminator_solo",
            "SingleDiscriminator_solo_multi", "BasicBlock", "Encoder_original", "BasicBlock_classification",
            "Encoder", "Encoder_classifier", "MinMax"]
@@ -206,10 +206,10 @@ class _AvgPool2(nn.Module):
         return ops.avgpool2(x)
 
 
-def _block_io16(x, conv1, conv2):
+def _block_io16(x, conv1, conv2, norm=None):
     """Can an encoder block (norm -> conv1 -> norm -> conv2 -> pool) keep its four intermediates in bf16?  Both convolutions and
-    both norms must be served for THIS shape (each by its own geometry)."""
-    if not x.is_cuda or ops.get_compute_dtype() != "bf16":
+    both norms must be served for THIS shape (each by its own geometry); never around batch norms (fp32 storage only)."""
+    if not x.is_cuda or ops.get_compute_dtype() != "bf16" or _is_batch_stat(norm):
         return False
     # (asked on every forward: the answer depends on the geometry and the switches only)
     key = (tuple(x.shape), tuple(conv1.weight.shape), conv1.weight.stride(), tuple(conv2.weight.shape), conv2.weight.stride(),
@@ -282,15 +282,118 @@ class PrecomputedCon:
         self.affine = {id(l): a for l, a in zip(layers, affs)}
 
 
+# ------------------------------------------------------------------------------------------------
+# batch-statistics norms                 (reference: _CBBNorm / CBBNorm2d, model.py:75-171; nn.BatchNorm2d, model.py:175)
+# ------------------------------------------------------------------------------------------------
+class BatchNorm2d(nn.BatchNorm2d):
+    """nn.BatchNorm2d (signature, parameters, buffers, state-dict versioning and initialisation are torch's own); forward =
+    the batch-norm kernels (ops.batch_norm_act) with a fused activation.  The running buffers are updated on the device and
+    num_batches_tracked is advanced there too (momentum=None reads it on the device: no host synchronisation)."""
+
+    def forward(self, x, act=ACT_NONE, slope=0.0, out_bf16=False):
+        self._check_input_dim(x)
+        if out_bf16 or x.dtype == torch.bfloat16:
+            raise ValueError("BatchNorm2d: no 16-bit activation storage around batch norms")
+        track = self.training and self.track_running_stats
+        use_buffers = not self.training or self.track_running_stats
+        batch_stats = self.training or (self.running_mean is None and self.running_var is None)
+        return ops.batch_norm_act(x, self.weight, self.bias, self.running_mean if use_buffers else None,
+                                  self.running_var if use_buffers else None, self.num_batches_tracked if track else None,
+                                  batch_stats, self.momentum, self.eps, act, slope)
+
+
+class CBBNorm2d(nn.Module):
+    """Central-biasing batch norm: (BN(x) - avgpool(BN(x)) + tanh(Linear(c))) * weight + bias, i.e.
+    ((x - mu_nc) * r_c) * scale[n,c] + shift[n,c] with CBINorm2d's affine (scale = weight, shift = tanh(cW^T + b) * weight + bias):
+    the per-image mean comes out of the same slab pass, r_c from the batch (training) or running variance."""
+
+    _version = 1          # as the reference's Module subclass: a checkpoint without num_batches_tracked loads it as 0
+
+    def __init__(self, num_features, num_con, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True):
+        super().__init__()
+        self.num_features, self.num_con = num_features, num_con
+        self.eps, self.momentum = eps, momentum
+        self.affine, self.track_running_stats = affine, track_running_stats
+        if affine:
+            self.weight = nn.Parameter(torch.Tensor(num_features))
+            self.bias = nn.Parameter(torch.Tensor(num_features))
+        else:
+            self.register_parameter("weight", None)
+            self.register_parameter("bias", None)
+        if track_running_stats:
+            self.register_buffer("running_mean", torch.zeros(num_features))
+            self.register_buffer("running_var", torch.ones(num_features))
+            self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+        else:
+            self.register_parameter("running_mean", None)
+            self.register_parameter("running_var", None)
+            self.register_parameter("num_batches_tracked", None)
+        self.reset_parameters()                           # weight.uniform_() draws BEFORE the Linear is built (model.py:99-100)
+        self.ConBias = nn.Sequential(_Linear(num_con, num_features), _Tanh())
+        self.avgpool = nn.AdaptiveAvgPool2d(1)            # (parameter-free; folded into the kernels)
+
+    def reset_running_stats(self):
+        if self.track_running_stats:
+            self.running_mean.zero_()
+            self.running_var.fill_(1)
+            self.num_batches_tracked.zero_()
+
+    def reset_parameters(self):
+        self.reset_running_stats()
+        if self.affine:
+            with torch.no_grad():
+                self.weight.uniform_()
+                self.bias.zero_()
+
+    def extra_repr(self):
+        return '{num_features}, eps={eps}, momentum={momentum}, affine={affine}, ' \
+               'track_running_stats={track_running_stats}'.format(**self.__dict__)
+
+    def _check_input_dim(self, input):
+        if input.dim() != 4:
+            raise ValueError('expected 4D input (got {}D input)'.format(input.dim()))
+
+    def _load_from_state_dict(self, state_dict, prefix, metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        # the reference's version handling (model.py:153-166); its super() call names an undefined class there, here it loads
+        version = metadata.get("version", None)
+        if (version is None or version < 2) and self.track_running_stats:
+            key = prefix + "num_batches_tracked"
+            if key not in state_dict:
+                state_dict[key] = torch.tensor(0, dtype=torch.long)
+        super()._load_from_state_dict(state_dict, prefix, metadata, strict, missing_keys, unexpected_keys, error_msgs)
+
+    def forward(self, input, ConInfor, act=ACT_NONE, slope=0.0, res=None, out_bf16=False):
+        self._check_input_dim(input)
+        if out_bf16 or input.dtype == torch.bfloat16:
+            raise ValueError("CBBNorm2d: no 16-bit activation storage around batch norms")
+        scale, shift = self.scale_shift(ConInfor, input.device)
+        track = self.training and self.track_running_stats
+        return ops.cbb_norm_act(input, scale, shift, self.running_mean, self.running_var,
+                                self.num_batches_tracked if track else None, self.training or not self.track_running_stats,
+                                self.momentum, self.eps, act, slope, res)
+
+    scale_shift = CBINorm2d.scale_shift
+    affine_params = CBINorm2d.affine_params
+
+
+def _is_batch_stat(m):
+    return isinstance(m, (nn.modules.batchnorm._BatchNorm, CBBNorm2d))
+
+
+def per_sample(net):
+    """True when no module of ``net`` normalises with batch statistics: each output row then depends on its own input row only,
+    and running several calls as one concatenated batch is exact (the trainer's batched sites)."""
+    return not any(_is_batch_stat(m) for m in net.modules())
+
+
 def get_norm_layer(layer_type='instance', num_con=2):
     """(norm_layer, c_norm_layer) factories, as model.py:173-182."""
     if layer_type == 'instance':
         norm_layer = functools.partial(_InstanceNorm2d, affine=False)
         c_norm_layer = functools.partial(CBINorm2d, affine=True, num_con=num_con)
     elif layer_type == 'batch':
-        # dead code in the reference (CBBNorm2d._load_from_state_dict references an undefined name,
-        # model.py:163; no notebook passes norm_type="batch") -- out of scope, SURVEY.md section 2 row 1
-        raise NotImplementedError('normalization layer [batch] is out of scope of the MI355X path')
+        norm_layer = functools.partial(BatchNorm2d, affine=True)
+        c_norm_layer = functools.partial(CBBNorm2d, affine=True, num_con=num_con)
     else:
         raise NotImplementedError('normalization layer [%s] is not found' % layer_type)
     return norm_layer, c_norm_layer
@@ -324,7 +427,7 @@ class SingleResidualBlock(nn.Module):
         # the block input feeds c1 and the skip connection: conv2d_skip routes the skip path's gradient into c1's
         # input-gradient kernel (added in its epilogue) instead of a separate accumulation pass
         y1, skip = ops.conv2d_skip(data, self.c1.weight, None, self.c1.stride[0], self.c1.padding[0], PAD_ZERO)
-        if ops.norm_act_conv_fusable(y1, self.c2.weight):
+        if isinstance(self.cn1, CBINorm2d) and ops.norm_act_conv_fusable(y1, self.c2.weight):
             # cn1 + ReLU + c2 without the normalised tensor: the norm kernel writes c2's transformed-input image directly
             self.cn1._check_input_dim(y1)
             scale, shift = self.cn1.scale_shift(con, y1.device)
@@ -361,6 +464,7 @@ class SingleGenerator(nn.Module):
         ups.append(_Conv2d(nch, nch_out, kernel_size=7, stride=1, padding=3, bias=False))
         self.up_convs = nn.ModuleList(ups)
         self.up_norms = nn.ModuleList(norms)
+        self._per_sample = per_sample(self)
 
     def forward(self, x, c):
         if c.is_cuda and not _lib.ab("SRGAN_NO_CBIN_MULTI"):
@@ -370,7 +474,8 @@ class SingleGenerator(nn.Module):
         # takes the ordinary fp32 path.  io[i]: down conv i (i >= 1) takes and writes bf16.
         n, _, h, w = x.shape
         io = [False] * (self.num_cls + 2)
-        if x.is_cuda and ops.get_compute_dtype() == "bf16":
+        s16 = self._per_sample                   # 16-bit storage decisions are off around batch norms (fp32 tensors only)
+        if s16 and x.is_cuda and ops.get_compute_dtype() == "bf16":
             hh, ww = h, w
             for i in range(1, self.num_cls + 1):
                 cv = self.down_convs[i]
@@ -381,7 +486,7 @@ class SingleGenerator(nn.Module):
         # round 6: the 64-channel side of the two 7x7 RGB layers too -- the first conv writes bf16 for norm 0, the last norm
         # writes bf16 for the RGB head (ops.conv2d_act_io with (k, stride, pad) = (7, 1, 3); the 3-channel side stays fp32)
         cv0, cvl = self.down_convs[0], self.up_convs[-1]
-        rgb16 = [x.is_cuda and cv.kernel_size == (7, 7) and cv.bias is None and
+        rgb16 = [s16 and x.is_cuda and cv.kernel_size == (7, 7) and cv.bias is None and
                  ops.conv_act_io_applicable(n, cv.in_channels, h, w, cv.weight, ACT_NONE, 7, 1, 3) and
                  ops.norm_io_applicable(n, ch, h, w) for cv, ch in ((cv0, cv0.out_channels), (cvl, cvl.in_channels))]
         for i in range(self.num_cls + 1):
@@ -394,7 +499,7 @@ class SingleGenerator(nn.Module):
         n, _, h, w = x.shape
         iot = [False] * (self.num_cls + 1)
         nio = [False] * (self.num_cls + 1)       # norm i can run on the 16-bit I/O kernels (its OWN shape: ADVICE r4)
-        if x.is_cuda and ops.get_compute_dtype() == "bf16":
+        if s16 and x.is_cuda and ops.get_compute_dtype() == "bf16":
             hh, ww = h, w
             for i in range(self.num_cls):
                 cv = self.up_convs[i]
@@ -410,6 +515,7 @@ class SingleGenerator(nn.Module):
         if x.dtype == torch.bfloat16:
             return ops.tanh(ops.conv2d_act_io(x, cvl.weight, ACT_NONE, 0.0, False, 7, 1, 3))
         return ops.tanh(self.up_convs[-1](x))
+
 
 
 # ------------------------------------------------------------------------------------------------
@@ -585,7 +691,7 @@ class BasicBlock_classification(nn.Module):
         x = input
         with _side_branch(x) as fork:        # pool + 1x1 conv: a few small launches beside the main path's large ones
             sc = self.shortcut(x)
-        if _block_io16(x, self.conv1, self.cmp[0]):
+        if _block_io16(x, self.conv1, self.cmp[0], self.norm1):
             h = self.conv1.forward_io(self.norm1(x, ACT_LRELU, self.nl1.negative_slope, out_bf16=True))
             h = self.cmp[0].forward_io(self.norm2(h, ACT_LRELU, self.nl2.negative_slope, out_bf16=True))
             h = self.cmp[1](h)
@@ -615,7 +721,7 @@ class BasicBlock(nn.Module):
         x, d = input
         with _side_branch(x) as fork:
             sc = self.shortcut(x)
-        if _block_io16(x, self.conv1, self.cmp[0]):
+        if _block_io16(x, self.conv1, self.cmp[0], self.cnorm1):
             h = self.conv1.forward_io(self.cnorm1(x, d, ACT_LRELU, self.nl1.negative_slope, out_bf16=True))
             h = self.cmp[0].forward_io(self.cnorm2(h, d, ACT_LRELU, self.nl2.negative_slope, out_bf16=True))
             h = self.cmp[1](h)

@@ -816,6 +816,143 @@ def instance_norm_act(x, scale=None, shift=None, res=None, act=ACT_NONE, slope=0
     return _InstNormFn.apply(x, scale, shift, res, act, slope, eps)
 
 
+# ------------------------------------------------------------------------------------------
+# batch norm (norm_type="batch"): nn.BatchNorm2d and CBBNorm2d (csrc/norm_batch.hip)
+# ------------------------------------------------------------------------------------------
+def _bn_check(x, training, what):
+    n, c, h, w = x.shape
+    if c % 4:
+        raise _lib.SrganHipError(f"{what}: C = {c} is not a multiple of 4 (the batch-norm kernels read channels four at a time)")
+    if training and n * h * w <= 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(list(x.shape)))
+
+
+def _bn_buffers(running_mean, running_var, num_batches_tracked, training, momentum):
+    """(running_mean, running_var, counter, cumulative, momentum) as the kernels take them: the buffers only where they are read or
+    updated (F.batch_norm: updated in training when given, read in eval)."""
+    if running_mean is None:
+        return None, None, None, 0, 0.0
+    cumulative = momentum is None
+    if cumulative and num_batches_tracked is None:
+        raise ValueError("batch norm with momentum=None needs num_batches_tracked")
+    return running_mean, running_var, num_batches_tracked, int(cumulative), 0.0 if cumulative else float(momentum)
+
+
+def _bn_stats(n, c, device):
+    mean = torch.empty(c, dtype=torch.float32, device=device)
+    return mean, torch.empty_like(mean), *(torch.empty(n * c, dtype=torch.float32, device=device) for _ in range(3))
+
+
+class _BatchNormFn(Function):
+    """act((x - mu_c) * r_c * weight + bias) with batch statistics (training) or the running ones.  Saves x and the statistics
+    the forward used -- never the running buffers, which later forwards move on the device.  The weight is held by reference and
+    read when backward RUNS (nn.BatchNorm2d's autograd saves it by reference: the stale-graph rule of the convolutions); the
+    activation mask comes from the forward's own folded coefficients a / b."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps, act, slope):
+        _require_gpu(x, "batch_norm")
+        x = to_nhwc(x)
+        n, c, h, w = x.shape
+        _bn_check(x, training, "batch_norm")
+        rm, rv, nbt, cumulative, mom = _bn_buffers(running_mean, running_var, num_batches_tracked, training, momentum)
+        if not training and rm is None:
+            raise ValueError("batch_norm: eval mode needs running statistics")
+        lib = _lib.load()
+        y = torch.empty_like(x)
+        mean, rstd, m, a, b = _bn_stats(n, c, x.device)
+        nb = lib.srgan_batchnorm_workspace(n, h * w, c)
+        ws = workspace(x.device, nb)
+        _lib.check(lib.srgan_batchnorm_fwd(_ptr(x), _ptr(weight), _ptr(bias), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(m), _ptr(a),
+                                           _ptr(b), _ptr(rm), _ptr(rv), _ptr(nbt), n, h * w, c, int(bool(training)), mom, cumulative,
+                                           float(eps), act, float(slope), _ptr(ws), nb, _stream()), "batchnorm_fwd")
+        ctx.act, ctx.slope, ctx.training = act, slope, bool(training)
+        ctx.has_affine = weight is not None
+        ctx.weight = weight                    # by reference: read at backward time
+        ctx.save_for_backward(x, mean, rstd, m, a, b)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, mean, rstd, m, a, b = ctx.saved_tensors
+        gy = to_nhwc(gy)
+        n, c, h, w = x.shape
+        lib = _lib.load()
+        dx = torch.empty_like(x)
+        dweight = torch.empty(c, dtype=torch.float32, device=x.device)
+        dbias = torch.empty_like(dweight)
+        nb = lib.srgan_batchnorm_workspace(n, h * w, c)
+        ws = workspace(x.device, nb)
+        _lib.check(lib.srgan_batchnorm_bwd(_ptr(x), _ptr(gy), _ptr(ctx.weight), _ptr(mean), _ptr(rstd), _ptr(m), _ptr(a), _ptr(b), _ptr(dx),
+                                           _ptr(dweight), _ptr(dbias), n, h * w, c, int(ctx.training), ctx.act, float(ctx.slope),
+                                           _ptr(ws), nb, _stream()), "batchnorm_bwd")
+        if not ctx.has_affine:
+            dweight = dbias = None
+        return dx, dweight, dbias, None, None, None, None, None, None, None, None
+
+
+def batch_norm_act(x, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum=0.1, eps=1e-5,
+                   act=ACT_NONE, slope=0.0):
+    """nn.BatchNorm2d + activation: act((x - mu_c) / sqrt(var_c + eps) * weight + bias).  training: batch statistics, and the
+    running buffers (if given) are updated on the device; otherwise the running buffers are used."""
+    return _BatchNormFn.apply(x, weight, bias, running_mean, running_var, num_batches_tracked, bool(training), momentum, eps,
+                              act, slope)
+
+
+class _CbbNormFn(Function):
+    """CBBNorm2d: act((x - mu_nc) * r_c * scale[n,c] + shift[n,c]) (+ res), r_c from the batch (training) or running variance.
+    scale / shift: CBIN's affine (cbin_affine / PrecomputedCon), whose backward takes dscale / dshift unchanged."""
+
+    @staticmethod
+    def forward(ctx, x, scale, shift, running_mean, running_var, num_batches_tracked, training, momentum, eps, act, slope, res):
+        _require_gpu(x, "cbb_norm")
+        x = to_nhwc(x)
+        n, c, h, w = x.shape
+        _bn_check(x, training, "cbb_norm")
+        rm, rv, nbt, cumulative, mom = _bn_buffers(running_mean, running_var, num_batches_tracked, training, momentum)
+        if not training and rm is None:
+            raise ValueError("cbb_norm: eval mode needs running statistics")
+        if res is not None:
+            res = to_nhwc(res)
+        scale, shift = _dense2d(scale), _dense2d(shift)
+        lib = _lib.load()
+        y = torch.empty_like(x)
+        mean, rstd, m, a, b = _bn_stats(n, c, x.device)
+        nb = lib.srgan_batchnorm_workspace(n, h * w, c)
+        ws = workspace(x.device, nb)
+        _lib.check(lib.srgan_cbbnorm_fwd(_ptr(x), _ptr(scale), _ptr(shift), _ptr(res), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(m),
+                                         _ptr(a), _ptr(b), _ptr(rm), _ptr(rv), _ptr(nbt), n, h * w, c, int(bool(training)), mom,
+                                         cumulative, float(eps), act, float(slope), _ptr(ws), nb, _stream()), "cbbnorm_fwd")
+        ctx.act, ctx.slope, ctx.training, ctx.has_res = act, slope, bool(training), res is not None
+        ctx.save_for_backward(x, scale, mean, rstd, m, a, b)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, scale, mean, rstd, m, a, b = ctx.saved_tensors
+        gy = to_nhwc(gy)
+        n, c, h, w = x.shape
+        lib = _lib.load()
+        dx = torch.empty_like(x)
+        dscale = torch.empty(n, c, dtype=torch.float32, device=x.device)
+        dshift = torch.empty_like(dscale)
+        nb = lib.srgan_batchnorm_workspace(n, h * w, c)
+        ws = workspace(x.device, nb)
+        _lib.check(lib.srgan_cbbnorm_bwd(_ptr(x), _ptr(gy), _ptr(scale), _ptr(mean), _ptr(rstd), _ptr(m), _ptr(a), _ptr(b),
+                                         _ptr(dx), _ptr(dscale), _ptr(dshift), n, h * w, c, int(ctx.training), ctx.act,
+                                         float(ctx.slope), _ptr(ws), nb, _stream()), "cbbnorm_bwd")
+        return (dx, dscale, dshift, None, None, None, None, None, None, None, None,
+                (gy.clone() if _DEBUG_CLONE else gy) if ctx.has_res else None)
+
+
+def cbb_norm_act(x, scale, shift, running_mean, running_var, num_batches_tracked, training, momentum=0.1, eps=1e-5,
+                 act=ACT_NONE, slope=0.0, res=None):
+    """CBBNorm2d + activation (+ residual): act((x - mu_nc) / sqrt(var_c + eps) * scale[n,c] + shift[n,c]) (+ res), the reference's
+    (F.batch_norm(x) - avgpool(F.batch_norm(x)) + tanh(Linear(c))) * weight + bias."""
+    return _CbbNormFn.apply(x, scale, shift, running_mean, running_var, num_batches_tracked, bool(training), momentum, eps, act,
+                            slope, res)
+
+
 class _NormActConvFn(Function):
     """conv3x3(act(instance_norm(x) * scale + shift), weight) for a 32x32 map feeding an F(4x4,3x3) layer, without the
     normalised tensor: the norm kernel writes the convolution's transformed-input (V) image directly

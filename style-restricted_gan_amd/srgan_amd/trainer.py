@@ -28,7 +28,7 @@ import torch.optim as optim
 
 from . import _lib, dp, ops
 from .losses import class_encode, get_domainloss_D, get_loss_D, histogram_imitation
-from .model import SingleGenerator, _cpu_normal_like, host_to_device
+from .model import SingleGenerator, _cpu_normal_like, _is_batch_stat, host_to_device, per_sample
 from .optim import Adam
 
 __all__ = ["SRGAN_training", "SingleGAN_training"]
@@ -87,6 +87,15 @@ class SRGAN_training():
         self._g_active = False         # True while the step body reads its inputs from the static device buffers
         ref = np.asarray(ref_label)
         self._ref_is_onehot = ref.ndim == 2 and ref.shape[0] == ref.shape[1] and np.array_equal(ref, np.eye(ref.shape[0]))
+        # norm_type="batch": G / E normalise with batch statistics, so batching several of the reference's calls into one is a
+        # different computation (and a different number of running-buffer updates); those sites run call by call
+        self._g_per_sample = per_sample(dp.unwrap(self.G))
+        self._e_per_sample = per_sample(dp.unwrap(self.E))
+        if dp.world_size() > 1 and not (self._g_per_sample and self._e_per_sample):
+            raise NotImplementedError(
+                "SRGAN_training: G / E hold batch-statistics norms (norm_type='batch') and a process group has "
+                f"{dp.world_size()} ranks; nn.DataParallel gives per-replica statistics and rank-0 running buffers, which this "
+                "package does not build (one process, or norm_type='instance')")
 
     # ------------------------------------------------------------------------------------------
     def opt_sche_initialization(self, lr=[0.0001, 0.0001, 0.0001]):
@@ -298,7 +307,7 @@ class SRGAN_training():
         with _frozen(e_unused):
             feat = E.features(src) if hasattr(E, "features") else None
             source_enc_info = self._encode(src, feat)
-            pair = feat is not None and L["idt"] > 0
+            pair = feat is not None and L["idt"] > 0 and self._g_per_sample and self._e_per_sample
             # Recorded data-parallel step (round 4): phase 1 reaches the kept target_image graph LAST in its backward (autograd
             # runs the youngest nodes first and that graph was built in the last discriminator update) -- after E's gradients are
             # final.  The pass is cut there: phase 1 reads target_image through a detached alias, the first backward stops at the
@@ -351,7 +360,10 @@ class SRGAN_training():
 
             if L["idt"] > 0:
                 if not pair:
-                    identity_image, _ = self.G_transformation("source", src, True, src)
+                    # batch statistics: the reference's second E(source) is a train-mode forward of its own (it advances E's
+                    # running buffers again), then G(source) runs as its own batch
+                    info = self._encode(src, noise=self._noise("normal", src.shape[0])) if feat is not None else None
+                    identity_image, _ = self.G_transformation("source", src, True, src, _enc_info=info)
                 errG_idt = ops.l1_mean(src, identity_image, 1.0)
                 g_terms.append((errG_idt, L["idt"]))
                 rep_terms.append((errG_idt, L["idt"]))
@@ -400,7 +412,7 @@ class SRGAN_training():
         self._step(self.optE)
         do_idt_reg = L["idt_reg"] * L["idt"] > 0
         early_info = None
-        if redG is not None and do_idt_reg and self._fused_paths():
+        if redG is not None and do_idt_reg and self._fused_paths() and self._e_per_sample:
             nb = src.shape[0]
             early_noise = [self._noise("normal", nb) for _ in range(3)]     # reference order: E(target_image), E(source), E(idt_random_image)
             with _frozen(list(self.E.parameters())), torch.no_grad():
@@ -413,7 +425,21 @@ class SRGAN_training():
         self.G.zero_grad()
         self.E.zero_grad()
         with _frozen(list(self.E.parameters())):           # only optG steps: E's weight grads are discarded
-            if do_idt_reg and self._fused_paths():
+            if do_idt_reg and self._fused_paths() and not self._e_per_sample:
+                # batch statistics: E's three forwards one by one, in the reference's order (E(target_image), E(source),
+                # E(idt_random_image)) -- each normalises its own batch and advances the running buffers once
+                nb = src.shape[0]
+                n1, n2, n3 = (self._noise("normal", nb) for _ in range(3))
+                target_cenc = self._encode(self.target_image, noise=n1)[1]
+                with torch.no_grad():                       # its gradient only reaches E's parameters
+                    info = self._encode(src, noise=n2)
+                idt_random_image, info = self.G_transformation("source", src, True, src, _enc_info=info)
+                idt_cenc_rand = self._encode(idt_random_image, noise=n3)[1]
+                errG_reg = ops.l1_mean(self.c_rand, target_cenc, 1.0)
+                errG_idt_reg = ops.l1_mean(info[1], idt_cenc_rand, 1.0)
+                errG_ex = ops.lincomb([(errG_reg, L["reg"]), (errG_idt_reg, L["idt_reg"] * (L["idt"] / L["cycle"]))])
+                terms["errG_reg"], terms["errG_idt_reg"] = errG_reg, errG_idt_reg
+            elif do_idt_reg and self._fused_paths():
                 # reference order of the noise draws: E(target_image), E(source), E(idt_random_image)
                 nb = src.shape[0]
                 if early_info is not None:                  # (data parallel: drawn and encoded under G's all-reduce, above)
@@ -492,7 +518,7 @@ class SRGAN_training():
             errorG, errorE = self.update_GandE()
             return [errorG, errorD, errorE]
         fakes = []
-        if k > 1 and isinstance(dp.unwrap(self.G), SingleGenerator):     # per-sample network: batching is exact
+        if k > 1 and isinstance(dp.unwrap(self.G), SingleGenerator) and self._g_per_sample:   # per-sample network: batching is exact
             # the kernels address an activation with 32-bit byte offsets (< 4 GiB per tensor): translations are batched in
             # groups whose widest activation (the first conv's nch planes at full resolution) stays under that, e.g.
             # 256x256, B=64, k=5 runs as two groups of 2*B images instead of one of 4*B
@@ -621,6 +647,10 @@ class _StepGraph:
                     m, v = st.get("exp_avg"), st.get("exp_avg_sq")
                     fp.append((id(p), m.data_ptr() if m is not None else 0, v.data_ptr() if v is not None else 0))
         fp.append(tuple((id(p), p.data_ptr(), p.requires_grad) for p in self._all_params()))
+        # batch norms: train / eval mode, momentum and eps are baked into the recorded launches (the running buffers themselves are
+        # device state the step updates in place)
+        fp.append(tuple((id(m), m.training, m.momentum, m.eps, m.track_running_stats) for net in (sg.G, sg.E)
+                        for m in net.modules() if _is_batch_stat(m)))
         return tuple(fp)
 
     def _opt_steps(self):
