@@ -207,6 +207,45 @@ int srgan_cbbnorm_bwd(const float* x, const float* dy, const float* scale, const
                       const float* m, const float* a, const float* b, float* dx, float* dscale, float* dshift, int N,
                       int HW, int C, int training, int act, float slope, void* ws, size_t ws_bytes, void* stream);
 
+/* The same norms under data parallelism, with the statistics of the GLOBAL batch (training mode only).  This rank holds images
+ * [n0, n0 + N_local) of N_global, n0 = rank * N_local.  Each direction is split around one all-gather that the caller issues
+ * between the two calls (srgan_allgather_rows or any other transport), in place on the exchange buffer `xbuf`:
+ *   *_partial : this rank's per-(image, slab, channel) partials, with the slab plan of the GLOBAL batch, into its chunk of xbuf;
+ *   all-gather: chunk r of xbuf (xbuf_bytes / (N_global / N_local) bytes each) comes from rank r;
+ *   *_apply   : the one-process merge over all N_global images in the one-process order, then the elementwise pass on the local
+ *               images.  mean / rstd, the running buffers, y and dx are bit-identical to one process with N_global images.
+ * xbuf: srgan_batchnorm_sync_exchange_bytes(N_global, N_local, HW, C, with_scale) bytes, fp32; with_scale = 1 for the CBB
+ * backward (the chunk then ends in the rank's scale rows, which the other ranks' delta needs), 0 otherwise.  The backward's
+ * parameter gradients are sums over the LOCAL images (the gradient all-reduce averages them over the ranks); only the dx
+ * coefficients use the global sums.  x / y / dy / dx / res and m / a / b / scale / shift / dscale / dshift are the local
+ * images'.  ws (backward apply): srgan_batchnorm_sync_workspace(N_local, C) bytes.  Everything else as above. */
+size_t srgan_batchnorm_sync_exchange_bytes(int N_global, int N_local, int HW, int C, int with_scale);
+size_t srgan_batchnorm_sync_workspace(int N_local, int C);
+int srgan_batchnorm_sync_fwd_partial(const float* x, void* xbuf, size_t xbuf_bytes, int N_global, int n0, int N_local, int HW,
+                                     int C, void* stream);
+int srgan_batchnorm_sync_fwd_apply(const float* x, const float* weight, const float* bias, float* y, float* mean, float* rstd,
+                                   float* m, float* a, float* b, float* running_mean, float* running_var,
+                                   long long* num_batches_tracked, const void* xbuf, size_t xbuf_bytes, int N_global, int n0,
+                                   int N_local, int HW, int C, float momentum, int cumulative, float eps, int act, float slope,
+                                   void* stream);
+int srgan_cbbnorm_sync_fwd_apply(const float* x, const float* scale, const float* shift, const float* res, float* y,
+                                 float* mean, float* rstd, float* m, float* a, float* b, float* running_mean,
+                                 float* running_var, long long* num_batches_tracked, const void* xbuf, size_t xbuf_bytes,
+                                 int N_global, int n0, int N_local, int HW, int C, float momentum, int cumulative, float eps,
+                                 int act, float slope, void* stream);
+/* scale: CBB's [N_local * C] affine (then xbuf has the with_scale layout), null for BN */
+int srgan_batchnorm_sync_bwd_partial(const float* x, const float* dy, const float* scale, const float* rstd, const float* m,
+                                     const float* a, const float* b, void* xbuf, size_t xbuf_bytes, int N_global, int n0,
+                                     int N_local, int HW, int C, int act, float slope, void* stream);
+int srgan_batchnorm_sync_bwd_apply(const float* x, const float* dy, const float* weight, const float* mean, const float* rstd,
+                                   const float* m, const float* a, const float* b, const void* xbuf, size_t xbuf_bytes,
+                                   float* dx, float* dweight, float* dbias, int N_global, int n0, int N_local, int HW, int C,
+                                   int act, float slope, void* ws, size_t ws_bytes, void* stream);
+int srgan_cbbnorm_sync_bwd_apply(const float* x, const float* dy, const float* mean, const float* rstd, const float* m,
+                                 const float* a, const float* b, const void* xbuf, size_t xbuf_bytes, float* dx, float* dscale,
+                                 float* dshift, int N_global, int n0, int N_local, int HW, int C, int act, float slope, void* ws,
+                                 size_t ws_bytes, void* stream);
+
 /* Central-biasing affine of _CBINorm.forward (model.py:54-67): t = tanh(c W^T + b);
  * scale[n,ch] = gamma[ch]; shift[n,ch] = t*gamma + beta.  c:[N,num_con] W:[C,num_con]. */
 int srgan_cbin_affine_fwd(const float* c, const float* W, const float* b, const float* gamma,

@@ -12,6 +12,11 @@
 // num_batches_tracked.
 // Backward: per-slab {sum g, sum g * xh} partials (the activation mask rebuilt from (x - m) * a + b) -> a per-channel
 // combine -> the dx pass.  Formulas: DESIGN.md section 7.
+//
+// Data parallel (srgan_batchnorm_sync_*): a rank holds images [n0, n0 + Nl) of a global batch of N.  Its
+// slab passes run with the slab plan of the GLOBAL batch and write into the rank's chunk of an exchange buffer; after an
+// all-gather of the chunks the finalize / combine read the partials of all N images in the one-process order, so the merged
+// statistics are bit-identical to one process with N images.  Only this rank's images get coefficients.
 #include <algorithm>
 #include "common.h"
 
@@ -109,31 +114,44 @@ __device__ __forceinline__ float wave_sum_down(float v) {
   return v;
 }
 
+// Where image n's slab partials are.  One process: rows of a dense [N][S][C] array.  Synced: the exchange buffer, rank chunks of
+// Nl images each, `chunk` floats apart ([Nl][S][C] float2, then -- CBB backward -- the images' scale rows [Nl][C]).
+template <bool SYNC>
+__device__ __forceinline__ const float2* part_row(const float2* part, int n, int S, int C, int Nl, size_t chunk) {
+  if constexpr (SYNC)
+    return reinterpret_cast<const float2*>(reinterpret_cast<const float*>(part) + (size_t)(n / Nl) * chunk) + (size_t)(n % Nl) * S * C;
+  else
+    return part + (size_t)n * S * C;
+}
+
 // One WAVE per channel, its lanes over the images: merges the partials (slabs in order per image, then the lanes' images in a
 // fixed tree), updates the running buffers, writes the statistics the backward keeps (mean / rstd [C]) and the folded per-(n, c)
 // coefficients of the apply pass: y = act((x - m) * a + b).  part == null: eval-mode BN (running statistics only).  The
 // counter is READ here (the factor of momentum=None) and incremented by the apply pass, after every wave has read it.
-__global__ __launch_bounds__(256) void bn_finalize(const float2* __restrict__ part, const float* __restrict__ scale,
-                                                   const float* __restrict__ shift, float* __restrict__ mean,
-                                                   float* __restrict__ rstd, float* __restrict__ m, float* __restrict__ a,
-                                                   float* __restrict__ b, float* __restrict__ rmean, float* __restrict__ rvar,
-                                                   const long long* __restrict__ nbt, int N, int HW, int C, int S, int rps,
-                                                   int cbb, int batch_stats, int update, float momentum, int cumulative,
-                                                   float eps) {
+// SYNC: the merge runs over the N images of the global batch; scale / shift / m / a / b are those of images [n0, n0 + Nl).
+template <bool SYNC>
+__device__ __forceinline__ void bn_finalize_body(const float2* __restrict__ part, const float* __restrict__ scale,
+                                                 const float* __restrict__ shift, float* __restrict__ mean,
+                                                 float* __restrict__ rstd, float* __restrict__ m, float* __restrict__ a,
+                                                 float* __restrict__ b, float* __restrict__ rmean, float* __restrict__ rvar,
+                                                 const long long* __restrict__ nbt, int N, int HW, int C, int S, int rps,
+                                                 int cbb, int batch_stats, int update, float momentum, int cumulative,
+                                                 float eps, int n0, int Nl, size_t chunk) {
   const int lane = threadIdx.x & 63;
   const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (c >= C) return;
   float mu = 0.f, m2 = 0.f, cnt = 0.f;
   if (part) {
     for (int n = lane; n < N; n += 64) {
+      const float2* row = part_row<SYNC>(part, n, S, C, Nl, chunk);
       float mn = 0.f, m2n = 0.f, cn = 0.f;
       for (int s = 0; s < S; ++s) {
         const int r0 = s * rps, r1 = min(HW, r0 + rps);
         if (r1 <= r0) continue;
-        const float2 p = part[((size_t)n * S + s) * C + c];
+        const float2 p = row[(size_t)s * C + c];
         chan_merge(mn, m2n, cn, p.x, p.y, (float)(r1 - r0));
       }
-      if (cbb) m[n * C + c] = mn;
+      if (cbb && n >= n0 && n < n0 + Nl) m[(n - n0) * C + c] = mn;
       chan_merge(mu, m2, cnt, mn, m2n, cn);
     }
     wave_chan_merge(mu, m2, cnt);
@@ -158,7 +176,7 @@ __global__ __launch_bounds__(256) void bn_finalize(const float2* __restrict__ pa
       rvar[c] = (1.f - f) * rvar[c] + f * (m2 / (cnt - 1.f));
     }
   }
-  for (int n = lane; n < N; n += 64) {
+  for (int n = lane; n < Nl; n += 64) {
     const int nc = n * C + c;
     if (cbb) {                               // (x - mu_nc) * r_c * scale + shift
       a[nc] = rs * scale[nc];
@@ -169,6 +187,29 @@ __global__ __launch_bounds__(256) void bn_finalize(const float2* __restrict__ pa
       b[nc] = shift ? shift[c] : 0.f;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void bn_finalize(const float2* __restrict__ part, const float* __restrict__ scale,
+                                                   const float* __restrict__ shift, float* __restrict__ mean,
+                                                   float* __restrict__ rstd, float* __restrict__ m, float* __restrict__ a,
+                                                   float* __restrict__ b, float* __restrict__ rmean, float* __restrict__ rvar,
+                                                   const long long* __restrict__ nbt, int N, int HW, int C, int S, int rps,
+                                                   int cbb, int batch_stats, int update, float momentum, int cumulative,
+                                                   float eps) {
+  bn_finalize_body<false>(part, scale, shift, mean, rstd, m, a, b, rmean, rvar, nbt, N, HW, C, S, rps, cbb, batch_stats, update,
+                          momentum, cumulative, eps, 0, N, 0);
+}
+
+// the synced finalize: training mode only (batch statistics of the global batch)
+__global__ __launch_bounds__(256) void bn_sync_finalize(const float2* __restrict__ part, const float* __restrict__ scale,
+                                                        const float* __restrict__ shift, float* __restrict__ mean,
+                                                        float* __restrict__ rstd, float* __restrict__ m, float* __restrict__ a,
+                                                        float* __restrict__ b, float* __restrict__ rmean,
+                                                        float* __restrict__ rvar, const long long* __restrict__ nbt, int N,
+                                                        int HW, int C, int S, int rps, int cbb, int update, float momentum,
+                                                        int cumulative, float eps, int n0, int Nl, size_t chunk) {
+  bn_finalize_body<true>(part, scale, shift, mean, rstd, m, a, b, rmean, rvar, nbt, N, HW, C, S, rps, cbb, 1, update, momentum,
+                         cumulative, eps, n0, Nl, chunk);
 }
 
 // y = act((x - m[n,c]) * a[n,c] + b[n,c]) (+ res), float4 per lane; grid (x: strides over one image, y: image), so the
@@ -242,34 +283,52 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(const float* __restrict__ 
 //   BN : alpha = weight[c] * r_c with the weight read NOW (nn.BatchNorm2d's autograd holds it by reference: the stale-graph
 //        rule of the convolutions); dbeta / dgamma per channel; k = -alpha * dbeta / M; delta = -alpha * dgamma / M.
 //   Eval statistics: the batch terms vanish.
-__global__ __launch_bounds__(256) void bn_bwd_combine(const float2* __restrict__ part, const float* __restrict__ scale,
-                                                      const float* __restrict__ weight, const float* __restrict__ a,
-                                                      const float* __restrict__ rstd, float* __restrict__ dscale,
-                                                      float* __restrict__ dshift, float* __restrict__ alpha,
-                                                      float* __restrict__ kcoef, float* __restrict__ delta, int N, int HW,
-                                                      int C, int S, int cbb, int batch_stats) {
+//   SYNC: the sums over the batch that enter dx (k, delta) run over the N images of the global batch, in the one-process order;
+//        the parameter gradients stay sums over THIS rank's images [n0, n0 + Nl) (dp.GradReducer averages them over the ranks,
+//        and every rank's loss is a mean over its own rows).  CBB's delta needs the other ranks' scale: it travels in the
+//        exchange buffer behind the partials, and the product scale * dscale is formed here exactly as one process forms it.
+template <bool SYNC>
+__device__ __forceinline__ void bn_bwd_combine_body(const float2* __restrict__ part, const float* __restrict__ scale,
+                                                    const float* __restrict__ weight, const float* __restrict__ a,
+                                                    const float* __restrict__ rstd, float* __restrict__ dscale,
+                                                    float* __restrict__ dshift, float* __restrict__ alpha,
+                                                    float* __restrict__ kcoef, float* __restrict__ delta, int N, int HW,
+                                                    int C, int S, int cbb, int batch_stats, int n0, int Nl, size_t chunk) {
   const int lane = threadIdx.x & 63;
   const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (c >= C) return;
   const float M = (float)N * (float)HW;
-  float sg = 0.f, sgx = 0.f, T = 0.f;
+  float sg = 0.f, sgx = 0.f, T = 0.f, lg = 0.f, lgx = 0.f;
   for (int n = lane; n < N; n += 64) {
+    const float2* row = part_row<SYNC>(part, n, S, C, Nl, chunk);
     float tg = 0.f, tgx = 0.f;
     for (int s = 0; s < S; ++s) {
-      const float2 p = part[((size_t)n * S + s) * C + c];
+      const float2 p = row[(size_t)s * C + c];
       tg += p.x;
       tgx += p.y;
     }
+    const bool mine = n >= n0 && n < n0 + Nl;
     if (cbb) {
-      const int nc = n * C + c;
-      dshift[nc] = tg;
-      dscale[nc] = tgx;
-      alpha[nc] = a[nc];
-      kcoef[nc] = -a[nc] * (tg / (float)HW);
-      T += scale[nc] * tgx;
+      if (mine) {
+        const int nc = (n - n0) * C + c;
+        dshift[nc] = tg;
+        dscale[nc] = tgx;
+        alpha[nc] = a[nc];
+        kcoef[nc] = -a[nc] * (tg / (float)HW);
+      }
+      float sc;
+      if constexpr (SYNC)      // the scale rows behind the chunk's partials
+        sc = (reinterpret_cast<const float*>(part) + (size_t)(n / Nl) * chunk + (size_t)Nl * S * C * 2)[(size_t)(n % Nl) * C + c];
+      else
+        sc = scale[n * C + c];
+      T += sc * tgx;
     } else {
       sg += tg;
       sgx += tgx;
+      if (SYNC && mine) {
+        lg += tg;
+        lgx += tgx;
+      }
     }
   }
   if (cbb) {
@@ -279,16 +338,48 @@ __global__ __launch_bounds__(256) void bn_bwd_combine(const float2* __restrict__
   }
   sg = __shfl(wave_sum_down(sg), 0, 64);
   sgx = __shfl(wave_sum_down(sgx), 0, 64);
+  if constexpr (SYNC) {
+    lg = wave_sum_down(lg);
+    lgx = wave_sum_down(lgx);
+  } else {
+    lg = sg;
+    lgx = sgx;
+  }
   const float ac = weight ? weight[c] * rstd[c] : rstd[c];      // the same for every image
   if (lane == 0) {
-    dshift[c] = sg;
-    dscale[c] = sgx;
+    dshift[c] = lg;
+    dscale[c] = lgx;
     delta[c] = batch_stats ? -ac * (sgx / M) : 0.f;
   }
-  for (int n = lane; n < N; n += 64) {
+  for (int n = lane; n < Nl; n += 64) {
     alpha[n * C + c] = ac;
     kcoef[n * C + c] = batch_stats ? -ac * (sg / M) : 0.f;
   }
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_combine(const float2* __restrict__ part, const float* __restrict__ scale,
+                                                      const float* __restrict__ weight, const float* __restrict__ a,
+                                                      const float* __restrict__ rstd, float* __restrict__ dscale,
+                                                      float* __restrict__ dshift, float* __restrict__ alpha,
+                                                      float* __restrict__ kcoef, float* __restrict__ delta, int N, int HW,
+                                                      int C, int S, int cbb, int batch_stats) {
+  bn_bwd_combine_body<false>(part, scale, weight, a, rstd, dscale, dshift, alpha, kcoef, delta, N, HW, C, S, cbb, batch_stats, 0, N,
+                             0);
+}
+
+__global__ __launch_bounds__(256) void bn_sync_bwd_combine(const float2* __restrict__ part, const float* __restrict__ weight,
+                                                           const float* __restrict__ a, const float* __restrict__ rstd,
+                                                           float* __restrict__ dscale, float* __restrict__ dshift,
+                                                           float* __restrict__ alpha, float* __restrict__ kcoef,
+                                                           float* __restrict__ delta, int N, int HW, int C, int S, int cbb,
+                                                           int n0, int Nl, size_t chunk) {
+  bn_bwd_combine_body<true>(part, nullptr, weight, a, rstd, dscale, dshift, alpha, kcoef, delta, N, HW, C, S, cbb, 1, n0, Nl, chunk);
+}
+
+// CBB backward, phase 1: this rank's scale rows [Nl][C] into its chunk of the exchange buffer (four channels per lane)
+__global__ __launch_bounds__(256) void bn_sync_pack_scale(const float* __restrict__ scale, float* __restrict__ dst, int count) {
+  const int i = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i < count) *reinterpret_cast<f32x4*>(dst + i) = ldf4(scale, i);
 }
 
 // the activation mask from the forward's own coefficients (m, a, b); the linear part from the combine's (alpha, k, delta)
@@ -393,6 +484,110 @@ int bn_backward(const char* what, int cbb, const float* x, const float* dy, cons
   return check_launch(what);
 }
 
+// ---- data parallel: the same passes split around the all-gathers of the per-image partials -------------------------------
+struct SyncPlan {
+  int S, rps;
+  size_t chunk;      // floats per rank chunk of the exchange buffer
+  size_t bytes;      // the whole buffer: N / Nl chunks
+};
+
+// plan of the GLOBAL batch (bn_plan(N_local, ...) may give another S); with_scale: CBB backward (the chunk ends in [Nl][C] scale rows)
+const char* sync_plan(int N, int n0, int Nl, int HW, int C, int with_scale, SyncPlan& p) {
+  if (N <= 0 || Nl <= 0 || HW <= 0 || C <= 0) return "bad shape";
+  if (C % 4) return "C % 4 != 0 (channels are read four at a time)";
+  if (Nl > N) return "N_local > N_global";
+  if (N % Nl) return "N_global is not a multiple of N_local (every rank holds the same number of images)";
+  if (n0 < 0 || n0 + Nl > N || n0 % Nl) return "rank offset outside the global batch (n0 = rank * N_local)";
+  if ((long long)HW * C >= (1LL << 31) || N > 65535) return "image too large (HW * C >= 2^31 or N > 65535)";
+  if ((long long)N * HW <= 1) return "Expected more than 1 value per channel when training";
+  bn_plan(N, HW, C, p.S, p.rps);
+  p.chunk = (size_t)Nl * ((size_t)p.S * C * 2 + (with_scale ? (size_t)C : 0));
+  p.bytes = (size_t)(N / Nl) * p.chunk * sizeof(float);
+  return nullptr;
+}
+
+// this rank's chunk, as the [Nl][S][C] partial rows the slab passes write
+float2* sync_chunk(void* xbuf, const SyncPlan& p, int n0, int Nl) {
+  return reinterpret_cast<float2*>(static_cast<float*>(xbuf) + (size_t)(n0 / Nl) * p.chunk);
+}
+
+int bn_sync_fwd_partial(const char* what, const float* x, void* xbuf, size_t xbuf_bytes, int N, int n0, int Nl, int HW, int C,
+                        void* stream) {
+  SyncPlan p;
+  const char* err = sync_plan(N, n0, Nl, HW, C, 0, p);
+  SRGAN_REQUIRE(!err, "%s: %s", what, err);
+  SRGAN_REQUIRE(x && xbuf, "%s: null pointer", what);
+  SRGAN_REQUIRE(xbuf_bytes >= p.bytes, "%s: exchange buffer too small (it holds the partials of the GLOBAL batch)", what);
+  hipLaunchKernelGGL(bn_stats_partial, dim3((unsigned)ceil_div(C, BN_CH), (unsigned)p.S, (unsigned)Nl), dim3(256), 0,
+                     as_stream(stream), x, sync_chunk(xbuf, p, n0, Nl), HW, C, p.S, p.rps);
+  return check_launch(what);
+}
+
+int bn_sync_fwd_apply(const char* what, int cbb, const float* x, const float* scale, const float* shift, const float* res,
+                      float* y, float* mean, float* rstd, float* m, float* a, float* b, float* rmean, float* rvar,
+                      long long* nbt, const void* xbuf, size_t xbuf_bytes, int N, int n0, int Nl, int HW, int C, float momentum,
+                      int cumulative, float eps, int act, float slope, void* stream) {
+  SyncPlan p;
+  const char* err = sync_plan(N, n0, Nl, HW, C, 0, p);
+  SRGAN_REQUIRE(!err, "%s: %s", what, err);
+  SRGAN_REQUIRE(x && y && mean && rstd && m && a && b && xbuf, "%s: null pointer", what);
+  SRGAN_REQUIRE((rmean == nullptr) == (rvar == nullptr), "%s: running_mean and running_var go together", what);
+  SRGAN_REQUIRE(!(rmean && cumulative && !nbt), "%s: momentum=None needs num_batches_tracked", what);
+  if (cbb) SRGAN_REQUIRE(scale && shift, "%s: null pointer (scale / shift)", what);
+  else SRGAN_REQUIRE((scale == nullptr) == (shift == nullptr), "%s: weight and bias go together", what);
+  SRGAN_REQUIRE(xbuf_bytes >= p.bytes, "%s: exchange buffer too small (it holds the partials of the GLOBAL batch)", what);
+  hipStream_t st = as_stream(stream);
+  const int update = rmean != nullptr;
+  hipLaunchKernelGGL(bn_sync_finalize, dim3((unsigned)ceil_div(C, 4)), dim3(256), 0, st, static_cast<const float2*>(xbuf), scale,
+                     shift, mean, rstd, m, a, b, rmean, rvar, nbt, N, HW, C, p.S, p.rps, cbb, update, momentum, cumulative, eps, n0,
+                     Nl, p.chunk);
+  long long* count = update ? nbt : nullptr;
+  if (res)
+    hipLaunchKernelGGL(bn_apply<true>, stream_grid(Nl, HW * C), dim3(256), 0, st, x, m, a, b, res, y, HW * C, C, act, slope, count);
+  else
+    hipLaunchKernelGGL(bn_apply<false>, stream_grid(Nl, HW * C), dim3(256), 0, st, x, m, a, b, res, y, HW * C, C, act, slope, count);
+  return check_launch(what);
+}
+
+int bn_sync_bwd_partial(const char* what, const float* x, const float* dy, const float* scale, const float* rstd, const float* m,
+                        const float* a, const float* b, void* xbuf, size_t xbuf_bytes, int N, int n0, int Nl, int HW, int C,
+                        int act, float slope, void* stream) {
+  SyncPlan p;
+  const char* err = sync_plan(N, n0, Nl, HW, C, scale != nullptr, p);
+  SRGAN_REQUIRE(!err, "%s: %s", what, err);
+  SRGAN_REQUIRE(x && dy && rstd && m && a && b && xbuf, "%s: null pointer", what);
+  SRGAN_REQUIRE(xbuf_bytes >= p.bytes, "%s: exchange buffer too small (it holds the partials of the GLOBAL batch)", what);
+  hipStream_t st = as_stream(stream);
+  float2* mine = sync_chunk(xbuf, p, n0, Nl);
+  hipLaunchKernelGGL(bn_bwd_partial, dim3((unsigned)ceil_div(C, BN_CH), (unsigned)p.S, (unsigned)Nl), dim3(256), 0, st, x, dy, m, a, b,
+                     rstd, mine, HW, C, p.S, p.rps, act, slope);
+  if (scale)
+    hipLaunchKernelGGL(bn_sync_pack_scale, dim3((unsigned)ceil_div((long long)Nl * C / 4, 256)), dim3(256), 0, st, scale,
+                       reinterpret_cast<float*>(mine) + (size_t)Nl * p.S * C * 2, Nl * C);
+  return check_launch(what);
+}
+
+int bn_sync_bwd_apply(const char* what, int cbb, const float* x, const float* dy, const float* weight, const float* mean,
+                      const float* rstd, const float* m, const float* a, const float* b, const void* xbuf, size_t xbuf_bytes,
+                      float* dx, float* dscale, float* dshift, int N, int n0, int Nl, int HW, int C, int act, float slope, void* ws,
+                      size_t ws_bytes, void* stream) {
+  SyncPlan p;
+  const char* err = sync_plan(N, n0, Nl, HW, C, cbb, p);
+  SRGAN_REQUIRE(!err, "%s: %s", what, err);
+  SRGAN_REQUIRE(x && dy && mean && rstd && m && a && b && dx && dscale && dshift && xbuf, "%s: null pointer", what);
+  SRGAN_REQUIRE(xbuf_bytes >= p.bytes, "%s: exchange buffer too small (it holds the partials of the GLOBAL batch)", what);
+  SRGAN_REQUIRE(ws && ws_bytes >= srgan_batchnorm_sync_workspace(Nl, C), "%s: workspace too small", what);
+  hipStream_t st = as_stream(stream);
+  float* alpha = static_cast<float*>(ws);
+  float* kcoef = alpha + (size_t)Nl * C;
+  float* delta = kcoef + (size_t)Nl * C;
+  hipLaunchKernelGGL(bn_sync_bwd_combine, dim3((unsigned)ceil_div(C, 4)), dim3(256), 0, st, static_cast<const float2*>(xbuf), weight,
+                     a, rstd, dscale, dshift, alpha, kcoef, delta, N, HW, C, p.S, cbb, n0, Nl, p.chunk);
+  hipLaunchKernelGGL(bn_bwd_dx, stream_grid(Nl, HW * C), dim3(256), 0, st, x, dy, m, a, b, mean, rstd, (const float*)alpha,
+                     (const float*)kcoef, (const float*)delta, dx, HW * C, C, act, slope);
+  return check_launch(what);
+}
+
 }  // namespace
 }  // namespace srgan
 
@@ -431,4 +626,65 @@ extern "C" int srgan_cbbnorm_bwd(const float* x, const float* dy, const float* s
                                  int HW, int C, int training, int act, float slope, void* ws, size_t ws_bytes, void* stream) {
   return bn_backward("cbbnorm_bwd", 1, x, dy, scale, nullptr, mean, rstd, m, a, b, dx, dscale, dshift, N, HW, C, training, act, slope, ws,
                      ws_bytes, stream);
+}
+
+// ---- data parallel: statistics of the global batch (include/srgan_hip.h) ---------------------------------------------------
+extern "C" size_t srgan_batchnorm_sync_exchange_bytes(int N_global, int N_local, int HW, int C, int with_scale) {
+  SyncPlan p;
+  return sync_plan(N_global, 0, N_local, HW, C, with_scale, p) ? 0 : p.bytes;
+}
+
+extern "C" size_t srgan_batchnorm_sync_workspace(int N_local, int C) {
+  if (N_local <= 0 || C <= 0) return 0;
+  return (2 * (size_t)N_local * C + (size_t)C) * sizeof(float);
+}
+
+extern "C" int srgan_batchnorm_sync_fwd_partial(const float* x, void* xbuf, size_t xbuf_bytes, int N_global, int n0, int N_local,
+                                                int HW, int C, void* stream) {
+  return bn_sync_fwd_partial("batchnorm_sync_fwd_partial", x, xbuf, xbuf_bytes, N_global, n0, N_local, HW, C, stream);
+}
+
+extern "C" int srgan_batchnorm_sync_fwd_apply(const float* x, const float* weight, const float* bias, float* y, float* mean,
+                                              float* rstd, float* m, float* a, float* b, float* running_mean, float* running_var,
+                                              long long* num_batches_tracked, const void* xbuf, size_t xbuf_bytes, int N_global,
+                                              int n0, int N_local, int HW, int C, float momentum, int cumulative, float eps, int act,
+                                              float slope, void* stream) {
+  return bn_sync_fwd_apply("batchnorm_sync_fwd_apply", 0, x, weight, bias, nullptr, y, mean, rstd, m, a, b, running_mean, running_var,
+                           num_batches_tracked, xbuf, xbuf_bytes, N_global, n0, N_local, HW, C, momentum, cumulative, eps, act, slope,
+                           stream);
+}
+
+extern "C" int srgan_cbbnorm_sync_fwd_apply(const float* x, const float* scale, const float* shift, const float* res, float* y,
+                                            float* mean, float* rstd, float* m, float* a, float* b, float* running_mean,
+                                            float* running_var, long long* num_batches_tracked, const void* xbuf, size_t xbuf_bytes,
+                                            int N_global, int n0, int N_local, int HW, int C, float momentum, int cumulative,
+                                            float eps, int act, float slope, void* stream) {
+  return bn_sync_fwd_apply("cbbnorm_sync_fwd_apply", 1, x, scale, shift, res, y, mean, rstd, m, a, b, running_mean, running_var,
+                           num_batches_tracked, xbuf, xbuf_bytes, N_global, n0, N_local, HW, C, momentum, cumulative, eps, act, slope,
+                           stream);
+}
+
+extern "C" int srgan_batchnorm_sync_bwd_partial(const float* x, const float* dy, const float* scale, const float* rstd,
+                                                const float* m, const float* a, const float* b, void* xbuf, size_t xbuf_bytes,
+                                                int N_global, int n0, int N_local, int HW, int C, int act, float slope,
+                                                void* stream) {
+  return bn_sync_bwd_partial("batchnorm_sync_bwd_partial", x, dy, scale, rstd, m, a, b, xbuf, xbuf_bytes, N_global, n0, N_local, HW,
+                             C, act, slope, stream);
+}
+
+extern "C" int srgan_batchnorm_sync_bwd_apply(const float* x, const float* dy, const float* weight, const float* mean,
+                                              const float* rstd, const float* m, const float* a, const float* b, const void* xbuf,
+                                              size_t xbuf_bytes, float* dx, float* dweight, float* dbias, int N_global, int n0,
+                                              int N_local, int HW, int C, int act, float slope, void* ws, size_t ws_bytes,
+                                              void* stream) {
+  return bn_sync_bwd_apply("batchnorm_sync_bwd_apply", 0, x, dy, weight, mean, rstd, m, a, b, xbuf, xbuf_bytes, dx, dweight, dbias,
+                           N_global, n0, N_local, HW, C, act, slope, ws, ws_bytes, stream);
+}
+
+extern "C" int srgan_cbbnorm_sync_bwd_apply(const float* x, const float* dy, const float* mean, const float* rstd, const float* m,
+                                            const float* a, const float* b, const void* xbuf, size_t xbuf_bytes, float* dx,
+                                            float* dscale, float* dshift, int N_global, int n0, int N_local, int HW, int C, int act,
+                                            float slope, void* ws, size_t ws_bytes, void* stream) {
+  return bn_sync_bwd_apply("cbbnorm_sync_bwd_apply", 1, x, dy, nullptr, mean, rstd, m, a, b, xbuf, xbuf_bytes, dx, dscale, dshift,
+                           N_global, n0, N_local, HW, C, act, slope, ws, ws_bytes, stream);
 }

@@ -102,6 +102,14 @@ SIGNATURES = {
     "srgan_cbbnorm_fwd": (c_int, [P] * 13 + [c_int, c_int, c_int, c_int, c_float, c_int, c_float, c_int, c_float, P, c_size_t, P]),
     "srgan_batchnorm_bwd": (c_int, [P] * 11 + [c_int, c_int, c_int, c_int, c_int, c_float, P, c_size_t, P]),
     "srgan_cbbnorm_bwd": (c_int, [P] * 11 + [c_int, c_int, c_int, c_int, c_int, c_float, P, c_size_t, P]),
+    "srgan_batchnorm_sync_exchange_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "srgan_batchnorm_sync_workspace": (c_size_t, [c_int, c_int]),
+    "srgan_batchnorm_sync_fwd_partial": (c_int, [P, P, c_size_t] + [c_int] * 5 + [P]),
+    "srgan_batchnorm_sync_fwd_apply": (c_int, [P] * 13 + [c_size_t] + [c_int] * 5 + [c_float, c_int, c_float, c_int, c_float, P]),
+    "srgan_cbbnorm_sync_fwd_apply": (c_int, [P] * 14 + [c_size_t] + [c_int] * 5 + [c_float, c_int, c_float, c_int, c_float, P]),
+    "srgan_batchnorm_sync_bwd_partial": (c_int, [P] * 8 + [c_size_t] + [c_int] * 5 + [c_int, c_float, P]),
+    "srgan_batchnorm_sync_bwd_apply": (c_int, [P] * 9 + [c_size_t, P, P, P] + [c_int] * 5 + [c_int, c_float, P, c_size_t, P]),
+    "srgan_cbbnorm_sync_bwd_apply": (c_int, [P] * 8 + [c_size_t, P, P, P] + [c_int] * 5 + [c_int, c_float, P, c_size_t, P]),
     "srgan_cbin_affine_fwd": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, P]),
     "srgan_cbin_affine_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, P, c_size_t, P]),
     "srgan_cbin_rec_bytes": (c_size_t, []),

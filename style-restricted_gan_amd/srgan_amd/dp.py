@@ -4,7 +4,9 @@ Replaces the reference's ``torch.nn.DataParallel(net, devices)`` (05-train noteb
 re-broadcasts every parameter on each of the 24 forwards of a step and gathers activations to GPU 0
 (SURVEY.md 2.3).  Here every rank owns its batch shard and a full replica; the only exchanges are
   * ``all_gather`` of mu [B_local, ndim] before the batch-statistics losses (batch-KL / correlation /
-    histogram are statistics of the GLOBAL batch), and
+    histogram are statistics of the GLOBAL batch),
+  * for ``norm_type="batch"`` networks marked with ``sync_batch_stats``: one ``all_gather`` of per-image slab partials per norm
+    call and direction, so that the norms use the statistics of the GLOBAL batch (``all_gather_chunks``), and
   * one bucketed ``all_reduce`` of gradients per optimiser step, launched on a side HIP stream so it can
     overlap independent compute (the next G forward during the D updates).
 Backend: ``nccl`` (= RCCL on ROCm) for GPU tensors, ``gloo`` for the CPU tests.
@@ -238,6 +240,39 @@ class _AllGatherRows(torch.autograd.Function):
 
 def all_gather_rows(x):
     return _AllGatherRows.apply(x) if is_distributed() else x
+
+
+# ---- batch-statistics norms under data parallelism -------------------------------------------------------------------
+_SYNC_MARK = "sync_stats"     # a plain attribute of the norm module: not a parameter or buffer, so never in state_dict()
+
+exchange_trace = None         # tests / diagnosis: a list -> (site, number of floats) of every all_gather_chunks call
+
+
+def sync_batch_stats(net, enable=True):
+    """Mark every batch-statistics norm of ``net`` (a module or a ``DataParallel`` wrapper), in place; returns ``net``.  A marked
+    norm in training mode under a process group normalises with the statistics of ALL ranks' images, so that N ranks with B/N
+    images each compute what one process computes with B images (``ops.batch_norm_act(sync=True)``: bit-identical statistics).
+    In eval mode, without a process group or unmarked it is the one-process norm and issues no collective."""
+    from .model import BatchNorm2d, CBBNorm2d
+    for m in unwrap(net).modules():
+        if isinstance(m, (BatchNorm2d, CBBNorm2d)):      # (another batch norm class has no synced path and stays unmarked)
+            setattr(m, _SYNC_MARK, bool(enable))
+    return net
+
+
+def all_gather_chunks(buf, site):
+    """In-place all-gather of a flat fp32 buffer of world_size equal chunks: chunk r comes from rank r (this rank has filled its
+    own).  The one exchange of the synced batch norms, forward and backward; it goes through ``_all_gather_into``, so all three
+    transports serve it.  While a step is recorded it is a cut of the recording, exactly like ``_AllGatherRows.forward``."""
+    ws = dist.get_world_size()
+    src = buf.view(ws, -1)[dist.get_rank()]
+    if exchange_trace is not None:
+        exchange_trace.append((site, buf.numel()))
+    if _recorder is not None:
+        launch_pending()
+        _recorder.cut(_Comm("all_gather", lambda: _all_gather_into(buf, src)))
+        return
+    _all_gather_into(buf, src)
 
 
 BUCKET_BYTES = 16 << 20   # per all-reduce message (fp32 bytes of its gradients): several buckets per network, so the first ones run under the backward

@@ -299,7 +299,7 @@ class BatchNorm2d(nn.BatchNorm2d):
         batch_stats = self.training or (self.running_mean is None and self.running_var is None)
         return ops.batch_norm_act(x, self.weight, self.bias, self.running_mean if use_buffers else None,
                                   self.running_var if use_buffers else None, self.num_batches_tracked if track else None,
-                                  batch_stats, self.momentum, self.eps, act, slope)
+                                  batch_stats, self.momentum, self.eps, act, slope, sync=self.training and _is_synced(self))
 
 
 class CBBNorm2d(nn.Module):
@@ -370,7 +370,7 @@ class CBBNorm2d(nn.Module):
         track = self.training and self.track_running_stats
         return ops.cbb_norm_act(input, scale, shift, self.running_mean, self.running_var,
                                 self.num_batches_tracked if track else None, self.training or not self.track_running_stats,
-                                self.momentum, self.eps, act, slope, res)
+                                self.momentum, self.eps, act, slope, res, sync=self.training and _is_synced(self))
 
     scale_shift = CBINorm2d.scale_shift
     affine_params = CBINorm2d.affine_params
@@ -378,6 +378,17 @@ class CBBNorm2d(nn.Module):
 
 def _is_batch_stat(m):
     return isinstance(m, (nn.modules.batchnorm._BatchNorm, CBBNorm2d))
+
+
+def _is_synced(m):
+    """The mark of dp.sync_batch_stats: in training mode under a process group this norm uses every rank's images."""
+    return bool(getattr(m, "sync_stats", False))
+
+
+def batch_stats_synced(net):
+    """True when ``net`` (a module or a dp.DataParallel wrapper) has no batch-statistics norm, or all of them carry the mark of
+    dp.sync_batch_stats: a data-parallel training run of it equals the one-process run."""
+    return all(_is_synced(m) for m in net.modules() if _is_batch_stat(m))
 
 
 def per_sample(net):

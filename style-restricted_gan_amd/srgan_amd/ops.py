@@ -892,9 +892,12 @@ class _BatchNormFn(Function):
 
 
 def batch_norm_act(x, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum=0.1, eps=1e-5,
-                   act=ACT_NONE, slope=0.0):
+                   act=ACT_NONE, slope=0.0, sync=False):
     """nn.BatchNorm2d + activation: act((x - mu_c) / sqrt(var_c + eps) * weight + bias).  training: batch statistics, and the
-    running buffers (if given) are updated on the device; otherwise the running buffers are used."""
+    running buffers (if given) are updated on the device; otherwise the running buffers are used.  sync: in training mode under a
+    process group, the statistics of every rank's images (two all-gathers per call, forward and backward)."""
+    if _synced(sync, training):
+        return _SyncBatchNormFn.apply(x, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps, act, slope)
     return _BatchNormFn.apply(x, weight, bias, running_mean, running_var, num_batches_tracked, bool(training), momentum, eps,
                               act, slope)
 
@@ -946,11 +949,142 @@ class _CbbNormFn(Function):
 
 
 def cbb_norm_act(x, scale, shift, running_mean, running_var, num_batches_tracked, training, momentum=0.1, eps=1e-5,
-                 act=ACT_NONE, slope=0.0, res=None):
+                 act=ACT_NONE, slope=0.0, res=None, sync=False):
     """CBBNorm2d + activation (+ residual): act((x - mu_nc) / sqrt(var_c + eps) * scale[n,c] + shift[n,c]) (+ res), the reference's
-    (F.batch_norm(x) - avgpool(F.batch_norm(x)) + tanh(Linear(c))) * weight + bias."""
+    (F.batch_norm(x) - avgpool(F.batch_norm(x)) + tanh(Linear(c))) * weight + bias.  sync: as batch_norm_act."""
+    if _synced(sync, training):
+        return _SyncCbbNormFn.apply(x, scale, shift, running_mean, running_var, num_batches_tracked, momentum, eps, act, slope, res)
     return _CbbNormFn.apply(x, scale, shift, running_mean, running_var, num_batches_tracked, bool(training), momentum, eps, act,
                             slope, res)
+
+
+# ---- data parallel: statistics of the global batch (dp.sync_batch_stats; DESIGN.md section 6) -----------------------------------
+def _sync_geometry(x, what):
+    """(N_global, n0) of this rank's x: rank r holds images [r * N_local, (r + 1) * N_local) of the global batch, every rank the
+    same number (the layout of everything in srgan_amd.dp)."""
+    from . import dp
+    n, c, h, w = x.shape
+    ng = n * dp.world_size()
+    if c % 4:
+        raise _lib.SrganHipError(f"{what}: C = {c} is not a multiple of 4 (the batch-norm kernels read channels four at a time)")
+    if ng * h * w <= 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size {}".format([ng, c, h, w]))
+    return ng, n * dp.rank()
+
+
+def _sync_exchange_buffer(lib, x, ng, with_scale):
+    """A fresh buffer per call (caching allocator: stream-ordered, so nothing is shared with the side stream the second
+    discriminator scale runs on), and the size the kernels check it against."""
+    n, c, h, w = x.shape
+    nb = lib.srgan_batchnorm_sync_exchange_bytes(ng, n, h * w, c, int(with_scale))
+    if not nb:
+        raise _lib.SrganHipError("batchnorm_sync: " + lib.srgan_last_error().decode(errors="replace"))
+    return torch.empty(nb // 4, dtype=torch.float32, device=x.device), nb
+
+
+def _sync_forward(ctx, cbb, x, p0, p1, res, running_mean, running_var, num_batches_tracked, momentum, eps, act, slope):
+    """Phase 1 (this rank's slab partials into its chunk), the all-gather, phase 2 (merge over the global batch + apply)."""
+    from . import dp
+    what = "cbb_norm" if cbb else "batch_norm"
+    _require_gpu(x, what)
+    x = to_nhwc(x)
+    n, c, h, w = x.shape
+    ng, n0 = _sync_geometry(x, what)
+    rm, rv, nbt, cumulative, mom = _bn_buffers(running_mean, running_var, num_batches_tracked, True, momentum)
+    lib = _lib.load()
+    y = torch.empty_like(x)
+    mean, rstd, m, a, b = _bn_stats(n, c, x.device)
+    buf, nb = _sync_exchange_buffer(lib, x, ng, False)
+    _lib.check(lib.srgan_batchnorm_sync_fwd_partial(_ptr(x), _ptr(buf), nb, ng, n0, n, h * w, c, _stream()), "batchnorm_sync_fwd_partial")
+    dp.all_gather_chunks(buf, what + ".forward")
+    tail = (_ptr(rm), _ptr(rv), _ptr(nbt), _ptr(buf), nb, ng, n0, n, h * w, c, mom, cumulative, float(eps), act, float(slope), _stream())
+    if cbb:
+        _lib.check(lib.srgan_cbbnorm_sync_fwd_apply(_ptr(x), _ptr(p0), _ptr(p1), _ptr(res), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(m),
+                                                    _ptr(a), _ptr(b), *tail), "cbbnorm_sync_fwd_apply")
+    else:
+        _lib.check(lib.srgan_batchnorm_sync_fwd_apply(_ptr(x), _ptr(p0), _ptr(p1), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(m), _ptr(a),
+                                                      _ptr(b), *tail), "batchnorm_sync_fwd_apply")
+    ctx.act, ctx.slope, ctx.geometry = act, slope, (ng, n0)
+    return x, y, mean, rstd, m, a, b
+
+
+def _sync_backward(ctx, cbb, x, gy, scale, weight, mean, rstd, m, a, b):
+    """Phase 1 (this rank's {sum g, sum g * xh} partials, CBB: and its scale rows), the all-gather, phase 2 (combine + dx).
+    Returns dx and the parameter gradients of the LOCAL images."""
+    from . import dp
+    what = "cbb_norm" if cbb else "batch_norm"
+    gy = to_nhwc(gy)
+    n, c, h, w = x.shape
+    ng, n0 = ctx.geometry
+    lib = _lib.load()
+    dx = torch.empty_like(x)
+    d0 = torch.empty((n, c) if cbb else (c,), dtype=torch.float32, device=x.device)      # dscale / dweight
+    d1 = torch.empty_like(d0)                                                           # dshift / dbias
+    buf, nb = _sync_exchange_buffer(lib, x, ng, cbb)
+    _lib.check(lib.srgan_batchnorm_sync_bwd_partial(_ptr(x), _ptr(gy), _ptr(scale), _ptr(rstd), _ptr(m), _ptr(a), _ptr(b), _ptr(buf),
+                                                    nb, ng, n0, n, h * w, c, ctx.act, float(ctx.slope), _stream()),
+               "batchnorm_sync_bwd_partial")
+    dp.all_gather_chunks(buf, what + ".backward")
+    wb = lib.srgan_batchnorm_sync_workspace(n, c)
+    ws = workspace(x.device, wb)
+    tail = (_ptr(mean), _ptr(rstd), _ptr(m), _ptr(a), _ptr(b), _ptr(buf), nb, _ptr(dx), _ptr(d0), _ptr(d1), ng, n0, n, h * w, c, ctx.act,
+            float(ctx.slope), _ptr(ws), wb, _stream())
+    if cbb:
+        _lib.check(lib.srgan_cbbnorm_sync_bwd_apply(_ptr(x), _ptr(gy), *tail), "cbbnorm_sync_bwd_apply")
+    else:
+        _lib.check(lib.srgan_batchnorm_sync_bwd_apply(_ptr(x), _ptr(gy), _ptr(weight), *tail), "batchnorm_sync_bwd_apply")
+    return gy, dx, d0, d1
+
+
+class _SyncBatchNormFn(Function):
+    """_BatchNormFn in training mode with the statistics of every rank's images (same kept semantics: the weight by reference)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps, act, slope):
+        x, y, mean, rstd, m, a, b = _sync_forward(ctx, False, x, weight, bias, None, running_mean, running_var, num_batches_tracked,
+                                                  momentum, eps, act, slope)
+        ctx.has_affine = weight is not None
+        ctx.weight = weight                    # by reference: read at backward time
+        ctx.save_for_backward(x, mean, rstd, m, a, b)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, mean, rstd, m, a, b = ctx.saved_tensors
+        gy, dx, dweight, dbias = _sync_backward(ctx, False, x, gy, None, ctx.weight, mean, rstd, m, a, b)
+        if not ctx.has_affine:
+            dweight = dbias = None
+        return dx, dweight, dbias, None, None, None, None, None, None, None
+
+
+class _SyncCbbNormFn(Function):
+    """_CbbNormFn in training mode with r_c from every rank's images."""
+
+    @staticmethod
+    def forward(ctx, x, scale, shift, running_mean, running_var, num_batches_tracked, momentum, eps, act, slope, res):
+        if res is not None:
+            res = to_nhwc(res)
+        scale, shift = _dense2d(scale), _dense2d(shift)
+        x, y, mean, rstd, m, a, b = _sync_forward(ctx, True, x, scale, shift, res, running_mean, running_var, num_batches_tracked,
+                                                  momentum, eps, act, slope)
+        ctx.has_res = res is not None
+        ctx.save_for_backward(x, scale, mean, rstd, m, a, b)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, scale, mean, rstd, m, a, b = ctx.saved_tensors
+        gy, dx, dscale, dshift = _sync_backward(ctx, True, x, gy, scale, None, mean, rstd, m, a, b)
+        return (dx, dscale, dshift, None, None, None, None, None, None, None,
+                (gy.clone() if _DEBUG_CLONE else gy) if ctx.has_res else None)
+
+
+def _synced(sync, training):
+    """The synced path is taken in training mode under a process group (dp.is_distributed()); otherwise no collective is issued."""
+    if not (sync and training):
+        return False
+    from . import dp
+    return dp.is_distributed()
 
 
 class _NormActConvFn(Function):

@@ -28,7 +28,7 @@ import torch.optim as optim
 
 from . import _lib, dp, ops
 from .losses import class_encode, get_domainloss_D, get_loss_D, histogram_imitation
-from .model import SingleGenerator, _cpu_normal_like, _is_batch_stat, host_to_device, per_sample
+from .model import SingleGenerator, _cpu_normal_like, _is_batch_stat, _is_synced, batch_stats_synced, host_to_device, per_sample
 from .optim import Adam
 
 __all__ = ["SRGAN_training", "SingleGAN_training"]
@@ -91,11 +91,12 @@ class SRGAN_training():
         # different computation (and a different number of running-buffer updates); those sites run call by call
         self._g_per_sample = per_sample(dp.unwrap(self.G))
         self._e_per_sample = per_sample(dp.unwrap(self.E))
-        if dp.world_size() > 1 and not (self._g_per_sample and self._e_per_sample):
+        if dp.world_size() > 1 and not (batch_stats_synced(dp.unwrap(self.G)) and batch_stats_synced(dp.unwrap(self.E))):
             raise NotImplementedError(
                 "SRGAN_training: G / E hold batch-statistics norms (norm_type='batch') and a process group has "
                 f"{dp.world_size()} ranks; nn.DataParallel gives per-replica statistics and rank-0 running buffers, which this "
-                "package does not build (one process, or norm_type='instance')")
+                "package does not build (one process, or norm_type='instance'). Statistics of the global batch are an opt-in: "
+                "mark both networks with dp.sync_batch_stats(net).")
 
     # ------------------------------------------------------------------------------------------
     def opt_sche_initialization(self, lr=[0.0001, 0.0001, 0.0001]):
@@ -572,7 +573,9 @@ class SRGAN_training():
         segments; between them the all-reduces are enqueued on the communication stream and run UNDER the following segment --
         the next translation, phase 1's forward passes, E's optimiser step: ``_Recording``, ``dp.launch_pending``); if any rank
         fails to record, all ranks drop graph mode together and continue eagerly
-        (``SRGAN_DP_GRAPH=0`` refuses graph mode under a process group altogether)."""
+        (``SRGAN_DP_GRAPH=0`` refuses graph mode under a process group altogether).  Networks marked with
+        ``dp.sync_batch_stats`` exchange partials inside their backward, where a recording cannot be cut: their step is recorded
+        only in the single-graph form of the C-ABI transport and runs eagerly otherwise (``_StepGraph.SEGMENTED_SYNC``)."""
         self._graph = _StepGraph(self)
         return self
 
@@ -593,7 +596,7 @@ class _StepGraph:
     def __init__(self, sg):
         self.sg = sg
         reason = self.unsupported_reason()
-        if reason:
+        if reason and reason is not self.SEGMENTED_SYNC:      # (that one is not a refusal: such steps run eagerly, _local_mode)
             raise NotImplementedError("SRGAN_training.enable_graph: " + reason)
         self.key = None          # input signature the eager warm-up ran with
         self.graph = None
@@ -613,6 +616,12 @@ class _StepGraph:
 
     fault_hook = None            # tests: callable(stage) with stage in {"before", "inside"}; raising makes the recording fail
 
+    # A synced norm's backward exchanges partials from autograd's thread; cutting the recording there would end, in that thread, a
+    # capture begun in this one, which the HIP runtime refuses (hipErrorStreamCaptureWrongThread).  Such a step runs eagerly on
+    # every rank, or as ONE graph with the captured C-ABI collectives (SRGAN_DP_COMM=abi: no cut).
+    SEGMENTED_SYNC = ("synced batch norms in the segmented form: their backward exchange cannot cut a recording from autograd's "
+                      "thread; the step runs eagerly (or as one graph with SRGAN_DP_COMM=abi)")
+
     def unsupported_reason(self):
         sg = self.sg
         if not sg._fused_paths():
@@ -622,7 +631,18 @@ class _StepGraph:
                 return f"{name} is not srgan_amd.optim.Adam (call opt_sche_initialization(), or pass that class)"
         if dp.is_distributed() and os.environ.get("SRGAN_DP_GRAPH") == "0":
             return "SRGAN_DP_GRAPH=0: data-parallel steps run eagerly (hook-driven all-reduce under the backward)"
+        if dp.is_distributed() and self._synced_norms() and not self._single_graph():
+            return self.SEGMENTED_SYNC
         return None
+
+    def _synced_norms(self):
+        sg = self.sg
+        return any(_is_synced(m) and m.training for net in (sg.G, sg.E) for m in net.modules() if _is_batch_stat(m))
+
+    def _single_graph(self):
+        """Would a recording made now capture its collectives (one graph, no cut)?  The condition of _Recording.single."""
+        return (not getattr(self, "_force_segmented", False) and dp.transport() == "abi"
+                and os.environ.get("SRGAN_DP_SINGLE_GRAPH") != "0")
 
     @staticmethod
     def _key(source_image, label):
@@ -649,7 +669,8 @@ class _StepGraph:
         fp.append(tuple((id(p), p.data_ptr(), p.requires_grad) for p in self._all_params()))
         # batch norms: train / eval mode, momentum and eps are baked into the recorded launches (the running buffers themselves are
         # device state the step updates in place)
-        fp.append(tuple((id(m), m.training, m.momentum, m.eps, m.track_running_stats) for net in (sg.G, sg.E)
+        # so is the mark of dp.sync_batch_stats (another autograd function, with exchanges)
+        fp.append(tuple((id(m), m.training, m.momentum, m.eps, m.track_running_stats, _is_synced(m)) for net in (sg.G, sg.E)
                         for m in net.modules() if _is_batch_stat(m)))
         return tuple(fp)
 
@@ -664,6 +685,11 @@ class _StepGraph:
 
     def _local_mode(self, source_image, label):
         """2: replay the recording, 1: record (the eager warm-up of this input shape has run), 0: eager."""
+        if dp.is_distributed() and self.unsupported_reason() is self.SEGMENTED_SYNC:
+            # the same answer on every rank (the marks, the transport and a failed single-graph recording are agreed state)
+            if self.graph is not None:
+                self._drop()
+            return 0
         if self.graph is not None:
             stale = self._epoch != ops.structure_epoch()
             # a buffer the recording points at was replaced (compute-mode switch, invalidate_packed, optimiser re-seeded), or
