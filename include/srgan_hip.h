@@ -454,6 +454,21 @@ int srgan_adam_state_init(void* state, float lr, float beta1, float beta2, float
 int srgan_adam_state_set_lr(void* state, float lr, void* stream);
 int srgan_adam_multi_dev(const void* table, int n_tensors, long long max_numel, void* state, void* stream);
 
+/* Exponential moving average of the sampling weights (G, and E whose mu feeds G), kept inside the train step.  Extension, no
+ * counterpart in the reference.  A 16-byte DEVICE record {int n; int ramp; float decay; float c} holds the number of updates
+ * done, so that replaying a captured step advances it.  srgan_ema_multi_dev = two launches: a tick (n += 1;
+ * d_n = ramp ? min(decay, (1 + n) / (10 + n)) : decay in double, rounded to float once; c = 1 - d_n in float), then one kernel
+ * over `table` (device memory): n_records records of five 64-bit words {dst, src, numel, kind, chunk0}.  kind 0:
+ * dst <- dst + c * (src - dst) on fp32 (dst stays bit-identical where src == dst); kind 1: dst <- src bit for bit, numel in
+ * 32-bit words (batch-norm running buffers are carried over, not averaged).  chunk0 is the index of the record's first chunk in
+ * the flat list of srgan_ema_chunk()-element chunks of all records (a prefix sum of ceil(numel / chunk)); total_chunks is that
+ * list's length.  decay must lie in [0, 1); n_done seeds n (0 for a fresh average, the checkpoint's count when resuming). */
+size_t srgan_ema_state_bytes(void);
+size_t srgan_ema_chunk(void);
+int srgan_ema_state_init(void* state, float decay, int ramp, int n_done, void* stream);
+int srgan_ema_state_set_decay(void* state, float decay, void* stream);
+int srgan_ema_multi_dev(const void* table, int n_records, long long total_chunks, void* state, void* stream);
+
 /* Small host -> device upload (pointer tables: <= 1 MiB, multiple of 4 bytes) carried in kernel arguments: nothing to keep
  * alive on the host after the call returns, and a captured hipGraph stores the bytes in its node instead of re-reading a host
  * address at replay (no reference counterpart; plumbing of the multi-tensor ops above). */

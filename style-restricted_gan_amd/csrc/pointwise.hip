@@ -388,6 +388,89 @@ __global__ __launch_bounds__(256) void adam_multi_dev_kernel(const unsigned long
   }
 }
 
+// ---- exponential moving average of the sampling weights (extension, no counterpart in the reference) ------------------
+// {n, ramp, decay, c}: n = updates done, c = 1 - d_n of the update in flight.  Like AdamState the count lives on the device so
+// that a captured train step advances it on every replay; the host mirrors n for checkpoints only.
+struct EmaState { int n; int ramp; float decay; float c; };
+static_assert(sizeof(EmaState) == 16, "EmaState layout");
+__global__ void ema_state_init_kernel(EmaState* s, int n, int ramp, float decay) {
+  s->n = n; s->ramp = ramp; s->decay = decay; s->c = 0.f;
+}
+__global__ void ema_state_decay_kernel(EmaState* s, float decay) { s->decay = decay; }
+// d_n = ramp ? min(decay, (1 + n) / (10 + n)) : decay in double, rounded to float once; c = 1 - d_n in float
+__global__ void ema_tick_kernel(EmaState* s) {
+  const int n = s->n + 1;
+  s->n = n;
+  double d = (double)s->decay;
+  if (s->ramp) {
+    const double r = (1.0 + (double)n) / (10.0 + (double)n);
+    d = r < d ? r : d;
+  }
+  s->c = 1.f - (float)d;
+}
+
+// One launch for every tensor of every averaged network.  `table`: n_records records of five 64-bit words
+// {dst, src, numel, kind, chunk0}.  The work is the FLAT list of 4096-element chunks of all records (chunk0 = index of a record's
+// first chunk, a prefix sum the host wrote); blocks grid-stride over that list, so a network of many small tensors costs one chunk
+// each instead of a grid row of idle blocks.  kind 0: e <- e + c * (p - e) on fp32 (returns e exactly where p == e); kind 1:
+// dst <- src bit for bit, numel counting 32-bit words.  Every element is written by exactly one thread from its own old value:
+// no atomics, and the result does not depend on the grid.
+constexpr int kEmaChunk = 4096;
+constexpr int kEmaRecWords = 5;
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void ema_multi_dev_kernel(const unsigned long long* __restrict__ table, int n_records,
+                                                            long long total_chunks, const EmaState* __restrict__ st) {
+  const float c = st->c;
+  for (long long ch = blockIdx.x; ch < total_chunks; ch += gridDim.x) {
+    int lo = 0, hi = n_records - 1;          // the last record whose first chunk is <= ch (block-uniform: scalar loads)
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if ((long long)table[(size_t)mid * kEmaRecWords + 4] <= ch) lo = mid; else hi = mid - 1;
+    }
+    const unsigned long long* rec = table + (size_t)lo * kEmaRecWords;
+    const long long n = (long long)rec[2];
+    const long long c0 = (ch - (long long)rec[4]) * kEmaChunk;
+    if (c0 < 0 || c0 >= n) continue;         // (a table whose prefix sums disagree with its sizes touches nothing)
+    const bool vec = ((rec[0] | rec[1]) & 15) == 0 && c0 + kEmaChunk <= n;
+    const long long end = c0 + kEmaChunk < n ? c0 + kEmaChunk : n;
+    if (rec[3] == 0) {
+      float* e = reinterpret_cast<float*>(rec[0]);
+      const float* p = reinterpret_cast<const float*>(rec[1]);
+      if (vec) {
+        f32x4 pv[4], ev[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const long long i = c0 + (j * 256 + threadIdx.x) * 4;
+          pv[j] = *reinterpret_cast<const f32x4*>(p + i);
+          ev[j] = *reinterpret_cast<const f32x4*>(e + i);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const long long i = c0 + (j * 256 + threadIdx.x) * 4;
+          *reinterpret_cast<f32x4*>(e + i) = ev[j] + c * (pv[j] - ev[j]);
+        }
+      } else {
+        for (long long i = c0 + threadIdx.x; i < end; i += 256) {
+          const float ei = e[i];
+          e[i] = ei + c * (p[i] - ei);
+        }
+      }
+    } else {
+      unsigned int* d = reinterpret_cast<unsigned int*>(rec[0]);
+      const unsigned int* s = reinterpret_cast<const unsigned int*>(rec[1]);
+      if (vec) {
+        u32x4 sv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sv[j] = *reinterpret_cast<const u32x4*>(s + c0 + (j * 256 + threadIdx.x) * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<u32x4*>(d + c0 + (j * 256 + threadIdx.x) * 4) = sv[j];
+      } else {
+        for (long long i = c0 + threadIdx.x; i < end; i += 256) d[i] = s[i];
+      }
+    }
+  }
+}
+
 }  // namespace srgan
 
 using namespace srgan;
@@ -602,4 +685,33 @@ extern "C" int srgan_adam_multi_dev(const void* table, int n_tensors, long long 
   hipLaunchKernelGGL(srgan::adam_multi_dev_kernel, dim3(bx, (unsigned)n_tensors), dim3(256), 0, as_stream(stream),
                      reinterpret_cast<const unsigned long long*>(table), static_cast<const srgan::AdamState*>(state));
   return check_launch("adam_multi_dev_kernel");
+}
+
+extern "C" size_t srgan_ema_state_bytes(void) { return sizeof(srgan::EmaState); }
+
+extern "C" size_t srgan_ema_chunk(void) { return (size_t)srgan::kEmaChunk; }
+
+extern "C" int srgan_ema_state_init(void* state, float decay, int ramp, int n_done, void* stream) {
+  SRGAN_REQUIRE(state && decay >= 0.f && decay < 1.f && n_done >= 0, "ema_state_init: bad argument (decay in [0, 1), n_done >= 0)");
+  hipLaunchKernelGGL(srgan::ema_state_init_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::EmaState*>(state),
+                     n_done, ramp ? 1 : 0, decay);
+  return check_launch("ema_state_init_kernel");
+}
+
+extern "C" int srgan_ema_state_set_decay(void* state, float decay, void* stream) {
+  SRGAN_REQUIRE(state && decay >= 0.f && decay < 1.f, "ema_state_set_decay: bad argument (decay in [0, 1))");
+  hipLaunchKernelGGL(srgan::ema_state_decay_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::EmaState*>(state),
+                     decay);
+  return check_launch("ema_state_decay_kernel");
+}
+
+extern "C" int srgan_ema_multi_dev(const void* table, int n_records, long long total_chunks, void* state, void* stream) {
+  SRGAN_REQUIRE(table && state && n_records > 0 && total_chunks > 0, "ema_multi_dev: bad argument");
+  hipLaunchKernelGGL(srgan::ema_tick_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::EmaState*>(state));
+  // memory bound: one block per chunk up to 256 CUs x 8 blocks, the rest by grid stride
+  const unsigned bx = (unsigned)std::min<long long>(total_chunks, 2048);
+  hipLaunchKernelGGL(srgan::ema_multi_dev_kernel, dim3(bx), dim3(256), 0, as_stream(stream),
+                     reinterpret_cast<const unsigned long long*>(table), n_records, total_chunks,
+                     static_cast<const srgan::EmaState*>(state));
+  return check_launch("ema_multi_dev_kernel");
 }

@@ -170,6 +170,11 @@ SIGNATURES = {
     "srgan_adam_state_init": (c_int, [P, c_float, c_float, c_float, c_float, c_int, P]),
     "srgan_adam_state_set_lr": (c_int, [P, c_float, P]),
     "srgan_adam_multi_dev": (c_int, [P, c_int, c_longlong, P, P]),
+    "srgan_ema_state_bytes": (c_size_t, []),
+    "srgan_ema_chunk": (c_size_t, []),
+    "srgan_ema_state_init": (c_int, [P, c_float, c_int, c_int, P]),
+    "srgan_ema_state_set_decay": (c_int, [P, c_float, P]),
+    "srgan_ema_multi_dev": (c_int, [P, c_int, c_longlong, P, P]),
     "srgan_upload_small": (c_int, [P, P, c_size_t, P]),
     "srgan_maxpool2_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "srgan_pairwise_dist": (c_int, [P, c_int, P, c_int, c_int, P, P]),

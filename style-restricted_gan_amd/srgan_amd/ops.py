@@ -2403,3 +2403,33 @@ def adam_multi_step_(table_dev, n_tensors, max_numel, lr, beta1, beta2, eps, ste
     """One launch of torch-1.4 Adam over a list of tensors described by a device pointer table (see optim.Adam)."""
     _lib.check(_lib.load().srgan_adam_multi(_ptr(table_dev), int(n_tensors), int(max_numel), float(lr), float(beta1),
                                             float(beta2), float(eps), int(step), _stream()), "adam_multi")
+
+
+# ---- exponential moving average of the sampling weights (srgan_amd.ema; extension, no counterpart in the reference) --------
+def ema_state_new(device, decay, ramp, n_done):
+    """Device-resident record {n, ramp, decay, c} seeded with ``n_done`` completed updates."""
+    lib = _lib.load()
+    st = torch.empty(lib.srgan_ema_state_bytes(), dtype=torch.uint8, device=device)
+    ema_state_init(st, decay, ramp, n_done)
+    return st
+
+
+def ema_state_init(state, decay, ramp, n_done):
+    """(Re-)seed an existing record in place: a captured step that points at it keeps pointing at it."""
+    _lib.check(_lib.load().srgan_ema_state_init(_ptr(state), float(decay), int(bool(ramp)), int(n_done), _stream()), "ema_state_init")
+
+
+def ema_state_set_decay(state, decay):
+    _lib.check(_lib.load().srgan_ema_state_set_decay(_ptr(state), float(decay), _stream()), "ema_state_set_decay")
+
+
+def ema_chunk():
+    """Elements per work item of ``ema_multi_dev_`` (the unit of a table's chunk0 prefix sums)."""
+    return int(_lib.load().srgan_ema_chunk())
+
+
+def ema_multi_dev_(table_dev, n_records, total_chunks, state):
+    """n += 1 and c = 1 - d_n on the device, then ONE launch over the records {dst, src, numel, kind, chunk0} of the table:
+    dst += c * (src - dst) (kind 0) or dst <- src bit for bit (kind 1).  hipGraph-capturable; writes through raw pointers."""
+    _lib.check(_lib.load().srgan_ema_multi_dev(_ptr(table_dev), int(n_records), int(total_chunks), _ptr(state), _stream()),
+               "ema_multi_dev")

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.optim as optim
 
-from . import _lib, dp, ops
+from . import _lib, dp, ema, ops
 from .losses import class_encode, get_domainloss_D, get_loss_D, histogram_imitation
 from .model import SingleGenerator, _cpu_normal_like, _is_batch_stat, _is_synced, batch_stats_synced, host_to_device, per_sample
 from .optim import Adam
@@ -85,6 +85,9 @@ class SRGAN_training():
         self.noise_fn = torch.randn    # style noise source (CPU default generator, as the reference); tests may inject
         self._graph = None             # hipGraph mode (enable_graph)
         self._g_active = False         # True while the step body reads its inputs from the static device buffers
+        self._ema = None               # averaged copies of G / E (enable_ema)
+        self.G_ema = self.E_ema = None
+        self._ema_scope = False        # inside ema_weights(): self.G / self.E are the copies
         ref = np.asarray(ref_label)
         self._ref_is_onehot = ref.ndim == 2 and ref.shape[0] == ref.shape[1] and np.array_equal(ref, np.eye(ref.shape[0]))
         # norm_type="batch": G / E normalise with batch statistics, so batching several of the reference's calls into one is a
@@ -517,6 +520,7 @@ class SRGAN_training():
                 if i == 0:
                     errorD = errD.detach()
             errorG, errorE = self.update_GandE()
+            self._ema_update()
             return [errorG, errorD, errorE]
         fakes = []
         if k > 1 and isinstance(dp.unwrap(self.G), SingleGenerator) and self._g_per_sample:   # per-sample network: batching is exact
@@ -542,9 +546,18 @@ class SRGAN_training():
             if i == 0:
                 errorD = errD.detach()
         errorG, errorE = self.update_GandE()
+        self._ema_update()
         return [errorG, errorD, errorE]
 
+    def _ema_update(self):
+        """One EMA update per ``train()`` (one iteration of the reference's loop), after phase 2's ``optG.step()``: on the
+        step's stream, inside its ``ops.pack_cache()`` scope and inside its recording.  Two launches, none with the EMA off."""
+        if self._ema is not None:
+            self._ema.update()
+
     def train(self, source_image, label):
+        if self._ema_scope:
+            raise RuntimeError("SRGAN_training.train() inside ema_weights(): self.G / self.E are the averaged copies there")
         self.label = label
         self.loss_terms = {}
         g = self._graph
@@ -588,6 +601,73 @@ class SRGAN_training():
     @property
     def graph_active(self):
         return self._graph is not None and self._graph.graph is not None
+
+    # ------------------------------------------------------------------------------------------
+    # exponential moving average of the sampling weights (extension, no counterpart in the reference; srgan_amd.ema)
+    def enable_ema(self, decay=0.999, nets=("G", "E"), ramp=True):
+        """Keep ``self.G_ema`` / ``self.E_ema`` (``None`` for a network not in ``nets``): copies of the live G / E at their
+        current weights -- same class and ``state_dict()`` layout, eval mode, no gradients -- that every ``train()`` from now on
+        moves by ``e <- e + (1 - d_n) * (p - e)``, ``d_n = min(decay, (1 + n) / (10 + n))`` with ``ramp`` (n = 1, 2, ... counts
+        the updates) or ``decay`` without; batch-norm buffers are carried over.  Two launches per step for everything, captured
+        with the step in graph mode (a recording made before is dropped).  Live weights, losses and optimiser states are
+        bit-identical to a run without it.  Under a process group every rank keeps its own, identical copies."""
+        nets = tuple(nets)
+        if not nets or any(n not in ("G", "E") for n in nets) or len(set(nets)) != len(nets):
+            raise ValueError("enable_ema: nets is a non-empty selection of 'G' and 'E'")
+        if self._ema_scope:
+            raise RuntimeError("enable_ema inside ema_weights()")
+        self._ema = ema.WeightEMA({n: getattr(self, n) for n in ("G", "E") if n in nets}, decay, ramp)
+        self.G_ema, self.E_ema = self._ema.twins.get("G"), self._ema.twins.get("E")
+        return self
+
+    def disable_ema(self):
+        if self._ema_scope:
+            raise RuntimeError("disable_ema inside ema_weights()")
+        self._ema = None
+        self.G_ema = self.E_ema = None
+
+    @property
+    def ema_updates(self):
+        """Updates done so far (host mirror of the device record's n)."""
+        return self._ema.updates if self._ema is not None else 0
+
+    def _need_ema(self, what):
+        if self._ema is None:
+            raise RuntimeError(f"{what}: the EMA is off (enable_ema)")
+        return self._ema
+
+    def set_ema_decay(self, decay):
+        """Write a new decay into the device record, between steps; a recorded step reads it from there and stays valid."""
+        self._need_ema("set_ema_decay").set_decay(decay)
+
+    def ema_state_dict(self):
+        """{"G": state_dict, "E": state_dict (the selected ones), "updates", "decay", "ramp"} -- a snapshot (cloned tensors)."""
+        return self._need_ema("ema_state_dict").state_dict()
+
+    def load_ema_state_dict(self, sd):
+        """Restore ``ema_state_dict()``; enables the EMA for the networks ``sd`` holds if it is off.  The copies are written in
+        place and the device record is re-seeded in place (outside any capture)."""
+        nets = tuple(n for n in ("G", "E") if n in sd)
+        if self._ema is None or tuple(self._ema.twins) != nets:
+            self.enable_ema(sd["decay"], nets, sd["ramp"])
+        self._ema.load_state_dict(sd)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the scope ``self.G`` / ``self.E`` are the averaged copies, so ``G_transformation`` and the helpers of
+        ``srgan_amd.inference`` that take the trainer sample from them; ``train()`` raises there."""
+        cur = self._need_ema("ema_weights")
+        if self._ema_scope:
+            raise RuntimeError("ema_weights() scopes do not nest")
+        live = (self.G, self.E)
+        self.G = cur.twins.get("G", self.G)
+        self.E = cur.twins.get("E", self.E)
+        self._ema_scope = True
+        try:
+            yield self
+        finally:
+            self.G, self.E = live
+            self._ema_scope = False
 
 
 class _StepGraph:
@@ -672,6 +752,9 @@ class _StepGraph:
         # so is the mark of dp.sync_batch_stats (another autograd function, with exchanges)
         fp.append(tuple((id(m), m.training, m.momentum, m.eps, m.track_running_stats, _is_synced(m)) for net in (sg.G, sg.E)
                         for m in net.modules() if _is_batch_stat(m)))
+        # the EMA's two launches, its record and its table (enable_ema / disable_ema between steps); the decay is device state
+        cur = getattr(sg, "_ema", None)
+        fp.append(cur.fingerprint() if cur is not None else None)
         return tuple(fp)
 
     def _opt_steps(self):
@@ -854,6 +937,8 @@ class _StepGraph:
         self.terms = dict(sg.loss_terms)
         self._epoch = ops.structure_epoch()
         self._keep = ops.graph_keepalive() + [t for opt in (sg.optG, sg.optD, sg.optE) for t in opt.graph_keepalive()]
+        if sg._ema is not None:
+            self._keep += sg._ema.graph_keepalive()
         self._baked = self._fingerprint()
 
     def _abandon(self, err, snap, keep_graph_mode=False):
@@ -864,6 +949,8 @@ class _StepGraph:
         sg = self.sg
         for opt, c in zip((sg.optG, sg.optD, sg.optE), snap):
             opt.restore_host_counters(c)          # the recording advanced them without running anything
+        if sg._ema is not None:
+            sg._ema.updates = self._ema_snap
         warnings.warn("SRGAN_training: the step could not be recorded as " + ("ONE hipGraph with captured collectives" if keep_graph_mode
                                                                               else "hipGraph segments") + " on every rank"
                       + (f" (this rank: {type(err).__name__}: {err})" if err is not None else "")
@@ -896,6 +983,7 @@ class _StepGraph:
         if self.graph is None:
             err = None
             snap = [opt.host_counters() for opt in (sg.optG, sg.optD, sg.optE)]
+            self._ema_snap = sg._ema.updates if sg._ema is not None else 0
             try:
                 self._capture()      # records; the host-side optimiser counters advanced while recording
             except Exception as e:   # noqa: BLE001 -- under a process group the ranks first agree on what happened
@@ -904,6 +992,8 @@ class _StepGraph:
                     # having run, caches may describe operands whose fill was only recorded, and graph mode stays off
                     for opt, c in zip((sg.optG, sg.optD, sg.optE), snap):
                         opt.restore_host_counters(c)
+                    if sg._ema is not None:
+                        sg._ema.updates = self._ema_snap
                     ops.invalidate_packed()
                     self._drop()
                     sg._graph = None
@@ -920,10 +1010,15 @@ class _StepGraph:
                 self._force_segmented = self._force_segmented or self._last_single
                 return self._abandon(err, snap, keep_graph_mode=retry)
             self._deltas = [opt.counters_since(c) for opt, c in zip((sg.optG, sg.optD, sg.optE), snap)]
+            self._ema_delta = sg._ema.updates - self._ema_snap if sg._ema is not None else 0
+            ema_moved = 0                # the recording advanced the host mirror already
         else:
             for opt, d in zip((sg.optG, sg.optD, sg.optE), self._deltas):
                 opt.advance_host(d)
+            ema_moved = self._ema_delta
         self.graph.replay()
+        if sg._ema is not None:
+            sg._ema.after_replay(ema_moved)   # the replay wrote the copies through raw pointers
         self._graph_ran = True
         self._steps = self._opt_steps()
         sg.source_image = self.x
