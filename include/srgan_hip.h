@@ -469,6 +469,28 @@ int srgan_ema_state_init(void* state, float decay, int ramp, int n_done, void* s
 int srgan_ema_state_set_decay(void* state, float decay, void* stream);
 int srgan_ema_multi_dev(const void* table, int n_records, long long total_chunks, void* state, void* stream);
 
+/* Device-side gradient guard of an optimiser: GradScaler's "found inf, skip the step" and
+ * torch.nn.utils.clip_grad_norm_(norm_type=2) for a step the host never sees (a replayed hipGraph).  Extension, no counterpart
+ * in the reference.  A 32-byte DEVICE record {float max_norm, norm, scale; int skip, steps, skipped, clipped, pad} holds the
+ * decision of the last step and three cumulative counters; max_norm = +inf means no clipping (NaN and values <= 0 are refused),
+ * srgan_grad_guard_state_init zeroes the counters, srgan_grad_guard_state_set_max_norm changes the threshold between steps.
+ * srgan_grad_guard_reduce = two launches over `table` (device memory): n_records records of three 64-bit words
+ * {g, numel, chunk0}, chunk0 as in srgan_ema_multi_dev for chunks of 4096 elements.  First one fp32 partial of sum g^2 per
+ * chunk into `ws` (srgan_grad_guard_workspace(total_chunks) bytes; add depth 24 per chunk: 16 serial fused multiply-adds per
+ * thread, an 8-level tree), then one workgroup sums the partials in double in a fixed order and writes norm = float(sqrt(S)),
+ * skip = S is not finite, scale = skip ? 0 : min(1, max_norm / (norm + 1e-6f)) in fp32, steps += 1, skipped / clipped += 1.
+ * No atomics: the result does not depend on the grid.  srgan_adam_multi_dev_guard = srgan_adam_multi_dev behind the record: the
+ * tick runs as always (t += 1 even for a skipped step), the update stores nothing when skip is set and otherwise runs the same
+ * arithmetic on g * scale (one fp32 multiply; the gradients are not written; scale = 1 leaves every result bit-identical). */
+size_t srgan_grad_guard_state_bytes(void);
+int srgan_grad_guard_state_init(void* state, float max_norm, void* stream);
+int srgan_grad_guard_state_set_max_norm(void* state, float max_norm, void* stream);
+size_t srgan_grad_guard_workspace(long long total_chunks);
+int srgan_grad_guard_reduce(const void* table, int n_records, long long total_chunks, void* ws, size_t ws_bytes, void* state,
+                            void* stream);
+int srgan_adam_multi_dev_guard(const void* table, int n_tensors, long long max_numel, void* adam_state, void* guard_state,
+                               void* stream);
+
 /* Small host -> device upload (pointer tables: <= 1 MiB, multiple of 4 bytes) carried in kernel arguments: nothing to keep
  * alive on the host after the call returns, and a captured hipGraph stores the bytes in its node instead of re-reading a host
  * address at replay (no reference counterpart; plumbing of the multi-tensor ops above). */

@@ -2,6 +2,7 @@
 // fused Adam.  NHWC fp32.  Reference call sites are listed in include/srgan_hip.h.
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include "common.h"
 
@@ -349,8 +350,24 @@ __global__ void adam_tick_kernel(AdamState* s) {
   s->step_size = (float)((double)s->lr / bc1);
   s->inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
 }
-__global__ __launch_bounds__(256) void adam_multi_dev_kernel(const unsigned long long* __restrict__ table,
-                                                             const AdamState* __restrict__ st) {
+// The scaled gradient enters the update as an opaque value, like the loaded one of the plain kernel: left visible, the product
+// g * scale changes which of the two multiplies of beta * m + (1 - beta) * g the compiler contracts into the fused multiply-add
+// (fma(1 - beta1, g, beta1 * m) in the plain kernel became fma(beta1, m, (1 - beta1) * g)), and the guarded update with
+// scale = 1 no longer matched the plain one bit for bit.
+__device__ __forceinline__ float adam_opaque(float x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+__device__ __forceinline__ f32x4 adam_opaque(f32x4 x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+// The update of one blockIdx.y record of the table, shared by the plain and the guarded kernel so that the two cannot drift:
+// kScaled multiplies every gradient element by `scale` first (one fp32 multiply, the gradient tensor itself is not written) and
+// is otherwise the same arithmetic; with kScaled = false `scale` is not read.
+template <bool kScaled>
+__device__ __forceinline__ void adam_multi_dev_update(const unsigned long long* __restrict__ table,
+                                                      const AdamState* __restrict__ st, float scale) {
   const float step_size = st->step_size, beta1 = st->beta1, beta2 = st->beta2, eps = st->eps, inv_sqrt_bc2 = st->inv_sqrt_bc2;
   const unsigned long long* rec = table + (size_t)blockIdx.y * 5;
   float* __restrict__ p = reinterpret_cast<float*>(rec[0]);
@@ -364,7 +381,8 @@ __global__ __launch_bounds__(256) void adam_multi_dev_kernel(const unsigned long
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const long long i = c0 + (j * 256 + threadIdx.x) * 4;
-        const f32x4 gi = *reinterpret_cast<const f32x4*>(g + i);
+        f32x4 gi = *reinterpret_cast<const f32x4*>(g + i);
+        if (kScaled) gi = adam_opaque(gi * scale);
         const f32x4 mi = beta1 * *reinterpret_cast<const f32x4*>(m + i) + (1.f - beta1) * gi;
         const f32x4 vi = beta2 * *reinterpret_cast<const f32x4*>(v + i) + (1.f - beta2) * gi * gi;
         f32x4 pi = *reinterpret_cast<const f32x4*>(p + i);
@@ -377,7 +395,8 @@ __global__ __launch_bounds__(256) void adam_multi_dev_kernel(const unsigned long
     } else {
       const long long end = c0 + 4096 < n ? c0 + 4096 : n;
       for (long long i = c0 + threadIdx.x; i < end; i += 256) {
-        const float gi = g[i];
+        float gi = g[i];
+        if (kScaled) gi = adam_opaque(gi * scale);
         const float mi = beta1 * m[i] + (1.f - beta1) * gi;
         const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
         m[i] = mi;
@@ -386,6 +405,108 @@ __global__ __launch_bounds__(256) void adam_multi_dev_kernel(const unsigned long
       }
     }
   }
+}
+__global__ __launch_bounds__(256) void adam_multi_dev_kernel(const unsigned long long* __restrict__ table,
+                                                             const AdamState* __restrict__ st) {
+  adam_multi_dev_update<false>(table, st, 1.f);
+}
+
+// ---- device-side gradient guard (extension, no counterpart in the reference) ------------------------------------------------------
+// GradScaler's "found inf: skip the step" and clip_grad_norm_ (norm type 2) for an optimiser whose step the host never sees (a
+// replayed hipGraph).  One record per optimiser; norm / scale / skip are those of the last step, the counters are cumulative.
+struct GuardState { float max_norm, norm, scale; int skip, steps, skipped, clipped, pad; };
+static_assert(sizeof(GuardState) == 32, "GuardState layout");
+__global__ void guard_state_init_kernel(GuardState* s, float max_norm) {
+  s->max_norm = max_norm; s->norm = 0.f; s->scale = 1.f; s->skip = 0; s->steps = 0; s->skipped = 0; s->clipped = 0; s->pad = 0;
+}
+__global__ void guard_state_max_norm_kernel(GuardState* s, float max_norm) { s->max_norm = max_norm; }
+
+// Sum of squares of every gradient, one fp32 partial per 4096-element chunk.  `table`: n_records records of three 64-bit words
+// {g, numel, chunk0}; the work is the flat chunk list of ema_multi_dev_kernel (chunk0 = prefix sum of ceil(numel / 4096)), so 300
+// tiny tensors cost one chunk each.  Element e of a chunk belongs to thread (e / 4) % 256, slot (e / 1024) * 4 + e % 4 -- the same
+// owner whether the chunk is read with 16-byte loads (aligned pointer, full chunk) or element by element (tail, misaligned view;
+// missing elements count as +0, which an add returns unchanged), so a partial does not depend on the path taken.
+// Add depth of one chunk, D = 24: 16 serial fused multiply-adds per thread (x * x + acc, ONE rounding each, slot order), 6 levels
+// of the xor butterfly over the 64 lanes of a wave, 2 levels over the 4 waves through LDS ((w0 + w1) + (w2 + w3)).  Every partial
+// has one owner block and a fixed order: no atomics, and the grid only decides which block computes which chunk.
+constexpr int kGuardChunk = 4096;
+constexpr int kGuardRecWords = 3;
+__global__ __launch_bounds__(256) void grad_sumsq_partials_kernel(const unsigned long long* __restrict__ table, int n_records,
+                                                                  long long total_chunks, float* __restrict__ partials) {
+  __shared__ float red[4];
+  for (long long ch = blockIdx.x; ch < total_chunks; ch += gridDim.x) {
+    int lo = 0, hi = n_records - 1;          // the last record whose first chunk is <= ch (block-uniform: scalar loads)
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if ((long long)table[(size_t)mid * kGuardRecWords + 2] <= ch) lo = mid; else hi = mid - 1;
+    }
+    const unsigned long long* rec = table + (size_t)lo * kGuardRecWords;
+    const float* __restrict__ g = reinterpret_cast<const float*>(rec[0]);
+    const long long n = (long long)rec[1];
+    const long long c0 = (ch - (long long)rec[2]) * kGuardChunk;
+    f32x4 x[4];
+    if (c0 >= 0 && c0 + kGuardChunk <= n && (rec[0] & 15) == 0) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) x[j] = *reinterpret_cast<const f32x4*>(g + c0 + (j * 256 + threadIdx.x) * 4);
+    } else {                                  // (a table whose prefix sums disagree with its sizes reads nothing: partial 0)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const long long i = c0 + (j * 256 + threadIdx.x) * 4 + e;
+          x[j][e] = (c0 >= 0 && i < n) ? g[i] : 0.f;
+        }
+      }
+    }
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = __builtin_fmaf(x[j][e], x[j][e], acc);
+    }
+    acc = wave_sum(acc);
+    __syncthreads();                          // the previous chunk's reads of red[]
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[ch] = (red[0] + red[1]) + (red[2] + red[3]);
+  }
+}
+
+// One workgroup: S = sum of the partials in double -- thread t adds partials t, t + 256, ... in ascending order, then a fixed
+// LDS tree over the 256 threads -- and the decision.  S not finite (a NaN, an Inf, squares that overflowed): skip.  Otherwise
+// scale = min(1, max_norm / (norm + 1e-6f)) in fp32 (clip_grad_norm_; max_norm = +inf gives exactly 1).
+__global__ __launch_bounds__(256) void grad_guard_finalize_kernel(const float* __restrict__ partials, long long total_chunks,
+                                                                  GuardState* __restrict__ s) {
+  __shared__ double red[256];
+  double acc = 0.0;
+  for (long long i = threadIdx.x; i < total_chunks; i += 256) acc += (double)partials[i];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double S = red[0];
+    const float norm = (float)sqrt(S);
+    const bool skip = !isfinite(S);
+    const float scale = skip ? 0.f : fminf(1.f, s->max_norm / (norm + 1e-6f));
+    s->norm = norm;
+    s->scale = scale;
+    s->skip = skip ? 1 : 0;
+    s->steps += 1;
+    if (skip) s->skipped += 1;
+    else if (scale < 1.f) s->clipped += 1;
+  }
+}
+
+// adam_multi_dev_kernel behind the guard record: nothing is stored when the step is skipped, otherwise the update runs on
+// g * scale (scale = 1 returns g bit for bit, so an idle guard changes no result).
+__global__ __launch_bounds__(256) void adam_multi_dev_guard_kernel(const unsigned long long* __restrict__ table,
+                                                                   const AdamState* __restrict__ st,
+                                                                   const GuardState* __restrict__ gs) {
+  if (gs->skip) return;
+  adam_multi_dev_update<true>(table, st, gs->scale);
 }
 
 // ---- exponential moving average of the sampling weights (extension, no counterpart in the reference) ------------------
@@ -685,6 +806,58 @@ extern "C" int srgan_adam_multi_dev(const void* table, int n_tensors, long long 
   hipLaunchKernelGGL(srgan::adam_multi_dev_kernel, dim3(bx, (unsigned)n_tensors), dim3(256), 0, as_stream(stream),
                      reinterpret_cast<const unsigned long long*>(table), static_cast<const srgan::AdamState*>(state));
   return check_launch("adam_multi_dev_kernel");
+}
+
+extern "C" size_t srgan_grad_guard_state_bytes(void) { return sizeof(srgan::GuardState); }
+
+extern "C" int srgan_grad_guard_state_init(void* state, float max_norm, void* stream) {
+  SRGAN_REQUIRE(state && max_norm > 0.f, "grad_guard_state_init: bad argument (max_norm > 0, +inf = no clipping; NaN refused)");
+  hipLaunchKernelGGL(srgan::guard_state_init_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::GuardState*>(state),
+                     max_norm);
+  return check_launch("guard_state_init_kernel");
+}
+
+extern "C" int srgan_grad_guard_state_set_max_norm(void* state, float max_norm, void* stream) {
+  SRGAN_REQUIRE(state && max_norm > 0.f, "grad_guard_state_set_max_norm: bad argument (max_norm > 0, +inf = no clipping; NaN refused)");
+  hipLaunchKernelGGL(srgan::guard_state_max_norm_kernel, dim3(1), dim3(1), 0, as_stream(stream),
+                     static_cast<srgan::GuardState*>(state), max_norm);
+  return check_launch("guard_state_max_norm_kernel");
+}
+
+extern "C" size_t srgan_grad_guard_workspace(long long total_chunks) {
+  if (total_chunks <= 0) {
+    srgan::set_error("grad_guard_workspace: bad argument (total_chunks > 0)");
+    return 0;
+  }
+  return (size_t)total_chunks * sizeof(float);
+}
+
+extern "C" int srgan_grad_guard_reduce(const void* table, int n_records, long long total_chunks, void* ws, size_t ws_bytes,
+                                       void* state, void* stream) {
+  SRGAN_REQUIRE(table && ws && state && n_records > 0 && total_chunks > 0, "grad_guard_reduce: bad argument");
+  SRGAN_REQUIRE(total_chunks >= n_records, "grad_guard_reduce: %lld chunks for %d records (every record holds at least one)",
+                total_chunks, n_records);
+  SRGAN_REQUIRE(ws_bytes >= (size_t)total_chunks * sizeof(float), "grad_guard_reduce: workspace of %zu bytes, %zu needed", ws_bytes,
+                (size_t)total_chunks * sizeof(float));
+  SRGAN_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 3) == 0, "grad_guard_reduce: workspace not 4-byte aligned");
+  // memory bound: one block per chunk up to 256 CUs x 8 blocks, the rest by grid stride
+  const unsigned bx = (unsigned)std::min<long long>(total_chunks, 2048);
+  hipLaunchKernelGGL(srgan::grad_sumsq_partials_kernel, dim3(bx), dim3(256), 0, as_stream(stream),
+                     reinterpret_cast<const unsigned long long*>(table), n_records, total_chunks, static_cast<float*>(ws));
+  hipLaunchKernelGGL(srgan::grad_guard_finalize_kernel, dim3(1), dim3(256), 0, as_stream(stream), static_cast<const float*>(ws),
+                     total_chunks, static_cast<srgan::GuardState*>(state));
+  return check_launch("grad_guard_reduce");
+}
+
+extern "C" int srgan_adam_multi_dev_guard(const void* table, int n_tensors, long long max_numel, void* adam_state, void* guard_state,
+                                          void* stream) {
+  SRGAN_REQUIRE(table && adam_state && guard_state && n_tensors > 0 && max_numel > 0, "adam_multi_dev_guard: bad argument");
+  hipLaunchKernelGGL(srgan::adam_tick_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::AdamState*>(adam_state));
+  const unsigned bx = (unsigned)std::max<long long>(1, std::min<long long>(ceil_div(max_numel, 4096), 2048));
+  hipLaunchKernelGGL(srgan::adam_multi_dev_guard_kernel, dim3(bx, (unsigned)n_tensors), dim3(256), 0, as_stream(stream),
+                     reinterpret_cast<const unsigned long long*>(table), static_cast<const srgan::AdamState*>(adam_state),
+                     static_cast<const srgan::GuardState*>(guard_state));
+  return check_launch("adam_multi_dev_guard_kernel");
 }
 
 extern "C" size_t srgan_ema_state_bytes(void) { return sizeof(srgan::EmaState); }

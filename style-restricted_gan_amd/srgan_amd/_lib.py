@@ -175,6 +175,12 @@ SIGNATURES = {
     "srgan_ema_state_init": (c_int, [P, c_float, c_int, c_int, P]),
     "srgan_ema_state_set_decay": (c_int, [P, c_float, P]),
     "srgan_ema_multi_dev": (c_int, [P, c_int, c_longlong, P, P]),
+    "srgan_grad_guard_state_bytes": (c_size_t, []),
+    "srgan_grad_guard_state_init": (c_int, [P, c_float, P]),
+    "srgan_grad_guard_state_set_max_norm": (c_int, [P, c_float, P]),
+    "srgan_grad_guard_workspace": (c_size_t, [c_longlong]),
+    "srgan_grad_guard_reduce": (c_int, [P, c_int, c_longlong, P, c_size_t, P, P]),
+    "srgan_adam_multi_dev_guard": (c_int, [P, c_int, c_longlong, P, P, P]),
     "srgan_upload_small": (c_int, [P, P, c_size_t, P]),
     "srgan_maxpool2_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "srgan_pairwise_dist": (c_int, [P, c_int, P, c_int, c_int, P, P]),

@@ -12,6 +12,7 @@ the reference's train step relies on, util_notebook.py:664-690); activations, no
 and the CBIN gamma copy are the forward-time values.
 """
 import ctypes
+import struct
 import weakref
 
 import torch
@@ -2403,6 +2404,75 @@ def adam_multi_step_(table_dev, n_tensors, max_numel, lr, beta1, beta2, eps, ste
     """One launch of torch-1.4 Adam over a list of tensors described by a device pointer table (see optim.Adam)."""
     _lib.check(_lib.load().srgan_adam_multi(_ptr(table_dev), int(n_tensors), int(max_numel), float(lr), float(beta1),
                                             float(beta2), float(eps), int(step), _stream()), "adam_multi")
+
+
+# ---- device-side gradient guard (optim.Adam.enable_grad_guard; extension, no counterpart in the reference) ---------------------
+GRAD_GUARD_CHUNK = 4096        # elements per partial of grad_guard_reduce_ (the unit of a reduce table's chunk0 prefix sums)
+
+
+def _max_norm_arg(max_norm):
+    """None -> +inf (no clipping); anything else must be a finite-or-inf float > 0 (the C ABI refuses the rest)."""
+    return float("inf") if max_norm is None else float(max_norm)
+
+
+def grad_guard_state_new(device, max_norm=None):
+    """Device-resident record {max_norm, norm, scale, skip, steps, skipped, clipped, pad} with the counters at zero."""
+    lib = _lib.load()
+    st = torch.empty(lib.srgan_grad_guard_state_bytes(), dtype=torch.uint8, device=device)
+    _lib.check(lib.srgan_grad_guard_state_init(_ptr(st), _max_norm_arg(max_norm), _stream()), "grad_guard_state_init")
+    return st
+
+
+def grad_guard_state_set_max_norm(state, max_norm):
+    _lib.check(_lib.load().srgan_grad_guard_state_set_max_norm(_ptr(state), _max_norm_arg(max_norm), _stream()),
+               "grad_guard_state_set_max_norm")
+
+
+def grad_guard_state_read(state):
+    """The record as a dict; synchronises the current stream (the only host read of the guard)."""
+    torch.cuda.current_stream(state.device).synchronize()
+    max_norm, norm, scale, skip, steps, skipped, clipped, _ = struct.unpack("fffiiiii", state.cpu().numpy().tobytes()[:32])
+    return dict(max_norm=None if max_norm == float("inf") else max_norm, norm=norm, scale=scale, skip=bool(skip), steps=steps,
+                skipped=skipped, clipped=clipped)
+
+
+def grad_guard_workspace_bytes(total_chunks):
+    n = int(_lib.load().srgan_grad_guard_workspace(int(total_chunks)))
+    if n == 0:
+        _lib.check(-1, "grad_guard_workspace")
+    return n
+
+
+def grad_guard_table(grads, device, out=None):
+    """Reduce table of a list of contiguous fp32 gradient tensors: three 64-bit words {g, numel, chunk0} per non-empty tensor.
+    Returns (device table, n_records, total_chunks)."""
+    rows, at, n = [], 0, 0
+    for g in grads:
+        _require_gpu(g, "grad_guard")
+        if not g.is_contiguous():
+            raise _lib.SrganHipError("grad_guard: gradients must be contiguous")
+        if g.numel():
+            rows.extend((g.data_ptr(), g.numel(), at))
+            at += -(-g.numel() // GRAD_GUARD_CHUNK)
+            n += 1
+    if not rows:
+        raise _lib.SrganHipError("grad_guard: no gradient elements")
+    return upload_small(struct.pack(f"{len(rows)}q", *rows), device, out=out), n, at
+
+
+def grad_guard_reduce_(table_dev, n_records, total_chunks, ws, state):
+    """Two launches: one fp32 partial of sum g^2 per 4096-element chunk of the table's tensors into ``ws``, then the partials
+    summed in double in a fixed order and norm / scale / skip / the counters written into the guard record.  hipGraph-capturable;
+    nothing comes back to the host."""
+    _lib.check(_lib.load().srgan_grad_guard_reduce(_ptr(table_dev), int(n_records), int(total_chunks), _ptr(ws),
+                                                   ws.numel() * ws.element_size(), _ptr(state), _stream()), "grad_guard_reduce")
+
+
+def adam_multi_dev_guard_(table_dev, n_tensors, max_numel, state, guard_state):
+    """``adam_multi_dev_`` behind a guard record: t += 1 as always; no store when the record says skip, else the update on
+    g * scale (the gradients are not written)."""
+    _lib.check(_lib.load().srgan_adam_multi_dev_guard(_ptr(table_dev), int(n_tensors), int(max_numel), _ptr(state),
+                                                      _ptr(guard_state), _stream()), "adam_multi_dev_guard")
 
 
 # ---- exponential moving average of the sampling weights (srgan_amd.ema; extension, no counterpart in the reference) --------

@@ -10,6 +10,15 @@ The step counter and the hyper-parameters of a parameter cohort live in a small 
 baking t or lr into the launch, so a train step captured into a hipGraph advances the optimiser on every
 replay.  The host keeps ``state[p]["step"]`` in step for ``state_dict()`` / resume (``advance_host`` after a
 replay) and pushes ``lr`` changes made by a scheduler to the device record (``sync_device``).
+
+Gradient guard (``enable_grad_guard``; off by default, extension): every ``step()`` first reduces ``S = sum g^2`` over every
+parameter that has a gradient in that call (all groups and cohorts) on the device.  ``S`` not finite -- a NaN, an Inf, squares that
+overflow -- skips the step: no parameter or moment is written (GradScaler's "found inf").  With ``max_norm`` set the update runs
+on ``g * min(1, max_norm / (sqrt(S) + 1e-6))`` (``clip_grad_norm_``, norm type 2; the gradient tensors are not modified).  The
+decision, the scale and three cumulative counters live in a 32-byte device record, so a replayed hipGraph decides, skips, clips
+and counts without the host.  A skipped step still counts as a step -- ``t`` and ``state[p]["step"]`` advance -- which keeps the
+host mirrors exact without a device read; the price is a bias correction one step ahead after each skip.  A guard that does not
+trigger changes no bit of the result (``g * 1.0f == g``).  The guard is not part of ``state_dict()``.
 """
 import struct
 
@@ -29,12 +38,30 @@ class _Cohort:
         self.n = self.max_numel = 0
 
 
+class _Guard:
+    """Device record, reduce table and partials workspace of one optimiser's gradient guard."""
+    __slots__ = ("state", "max_norm", "table", "rows", "ws", "chunks")
+
+    def __init__(self, device, max_norm):
+        self.state = ops.grad_guard_state_new(device, max_norm)
+        self.max_norm = max_norm
+        self.table = self.ws = None         # sized by the first guarded step (and re-sized if a later one needs more)
+        self.rows = self.chunks = 0
+
+
+def _check_max_norm(max_norm):
+    if max_norm is not None and not float(max_norm) > 0.0:        # (NaN compares false)
+        raise ValueError(f"grad guard: max_norm must be None (no clipping) or a number > 0, got {max_norm!r}")
+    return None if max_norm is None else float(max_norm)
+
+
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
         if lr < 0.0 or eps < 0.0 or not (0.0 <= betas[0] < 1.0) or not (0.0 <= betas[1] < 1.0):
             raise ValueError("invalid Adam hyper-parameters")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self._cohorts = {}
+        self._guard = None
 
     def _cohort(self, gi, params, group, steps_done):
         key = (gi,) + tuple(id(p) for p in params)
@@ -61,38 +88,130 @@ class Adam(torch.optim.Optimizer):
             co.lr = group["lr"]
         return co
 
+    def _collect(self, group):
+        """completed step count -> [(p, g, m, v)] of one group: one multi-tensor launch per count; advances state[p]["step"]"""
+        batches = {}
+        for p in group["params"]:
+            if p.grad is None:       # torch 1.4 skips parameters that received no gradient
+                continue
+            st = self.state[p]
+            if len(st) == 0:
+                st["step"] = 0
+                st["exp_avg"] = torch.zeros_like(p.data, memory_format=torch.contiguous_format)
+                st["exp_avg_sq"] = torch.zeros_like(p.data, memory_format=torch.contiguous_format)
+            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+            if not p.data.is_contiguous():
+                raise RuntimeError("srgan_amd.optim.Adam needs contiguous parameters")
+            batches.setdefault(int(st["step"]), []).append((p, g, st["exp_avg"], st["exp_avg_sq"]))
+            st["step"] += 1
+        return batches
+
+    def _update(self, gi, group, batches, guard):
+        kept = []
+        for steps_done, items in batches.items():
+            params = [it[0] for it in items]
+            co = self._cohort(gi, params, group, steps_done)
+            rows = []
+            for p, g, m, v in items:
+                rows.extend((p.data.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()))
+            # the gradient pointers change from step to step (and are the capture-time ones inside a graph): the table is
+            # rewritten by every step, in stream order, through kernel arguments
+            ops.upload_small(struct.pack(f"{len(rows)}q", *rows), params[0].device, out=co.table)
+            if guard is None:
+                ops.adam_multi_dev_(co.table, co.n, co.max_numel, co.state)
+            else:
+                ops.adam_multi_dev_guard_(co.table, co.n, co.max_numel, co.state, guard.state)
+            co.steps = steps_done + 1
+            kept = items
+        ops.mark_stale(group["params"])                  # parameters were written through raw pointers
+        return kept
+
+    def _reduce(self, guard, grads):
+        """The guard's two launches over every gradient of this call; (re)sizes its table and workspace outside a capture."""
+        device = grads[0].device
+        rows = sum(1 for g in grads if g.numel())
+        chunks = sum(-(-g.numel() // ops.GRAD_GUARD_CHUNK) for g in grads)
+        if guard.table is None or rows > guard.rows or chunks > guard.chunks:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("srgan_amd.optim.Adam: the gradient guard's table / workspace first appear (or grow) inside a "
+                                   "hipGraph capture -- run one eager train step with the guard enabled first")
+            if guard.table is not None:
+                ops.bump_structure_epoch()       # a captured step points at the buffers being replaced
+            guard.rows, guard.chunks = max(rows, guard.rows), max(chunks, guard.chunks)
+            guard.table = torch.empty(24 * guard.rows, dtype=torch.uint8, device=device)
+            guard.ws = torch.empty(ops.grad_guard_workspace_bytes(guard.chunks), dtype=torch.uint8, device=device)
+        table, n_records, total_chunks = ops.grad_guard_table(grads, device, out=guard.table)
+        ops.grad_guard_reduce_(table, n_records, total_chunks, guard.ws, guard.state)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        for gi, group in enumerate(self.param_groups):
-            batches = {}                 # completed step count -> [(p, g, m, v)]: one multi-tensor launch per count
-            for p in group["params"]:
-                if p.grad is None:       # torch 1.4 skips parameters that received no gradient
-                    continue
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p.data, memory_format=torch.contiguous_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p.data, memory_format=torch.contiguous_format)
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                if not p.data.is_contiguous():
-                    raise RuntimeError("srgan_amd.optim.Adam needs contiguous parameters")
-                batches.setdefault(int(st["step"]), []).append((p, g, st["exp_avg"], st["exp_avg_sq"]))
-                st["step"] += 1
-            for steps_done, items in batches.items():
-                params = [it[0] for it in items]
-                co = self._cohort(gi, params, group, steps_done)
-                rows = []
-                for p, g, m, v in items:
-                    rows.extend((p.data.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()))
-                # the gradient pointers change from step to step (and are the capture-time ones inside a graph): the table is
-                # rewritten by every step, in stream order, through kernel arguments
-                ops.upload_small(struct.pack(f"{len(rows)}q", *rows), params[0].device, out=co.table)
-                ops.adam_multi_dev_(co.table, co.n, co.max_numel, co.state)
-                co.steps = steps_done + 1
-                self._keep_alive = items                     # until the next step: the launch reads them asynchronously
-            ops.mark_stale(group["params"])                  # parameters were written through raw pointers
+        guard = self._guard
+        if guard is None:
+            for gi, group in enumerate(self.param_groups):
+                kept = self._update(gi, group, self._collect(group), None)
+                if kept:
+                    self._keep_alive = kept                  # until the next step: the launch reads them asynchronously
+            return loss
+        # guarded: ONE reduction over the gradients of all groups and cohorts of this call decides for all of them, so the
+        # gradients are collected first; then per cohort the tick and the guarded update, as above
+        collected = [self._collect(group) for group in self.param_groups]
+        items = [it for batches in collected for its in batches.values() for it in its]
+        if items:
+            self._reduce(guard, [it[1] for it in items])
+            self._keep_alive = items
+        for gi, (group, batches) in enumerate(zip(self.param_groups, collected)):
+            self._update(gi, group, batches, guard)
         return loss
+
+    # -- gradient guard -------------------------------------------------------------------------------------------------
+    def enable_grad_guard(self, max_norm=None):
+        """Skip steps whose gradients are not finite and, with ``max_norm``, clip by the global 2-norm -- on the device, see the
+        module docstring.  Between steps only; a hipGraph recording of the step made before is dropped by its owner
+        (``grad_guard_fingerprint``).  Enabling again re-creates the record (counters at zero)."""
+        max_norm = _check_max_norm(max_norm)
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("srgan_amd.optim.Adam: gradient guard enabled inside a hipGraph capture -- enable it between steps")
+        params = [p for g in self.param_groups for p in g["params"]]
+        if not params or params[0].device.type != "cuda":
+            raise RuntimeError("srgan_amd.optim.Adam: the gradient guard is a HIP kernel; the parameters are not on the GPU "
+                               "(no CPU fallback)")
+        if self._guard is not None:
+            ops.bump_structure_epoch()
+        self._guard = _Guard(params[0].device, max_norm)
+        return self
+
+    def disable_grad_guard(self):
+        if self._guard is not None and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("srgan_amd.optim.Adam: gradient guard disabled inside a hipGraph capture")
+        self._guard = None
+
+    def _need_guard(self, what):
+        if self._guard is None:
+            raise RuntimeError(f"{what}: the gradient guard is off (enable_grad_guard)")
+        return self._guard
+
+    def set_max_norm(self, max_norm):
+        """Write a new clipping threshold (``None``: no clipping) into the device record, between steps; a recorded step reads it
+        from there and stays valid."""
+        guard = self._need_guard("set_max_norm")
+        max_norm = _check_max_norm(max_norm)
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("srgan_amd.optim.Adam: max_norm changed inside a hipGraph capture")
+        ops.grad_guard_state_set_max_norm(guard.state, max_norm)
+        guard.max_norm = max_norm
+
+    def grad_guard_stats(self):
+        """{"max_norm", "norm", "scale", "skip", "steps", "skipped", "clipped"} read from the device record: norm / scale / skip
+        of the last ``step()``, cumulative counters since ``enable_grad_guard``.  SYNCHRONISES the current stream -- the only
+        point at which the host looks at the guard."""
+        return ops.grad_guard_state_read(self._need_guard("grad_guard_stats").state)
+
+    def grad_guard_fingerprint(self):
+        """What a recording of ``step()`` bakes in of the guard: whether it is on, and which record (the threshold is device
+        state and stays out)."""
+        g = self._guard
+        return None if g is None else (id(g), g.state.data_ptr())
 
     # -- hipGraph support --------------------------------------------------------------------------------------------
     def sync_device(self):
@@ -104,7 +223,10 @@ class Adam(torch.optim.Optimizer):
                 co.lr = lr
 
     def graph_keepalive(self):
-        return [t for co in self._cohorts.values() for t in (co.state, co.table)]
+        keep = [t for co in self._cohorts.values() for t in (co.state, co.table)]
+        if self._guard is not None:
+            keep += [t for t in (self._guard.state, self._guard.table, self._guard.ws) if t is not None]
+        return keep
 
     def host_counters(self):
         """Snapshot of the host-side step counters (per-parameter ``state[p]["step"]`` and the cohorts')."""

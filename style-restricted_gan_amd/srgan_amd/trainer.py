@@ -652,6 +652,82 @@ class SRGAN_training():
             self.enable_ema(sd["decay"], nets, sd["ramp"])
         self._ema.load_state_dict(sd)
 
+    # ------------------------------------------------------------------------------------------
+    # device-side gradient guard (extension, no counterpart in the reference; srgan_amd.optim.Adam.enable_grad_guard)
+    _GUARD_NETS = ("G", "D", "E")
+
+    def _guard_opts(self, nets, what):
+        nets = tuple(nets)
+        if not nets or any(n not in self._GUARD_NETS for n in nets) or len(set(nets)) != len(nets):
+            raise ValueError(f"{what}: nets is a non-empty selection of 'G', 'D' and 'E'")
+        out = {}
+        for n in nets:
+            opt = getattr(self, "opt" + n)
+            if opt is None:
+                raise RuntimeError(f"{what}: opt{n} does not exist yet (call opt_sche_initialization() first)")
+            if not isinstance(opt, Adam):
+                raise TypeError(f"{what}: opt{n} is {type(opt).__module__}.{type(opt).__qualname__}, not srgan_amd.optim.Adam -- the "
+                                "guard lives inside that optimiser's step (call opt_sche_initialization(), or pass that class)")
+            out[n] = opt
+        return out
+
+    @staticmethod
+    def _guard_value(max_norm, n, what):
+        if isinstance(max_norm, dict):
+            if n not in max_norm:
+                raise ValueError(f"{what}: max_norm has no entry for '{n}'")
+            return max_norm[n]
+        return max_norm
+
+    def enable_grad_guard(self, max_norm=None, nets=("G", "D", "E")):
+        """From now on every optimiser step of the selected networks first checks its gradients ON THE DEVICE: a step whose squared
+        gradient norm is not finite (a NaN or Inf anywhere, an overflow in the bf16 mode, a broken image) writes no parameter and
+        no Adam moment, and with ``max_norm`` (a number, or a dict per net; ``None``: no clipping) the update runs on gradients
+        scaled to that global 2-norm (``clip_grad_norm_``).  Works the same in a replayed hipGraph, which the host never looks
+        into; a recording made before is dropped and made again.  A skipped step still advances the step counts (the bias
+        correction runs one step ahead after it).  A guard that does not trigger changes no bit of the run.
+        Data parallel: the check runs on the all-reduced gradients (the optimiser steps come after the reducer has finished), so
+        every rank takes the same decision and no collective is added.  EMA: the update after a skipped step runs as always -- the
+        live weights are unchanged and finite.  ``norm_type="batch"``: the running buffers are written by the forward pass, before
+        any gradient exists, and are NOT protected (``grad_guard_stats()`` still shows the skip).  The returned losses are not
+        filtered: a NaN loss stays NaN."""
+        opts = self._guard_opts(nets, "enable_grad_guard")
+        values = {n: self._guard_value(max_norm, n, "enable_grad_guard") for n in opts}
+        for n, opt in opts.items():
+            opt.enable_grad_guard(values[n])
+        self._guard_changed()
+        return self
+
+    def _guard_changed(self):
+        """The step's launches changed: forget a recording AND the warm-up of the input shape, so that the next step runs eagerly
+        (it sizes the guards' tables and workspaces, which a capture must not create) and the one after records again."""
+        if self._graph is not None:
+            self._graph._drop()
+
+    def set_grad_clip(self, max_norm, nets=("G", "D", "E")):
+        """Write a new clipping threshold (a number, a dict per net, ``None``: no clipping) into the guards' device records,
+        between steps; a recorded step reads it from there and stays valid."""
+        opts = self._guard_opts(nets, "set_grad_clip")
+        for n, opt in opts.items():
+            opt.set_max_norm(self._guard_value(max_norm, n, "set_grad_clip"))
+
+    def disable_grad_guard(self):
+        for n in self._GUARD_NETS:
+            opt = getattr(self, "opt" + n)
+            if isinstance(opt, Adam):
+                opt.disable_grad_guard()
+        self._guard_changed()
+
+    def grad_guard_stats(self):
+        """{"G": {...}, "D": {...}, "E": {...}} of ``optim.Adam.grad_guard_stats()`` (``None`` for a net without a guard): norm,
+        scale and skip of each optimiser's last step and its cumulative steps / skipped / clipped counts.  Reads the device
+        records: SYNCHRONISES the stream."""
+        out = {}
+        for n in self._GUARD_NETS:
+            opt = getattr(self, "opt" + n)
+            out[n] = opt.grad_guard_stats() if isinstance(opt, Adam) and opt._guard is not None else None
+        return out
+
     @contextlib.contextmanager
     def ema_weights(self):
         """Inside the scope ``self.G`` / ``self.E`` are the averaged copies, so ``G_transformation`` and the helpers of
@@ -755,6 +831,9 @@ class _StepGraph:
         # the EMA's two launches, its record and its table (enable_ema / disable_ema between steps); the decay is device state
         cur = getattr(sg, "_ema", None)
         fp.append(cur.fingerprint() if cur is not None else None)
+        # the gradient guards: their reduce launches, the guarded update and the records (enable / disable between steps); the
+        # clipping threshold is device state
+        fp.append(tuple(opt.grad_guard_fingerprint() if isinstance(opt, Adam) else None for opt in (sg.optG, sg.optD, sg.optE)))
         return tuple(fp)
 
     def _opt_steps(self):
