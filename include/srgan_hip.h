@@ -32,6 +32,9 @@ extern "C" {
 
 enum { SRGAN_ACT_NONE = 0, SRGAN_ACT_RELU = 1, SRGAN_ACT_LRELU = 2 };
 enum { SRGAN_PAD_ZERO = 0, SRGAN_PAD_REFLECT = 1 };
+/* criterion kind of the fused loss kernels: nn.MSELoss, or the binary cross-entropy of the slot (nn.BCEWithLogitsLoss on the
+ * discriminator's raw maps, nn.BCELoss on the class probabilities); mean reduction, no weights */
+enum { SRGAN_CRIT_MSE = 0, SRGAN_CRIT_BCE = 1 };
 
 int srgan_abi_version(void);
 const char* srgan_last_error(void);
@@ -387,10 +390,19 @@ int srgan_nhwc_to_nchw(const float* x, float* y, int N, int C, int H, int W, voi
  * Each writes loss[0] (overwrite) and the gradient of `weight * loss` w.r.t. its input. */
 /* get_loss_D, util.py:457-462 with nn.MSELoss: one scale; loss = mean((o-target)^2)*weight */
 int srgan_mse_const(const float* o, long long n, float target, float weight, float* loss, float* d_o, void* stream);
+/* get_loss_D, util.py:457-462 (`criterion(output, targets)` with targets = full_like(output, target)) for either criterion
+ * kind: SRGAN_CRIT_MSE is srgan_mse_const; SRGAN_CRIT_BCE is nn.BCEWithLogitsLoss on the raw map,
+ * loss = weight * mean(max(o,0) - o*target + log1p(exp(-|o|))), d_o = weight * (sigmoid(o) - target) / n; any real target. */
+int srgan_crit_const(const float* o, long long n, float target, float weight, int kind, float* loss, float* d_o, void* stream);
 /* nn.Softmax(dim=1) + get_domainloss_D (util.py:464-468, model.py:333-346): z:[B,n_class] logits,
  * label:[B] int64; q=softmax(z) is written to `q`; loss = mean((q-onehot)^2)*weight; dz via softmax Jacobian. */
 int srgan_softmax_mse(const float* z, const long long* label, int B, int n_class, float weight,
                       float* q, float* loss, float* dz, void* stream);
+/* nn.Softmax(dim=1) + get_domainloss_D (util.py:464-468: `criterion_class(output_class, true_label)`, model.py:333-346) for
+ * either kind: SRGAN_CRIT_MSE is srgan_softmax_mse; SRGAN_CRIT_BCE is nn.BCELoss(q, onehot(label)) with ATen's -100 clamp of
+ * both logs and its 1e-12 floor under q (1 - q) in the gradient (a saturated row: element losses of 100, dz = 0). */
+int srgan_softmax_crit(const float* z, const long long* label, int B, int n_class, float weight, int kind,
+                       float* q, float* loss, float* dz, void* stream);
 /* nn.CrossEntropyLoss() (mean reduction) of the encoder pre-training job, 04_Facial_Recognition-Encoder.ipynb cell 18/22:
  * loss = weight * mean_b(logsumexp(z_b) - z_b[label_b]); dz = weight * (softmax(z) - onehot) / B. */
 int srgan_softmax_xent(const float* z, const long long* label, int B, int n_class, float weight, float* loss,
@@ -415,6 +427,12 @@ int srgan_latent_losses(const float* mu, int B, int d, float n_batch, const floa
 int srgan_d_losses(const float* const* o, const long long* per_row, const float* const* z, int n_scales, int rows,
                    int rows_first, int n_class, const long long* label, float t_first, float t_rest, float w_class,
                    float* vals, float* const* d_o, float* const* dz, void* stream);
+/* srgan_d_losses for any pair of criterion kinds (util.py:457-468 as used by util_notebook.py:582-590 and :622-624 with the
+ * trainer's `criterion` / `criterion_class`): gan_kind selects nn.MSELoss / nn.BCEWithLogitsLoss for the maps, class_kind
+ * nn.MSELoss / nn.BCELoss for softmax(z) against the one-hot label; (SRGAN_CRIT_MSE, SRGAN_CRIT_MSE) is srgan_d_losses. */
+int srgan_d_losses_crit(const float* const* o, const long long* per_row, const float* const* z, int n_scales, int rows,
+                        int rows_first, int n_class, const long long* label, float t_first, float t_rest, float w_class,
+                        int gan_kind, int class_kind, float* vals, float* const* d_o, float* const* dz, void* stream);
 /* out[0] = sum_i w[i] * x[i][0] over n <= 16 device scalars (x, w: host arrays) -- the weighted sum of a phase's loss terms
  * (util_notebook.py:585, :626-662, :677-687) in one launch; srgan_lincomb_bwd: dx[i] = w[i] * g[0]. */
 int srgan_lincomb(const float* const* x, const float* w, int n, float* out, void* stream);
@@ -426,6 +444,11 @@ int srgan_kl_normal(const float* mu, const float* logvar, long long n, float wei
 /* generic nn.MSELoss(a, b) * weight with both gradients (get_domainloss_D on probabilities, util.py:464-468) */
 int srgan_mse_pair(const float* a, const float* b, long long n, float weight, float* loss, float* da, float* db,
                    void* stream);
+/* generic `criterion_class(output_class, true_label)` of get_domainloss_D (util.py:464-468) on probabilities: SRGAN_CRIT_MSE
+ * is srgan_mse_pair; SRGAN_CRIT_BCE is nn.BCELoss(a, b) * weight, a in [0, 1] the probabilities and b the targets, with
+ * da = weight * (a - b) / max(a (1 - a), 1e-12) / n; the targets take no gradient (db must be NULL). */
+int srgan_crit_pair(const float* a, const float* b, long long n, float weight, int kind, float* loss, float* da, float* db,
+                    void* stream);
 /* GaussianHistogram.forward (util.py:521-537) of a 1-D sample x[n] -> h[bins], and its vector-Jacobian product */
 size_t srgan_soft_histogram_workspace(long long n, int bins);
 int srgan_soft_histogram_fwd(const float* x, long long n, int bins, float lo, float hi, float sigma, float* h,

@@ -1,8 +1,8 @@
 // Fused loss reductions of the SRGAN train step: every kernel produces the loss value AND the
 // gradient w.r.t. its input in one launch (wavefront-shuffle reductions, 64-lane waves).
 //
-//   mse_const       get_loss_D  (pyfiles/util.py:457-462, nn.MSELoss against a constant)
-//   softmax_mse     nn.Softmax(dim=1) + get_domainloss_D (model.py:333-346, util.py:464-468)
+//   crit_const      get_loss_D  (pyfiles/util.py:457-462, criterion against a constant: nn.MSELoss / nn.BCEWithLogitsLoss)
+//   softmax_crit    nn.Softmax(dim=1) + get_domainloss_D (model.py:333-346, util.py:464-468: nn.MSELoss / nn.BCELoss)
 //   l1_mean         torch.mean(torch.abs(a-b)) (util_notebook.py:625,639,676,686)
 //   latent_losses   batch-KL (util_notebook.py:644-650), correlation (util.py:470-517),
 //                   histogram imitation (util.py:521-553); closed forms: SURVEY.md Appendix F.2-F.4
@@ -12,27 +12,96 @@
 
 namespace srgan {
 
-__global__ __launch_bounds__(256) void mse_const_kernel(const float* o, long long n, float target, float weight,
-                                                        float* loss, float* d_o) {
+// The criterion kinds of the templated kernels below (SRGAN_CRIT_* of srgan_hip.h).  The MSE instantiations hold the arithmetic
+// of the LSGAN-only kernels they replace, operation for operation.
+constexpr int CRIT_MSE = SRGAN_CRIT_MSE, CRIT_BCE = SRGAN_CRIT_BCE;
+
+// nn.BCEWithLogitsLoss of one logit against the target t (any real t): value max(x,0) - x*t + log1p(exp(-|x|)), and
+// d = sigmoid(x) - t with the sigmoid evaluated from exp(-|x|) <= 1 (no overflow for either sign).
+__device__ __forceinline__ float bce_logit(float x, float t, float& d) {
+  const float e = expf(-fabsf(x));
+  const float r = 1.f / (1.f + e);
+  d = (x >= 0.f ? r : e * r) - t;
+  return fmaxf(x, 0.f) - x * t + log1pf(e);
+}
+
+// nn.BCELoss of one probability p against the target y (ATen binary_cross_entropy: both logs clamped at -100)
+__device__ __forceinline__ float bce_prob(float p, float log_1mp /* log(1 - p) */, float y) {
+  return (y - 1.f) * fmaxf(log_1mp, -100.f) - y * fmaxf(logf(p), -100.f);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void crit_const_kernel(const float* o, long long n, float target, float weight,
+                                                         float* loss, float* d_o) {
   __shared__ float red[16];
   float s = 0.f;
-  const float gscale = 2.f * weight / (float)n;
+  const float gscale = KIND == CRIT_MSE ? 2.f * weight / (float)n : weight / (float)n;
   for (long long i = threadIdx.x; i < n; i += blockDim.x) {
-    const float d = o[i] - target;
-    s += d * d;
-    if (d_o) d_o[i] = gscale * d;
+    if constexpr (KIND == CRIT_MSE) {
+      const float d = o[i] - target;
+      s += d * d;
+      if (d_o) d_o[i] = gscale * d;
+    } else {
+      float d;
+      s += bce_logit(o[i], target, d);
+      if (d_o) d_o[i] = gscale * d;
+    }
   }
   s = block_sum(s, red);
   if (threadIdx.x == 0) loss[0] = weight * s / (float)n;
 }
 
-__global__ __launch_bounds__(256) void softmax_mse_kernel(const float* z, const long long* label, int B, int nc,
-                                                          float weight, float* q, float* loss, float* dz) {
+// One row of nn.BCELoss(softmax(z), onehot(lab)): returns the row's sum of the nc element losses, leaves q in qq and writes
+// dz (may be null) = gs * d(sum)/dz.  With e_j = exp(z_j - max), q_j = e_j / den and r_j = 1 - q_j = (den - e_j) / den formed from
+// the OTHER exponentials (1.f - q_j would carry q_j's rounding error at full size into a difference that can be 1e-5 of it):
+//   dq_j = (q_j - y_j) / max(q_j r_j, 1e-12)          nn.BCELoss's own gradient (ATen binary_cross_entropy_backward), and
+//   dz_j = q_j (dq_j - sum_i q_i dq_i) = q_j dq_j r_j - q_j sum_{i != j} q_i dq_i
+// -- the softmax Jacobian with the j-th term of the sum taken out, so that a class with q -> 1 (dq ~ 1/r) does not leave the
+// difference of two numbers of size 1/r.  A saturated row (q exactly 0 / 1) gives element losses of 100 and dz = 0, as ATen does.
+__device__ __forceinline__ float softmax_bce_row(const float* z, int nc, int lab, float gs, float* qq, float* dz) {
+  float ee[16], rr[16], t[16];
+  float mx = -INFINITY;
+  for (int j = 0; j < nc; ++j) mx = fmaxf(mx, z[j]);
+  float den = 0.f;
+  for (int j = 0; j < nc; ++j) { ee[j] = expf(z[j] - mx); den += ee[j]; }
+  float s = 0.f;
+  for (int j = 0; j < nc; ++j) {
+    float oth = 0.f;
+    for (int i = 0; i < nc; ++i) if (i != j) oth += ee[i];
+    const float q = ee[j] / den, r = oth / den;
+    const float y = j == lab ? 1.f : 0.f;
+    qq[j] = q;
+    // log(1 - q): log1p(-q) for small q (r rounds to 1), log(r) where r is the small one; a q that has rounded to 1 is a
+    // saturated element for nn.BCELoss, which sees only q: log1p(-1) = -inf -> the -100 clamp
+    s += bce_prob(q, (q < 0.5f || q == 1.f) ? log1pf(-q) : logf(r), y);
+    const float dq = gs * (j == lab ? -r : q) / fmaxf(q * r, 1e-12f);
+    t[j] = q * dq;
+    rr[j] = r;
+  }
+  if (dz)
+    for (int j = 0; j < nc; ++j) {
+      float oth = 0.f;
+      for (int i = 0; i < nc; ++i) if (i != j) oth += t[i];
+      dz[j] = t[j] * rr[j] - qq[j] * oth;
+    }
+  return s;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void softmax_crit_kernel(const float* z, const long long* label, int B, int nc,
+                                                           float weight, float* q, float* loss, float* dz) {
   __shared__ float red[16];
   float s = 0.f;
-  const float gscale = 2.f * weight / (float)(B * nc);
+  const float gscale = KIND == CRIT_MSE ? 2.f * weight / (float)(B * nc) : weight / (float)(B * nc);
   for (int b = threadIdx.x; b < B; b += blockDim.x) {
     float zz[16], qq[16];
+    if constexpr (KIND == CRIT_BCE) {
+      for (int j = 0; j < nc; ++j) zz[j] = z[b * nc + j];
+      s += softmax_bce_row(zz, nc, (int)label[b], gscale, qq, dz ? dz + b * nc : nullptr);
+      if (q)
+        for (int j = 0; j < nc; ++j) q[b * nc + j] = qq[j];
+      continue;
+    }
     float mx = -INFINITY;
     for (int j = 0; j < nc; ++j) { zz[j] = z[b * nc + j]; mx = fmaxf(mx, zz[j]); }
     float den = 0.f;
@@ -57,10 +126,11 @@ __global__ __launch_bounds__(256) void softmax_mse_kernel(const float* z, const 
 }
 
 // All losses of one discriminator evaluation in ONE launch (K12 of SURVEY.md 2.2: util.py:457-468 applied by
-// util_notebook.py:582-590 and :622-624): per scale s an LSGAN map o_s [rows][per_s] and class logits z_s [rows][nc]; the
+// util_notebook.py:582-590 and :622-624): per scale s a PatchGAN map o_s [rows][per_s] and class logits z_s [rows][nc]; the
 // first `rows_first` rows are compared with the constant t_first and carry the class loss against `label`, the remaining rows
-// (the translated half of a real | fake batch) with t_rest.  vals = {lsgan_first, class, lsgan_rest, total}, each the MEAN over
-// scales of the per-scale nn.MSELoss; total = lsgan_first + w_class * class + lsgan_rest; d_o_s / dz_s = d total / d (.).
+// (the translated half of a real | fake batch) with t_rest.  vals = {gan_first, class, gan_rest, total}, each the MEAN over
+// scales of the per-scale criterion (GK: nn.MSELoss = LSGAN / nn.BCEWithLogitsLoss on the maps; CK: nn.MSELoss / nn.BCELoss on
+// softmax(z)); total = gan_first + w_class * class + gan_rest; d_o_s / dz_s = d total / d (.).
 struct DLossParams {
   const float* o[4];
   const float* z[4];
@@ -73,19 +143,32 @@ struct DLossParams {
   float t_first, t_rest, w_class;
 };
 
+template <int GK, int CK>
 __global__ __launch_bounds__(256) void d_losses_kernel(DLossParams p) {
   __shared__ float red[16];
   const float ws = 1.f / (float)p.n_scales;
   float first = 0.f, rest = 0.f, cls = 0.f;
   for (int s = 0; s < p.n_scales; ++s) {
     const long long n1 = (long long)p.rows_first * p.per[s], n2 = (long long)(p.rows - p.rows_first) * p.per[s];
-    const float g1 = n1 > 0 ? 2.f * ws / (float)n1 : 0.f, g2 = n2 > 0 ? 2.f * ws / (float)n2 : 0.f;
+    float g1, g2;
+    if constexpr (GK == CRIT_MSE) {
+      g1 = n1 > 0 ? 2.f * ws / (float)n1 : 0.f; g2 = n2 > 0 ? 2.f * ws / (float)n2 : 0.f;
+    } else {
+      g1 = n1 > 0 ? ws / (float)n1 : 0.f; g2 = n2 > 0 ? ws / (float)n2 : 0.f;
+    }
     float s1 = 0.f, s2 = 0.f;
     for (long long i = threadIdx.x; i < n1 + n2; i += blockDim.x) {
       const bool f = i < n1;
-      const float d = p.o[s][i] - (f ? p.t_first : p.t_rest);
-      if (f) s1 += d * d; else s2 += d * d;
-      p.d_o[s][i] = (f ? g1 : g2) * d;
+      if constexpr (GK == CRIT_MSE) {
+        const float d = p.o[s][i] - (f ? p.t_first : p.t_rest);
+        if (f) s1 += d * d; else s2 += d * d;
+        p.d_o[s][i] = (f ? g1 : g2) * d;
+      } else {
+        float d;
+        const float v = bce_logit(p.o[s][i], f ? p.t_first : p.t_rest, d);
+        if (f) s1 += v; else s2 += v;
+        p.d_o[s][i] = (f ? g1 : g2) * d;
+      }
     }
     s1 = block_sum(s1, red);
     s2 = block_sum(s2, red);
@@ -93,7 +176,7 @@ __global__ __launch_bounds__(256) void d_losses_kernel(DLossParams p) {
     if (n2 > 0) rest += ws * s2 / (float)n2;
     if (p.z[s]) {
       const int nc = p.nc;
-      const float gs = 2.f * ws * p.w_class / (float)(p.rows_first * nc);
+      const float gs = CK == CRIT_MSE ? 2.f * ws * p.w_class / (float)(p.rows_first * nc) : ws * p.w_class / (float)(p.rows_first * nc);
       float sc = 0.f;
       for (int b = threadIdx.x; b < p.rows; b += blockDim.x) {
         if (b >= p.rows_first) {
@@ -101,6 +184,11 @@ __global__ __launch_bounds__(256) void d_losses_kernel(DLossParams p) {
           continue;
         }
         float qq[16], dq[16];
+        if constexpr (CK == CRIT_BCE) {
+          for (int j = 0; j < nc; ++j) dq[j] = p.z[s][b * nc + j];
+          sc += softmax_bce_row(dq, nc, (int)p.label[b], gs, qq, p.dz[s] + b * nc);
+          continue;
+        }
         float mx = -INFINITY;
         for (int j = 0; j < nc; ++j) mx = fmaxf(mx, p.z[s][b * nc + j]);
         float den = 0.f;
@@ -188,17 +276,25 @@ __global__ void l1_final_kernel(const float* part, int nparts, float scale, floa
   if (threadIdx.x == 0) loss[0] = s * scale;
 }
 
-// mean((a-b)^2) * weight between two tensors (generic nn.MSELoss(a, b)); single block (small inputs)
-__global__ __launch_bounds__(256) void mse_pair_kernel(const float* a, const float* b, long long n, float weight,
-                                                       float* loss, float* da, float* db) {
+// mean((a-b)^2) * weight between two tensors (generic nn.MSELoss(a, b)), or nn.BCELoss(a, b) * weight of probabilities a
+// against targets b (no gradient w.r.t. the targets: db stays null); single block (small inputs)
+template <int KIND>
+__global__ __launch_bounds__(256) void crit_pair_kernel(const float* a, const float* b, long long n, float weight,
+                                                        float* loss, float* da, float* db) {
   __shared__ float red[16];
   float s = 0.f;
-  const float gscale = 2.f * weight / (float)n;
+  const float gscale = KIND == CRIT_MSE ? 2.f * weight / (float)n : weight / (float)n;
   for (long long i = threadIdx.x; i < n; i += blockDim.x) {
-    const float d = a[i] - b[i];
-    s += d * d;
-    if (da) da[i] = gscale * d;
-    if (db) db[i] = -gscale * d;
+    if constexpr (KIND == CRIT_MSE) {
+      const float d = a[i] - b[i];
+      s += d * d;
+      if (da) da[i] = gscale * d;
+      if (db) db[i] = -gscale * d;
+    } else {
+      const float q = a[i], y = b[i];
+      s += bce_prob(q, log1pf(-q), y);
+      if (da) da[i] = gscale * (q - y) / fmaxf((1.f - q) * q, 1e-12f);
+    }
   }
   s = block_sum(s, red);
   if (threadIdx.x == 0) loss[0] = weight * s / (float)n;
@@ -408,15 +504,35 @@ using namespace srgan;
 
 extern "C" int srgan_mse_const(const float* o, long long n, float target, float weight, float* loss, float* d_o, void* stream) {
   SRGAN_REQUIRE(o && loss && n > 0, "mse_const: bad argument");
-  hipLaunchKernelGGL(mse_const_kernel, dim3(1), dim3(256), 0, as_stream(stream), o, n, target, weight, loss, d_o);
-  return check_launch("mse_const_kernel");
+  return srgan_crit_const(o, n, target, weight, SRGAN_CRIT_MSE, loss, d_o, stream);
+}
+
+extern "C" int srgan_crit_const(const float* o, long long n, float target, float weight, int kind, float* loss, float* d_o,
+                                void* stream) {
+  SRGAN_REQUIRE(o && loss && n > 0, "crit_const: bad argument");
+  SRGAN_REQUIRE(kind == SRGAN_CRIT_MSE || kind == SRGAN_CRIT_BCE, "crit_const: kind is 0 (MSE) or 1 (BCE)");
+  if (kind == SRGAN_CRIT_MSE)
+    hipLaunchKernelGGL(crit_const_kernel<CRIT_MSE>, dim3(1), dim3(256), 0, as_stream(stream), o, n, target, weight, loss, d_o);
+  else
+    hipLaunchKernelGGL(crit_const_kernel<CRIT_BCE>, dim3(1), dim3(256), 0, as_stream(stream), o, n, target, weight, loss, d_o);
+  return check_launch("crit_const_kernel");
 }
 
 extern "C" int srgan_softmax_mse(const float* z, const long long* label, int B, int n_class, float weight, float* q,
                                  float* loss, float* dz, void* stream) {
   SRGAN_REQUIRE(z && label && loss && B > 0 && n_class > 0 && n_class <= 16, "softmax_mse: bad argument (n_class<=16)");
-  hipLaunchKernelGGL(softmax_mse_kernel, dim3(1), dim3(256), 0, as_stream(stream), z, label, B, n_class, weight, q, loss, dz);
-  return check_launch("softmax_mse_kernel");
+  return srgan_softmax_crit(z, label, B, n_class, weight, SRGAN_CRIT_MSE, q, loss, dz, stream);
+}
+
+extern "C" int srgan_softmax_crit(const float* z, const long long* label, int B, int n_class, float weight, int kind, float* q,
+                                  float* loss, float* dz, void* stream) {
+  SRGAN_REQUIRE(z && label && loss && B > 0 && n_class > 0 && n_class <= 16, "softmax_crit: bad argument (n_class<=16)");
+  SRGAN_REQUIRE(kind == SRGAN_CRIT_MSE || kind == SRGAN_CRIT_BCE, "softmax_crit: kind is 0 (MSE) or 1 (BCE)");
+  if (kind == SRGAN_CRIT_MSE)
+    hipLaunchKernelGGL(softmax_crit_kernel<CRIT_MSE>, dim3(1), dim3(256), 0, as_stream(stream), z, label, B, n_class, weight, q, loss, dz);
+  else
+    hipLaunchKernelGGL(softmax_crit_kernel<CRIT_BCE>, dim3(1), dim3(256), 0, as_stream(stream), z, label, B, n_class, weight, q, loss, dz);
+  return check_launch("softmax_crit_kernel");
 }
 
 extern "C" size_t srgan_l1_workspace(long long n) {
@@ -451,14 +567,35 @@ extern "C" int srgan_latent_losses(const float* mu, int B, int d, float n_batch,
 extern "C" int srgan_mse_pair(const float* a, const float* b, long long n, float weight, float* loss, float* da, float* db,
                               void* stream) {
   SRGAN_REQUIRE(a && b && loss && n > 0, "mse_pair: bad argument");
-  hipLaunchKernelGGL(mse_pair_kernel, dim3(1), dim3(256), 0, as_stream(stream), a, b, n, weight, loss, da, db);
-  return check_launch("mse_pair_kernel");
+  return srgan_crit_pair(a, b, n, weight, SRGAN_CRIT_MSE, loss, da, db, stream);
+}
+
+extern "C" int srgan_crit_pair(const float* a, const float* b, long long n, float weight, int kind, float* loss, float* da,
+                               float* db, void* stream) {
+  SRGAN_REQUIRE(a && b && loss && n > 0, "crit_pair: bad argument");
+  SRGAN_REQUIRE(kind == SRGAN_CRIT_MSE || kind == SRGAN_CRIT_BCE, "crit_pair: kind is 0 (MSE) or 1 (BCE)");
+  SRGAN_REQUIRE(kind == SRGAN_CRIT_MSE || !db, "crit_pair: nn.BCELoss has no gradient w.r.t. its targets (db must be NULL)");
+  if (kind == SRGAN_CRIT_MSE)
+    hipLaunchKernelGGL(crit_pair_kernel<CRIT_MSE>, dim3(1), dim3(256), 0, as_stream(stream), a, b, n, weight, loss, da, db);
+  else
+    hipLaunchKernelGGL(crit_pair_kernel<CRIT_BCE>, dim3(1), dim3(256), 0, as_stream(stream), a, b, n, weight, loss, da, db);
+  return check_launch("crit_pair_kernel");
 }
 
 extern "C" int srgan_d_losses(const float* const* o, const long long* per_row, const float* const* z, int n_scales, int rows,
                               int rows_first, int n_class, const long long* label, float t_first, float t_rest, float w_class,
                               float* vals, float* const* d_o, float* const* dz, void* stream) {
+  return srgan_d_losses_crit(o, per_row, z, n_scales, rows, rows_first, n_class, label, t_first, t_rest, w_class, SRGAN_CRIT_MSE,
+                             SRGAN_CRIT_MSE, vals, d_o, dz, stream);
+}
+
+extern "C" int srgan_d_losses_crit(const float* const* o, const long long* per_row, const float* const* z, int n_scales, int rows,
+                                   int rows_first, int n_class, const long long* label, float t_first, float t_rest,
+                                   float w_class, int gan_kind, int class_kind, float* vals, float* const* d_o, float* const* dz,
+                                   void* stream) {
   SRGAN_REQUIRE(o && per_row && d_o && vals && n_scales >= 1 && n_scales <= 4, "d_losses: 1..4 scales");
+  SRGAN_REQUIRE((gan_kind == SRGAN_CRIT_MSE || gan_kind == SRGAN_CRIT_BCE) && (class_kind == SRGAN_CRIT_MSE || class_kind == SRGAN_CRIT_BCE),
+                "d_losses: gan_kind / class_kind are 0 (MSE) or 1 (BCE)");
   SRGAN_REQUIRE(rows > 0 && rows_first >= 0 && rows_first <= rows, "d_losses: bad row split");
   DLossParams p{};
   p.n_scales = n_scales; p.rows = rows; p.rows_first = rows_first; p.nc = n_class;
@@ -470,7 +607,15 @@ extern "C" int srgan_d_losses(const float* const* o, const long long* per_row, c
     p.dz[s] = dz ? dz[s] : nullptr;
     SRGAN_REQUIRE(!p.z[s] || (p.dz[s] && label && rows_first > 0 && n_class > 0 && n_class <= 16), "d_losses: class head needs dz, labels, <= 16 classes");
   }
-  hipLaunchKernelGGL(d_losses_kernel, dim3(1), dim3(256), 0, as_stream(stream), p);
+  hipStream_t st = as_stream(stream);
+  if (gan_kind == SRGAN_CRIT_MSE && class_kind == SRGAN_CRIT_MSE)
+    hipLaunchKernelGGL((d_losses_kernel<CRIT_MSE, CRIT_MSE>), dim3(1), dim3(256), 0, st, p);
+  else if (gan_kind == SRGAN_CRIT_MSE)
+    hipLaunchKernelGGL((d_losses_kernel<CRIT_MSE, CRIT_BCE>), dim3(1), dim3(256), 0, st, p);
+  else if (class_kind == SRGAN_CRIT_MSE)
+    hipLaunchKernelGGL((d_losses_kernel<CRIT_BCE, CRIT_MSE>), dim3(1), dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL((d_losses_kernel<CRIT_BCE, CRIT_BCE>), dim3(1), dim3(256), 0, st, p);
   return check_launch("d_losses_kernel");
 }
 

@@ -10,7 +10,7 @@ import torch.nn as nn
 
 from . import ops
 
-__all__ = ["CrossEntropyLoss", "get_loss_D", "get_domainloss_D", "corrcoef", "corrcoef_loss", "GaussianHistogram",
+__all__ = ["CrossEntropyLoss", "criterion_kind", "get_loss_D", "get_domainloss_D", "corrcoef", "corrcoef_loss", "GaussianHistogram",
            "histogram_imitation", "class_encode", "get_target", "weights_init", "load_classifier"]
 
 
@@ -23,29 +23,66 @@ class CrossEntropyLoss(nn.Module):
         return ops.softmax_xent(input, target, 1.0)
 
 
-def _require_mse(criterion, who):
-    if not isinstance(criterion, nn.MSELoss) or getattr(criterion, "reduction", "mean") != "mean":
-        raise NotImplementedError(f"{who}: only nn.MSELoss() (mean reduction) has a HIP kernel -- the criterion "
-                                  "every reference notebook passes (05-train cell 13)")
+def criterion_kind(criterion, slot, who="criterion"):
+    """The fused-kernel kind (``ops.CRIT_MSE`` / ``ops.CRIT_BCE``) of a criterion module in one of the trainer's two slots:
+
+      slot "gan"    ``criterion``        the discriminator's raw maps against a constant   nn.MSELoss | nn.BCEWithLogitsLoss
+      slot "class"  ``criterion_class``  softmax probabilities against the one-hot label   nn.MSELoss | nn.BCELoss
+
+    each with mean reduction and without ``weight`` / ``pos_weight``.  Everything else has no HIP kernel and is refused here --
+    the one place that owns the refusals (the reference applies whatever ``torch.nn.modules.loss`` it is given,
+    util.py:457-468)."""
+    accepted = ("nn.MSELoss() or nn.BCEWithLogitsLoss()" if slot == "gan" else "nn.MSELoss() or nn.BCELoss()")
+    why = None
+    if isinstance(criterion, nn.MSELoss):
+        kind = ops.CRIT_MSE
+    elif slot == "gan" and isinstance(criterion, nn.BCEWithLogitsLoss):
+        kind = ops.CRIT_BCE
+        if criterion.pos_weight is not None:
+            why = "pos_weight is not supported"
+    elif slot == "class" and isinstance(criterion, nn.BCELoss):
+        kind = ops.CRIT_BCE
+    elif isinstance(criterion, nn.BCELoss):
+        why = "nn.BCELoss expects probabilities, the discriminator's maps are raw logits"
+    elif isinstance(criterion, nn.BCEWithLogitsLoss):
+        why = "nn.BCEWithLogitsLoss expects logits, the class head's outputs are softmax probabilities"
+    else:
+        why = f"{type(criterion).__name__} has no HIP kernel"
+    if why is None and getattr(criterion, "weight", None) is not None:
+        why = "a per-element weight is not supported"
+    if why is None and getattr(criterion, "reduction", "mean") != "mean":
+        why = f"reduction={criterion.reduction!r} is not supported"
+    if why is not None:
+        raise NotImplementedError(f"{who}: only {accepted} (mean reduction, no weights) has a HIP kernel in this slot -- {why}")
+    return kind
+
+
+def has_fused_kind(criterion, slot):
+    try:
+        criterion_kind(criterion, slot)
+    except NotImplementedError:
+        return False
+    return True
 
 
 def get_loss_D(outputs, target, criterion, device="cuda"):
     """mean over the scales of criterion(output, full_like(output, target))   (util.py:457-462)."""
-    _require_mse(criterion, "get_loss_D")
+    kind = criterion_kind(criterion, "gan", "get_loss_D")
     loss = 0.0
     w = 1.0 / len(outputs)
     for output in outputs:
-        loss = loss + ops.mse_const(output, float(target), w)
+        loss = loss + (ops.mse_const(output, float(target), w) if kind == ops.CRIT_MSE
+                       else ops.crit_const(output, float(target), w, kind))
     return loss
 
 
 def get_domainloss_D(outputs_class, true_label, criterion_class):
     """mean over the scales of criterion_class(class probabilities, one-hot label)   (util.py:464-468)."""
-    _require_mse(criterion_class, "get_domainloss_D")
+    kind = criterion_kind(criterion_class, "class", "get_domainloss_D")
     loss = 0.0
     w = 1.0 / len(outputs_class)
     for q in outputs_class:
-        loss = loss + ops.mse_pair(q, true_label, w)
+        loss = loss + (ops.mse_pair(q, true_label, w) if kind == ops.CRIT_MSE else ops.crit_pair(q, true_label, w, kind))
     return loss
 
 

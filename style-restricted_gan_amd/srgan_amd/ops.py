@@ -2132,6 +2132,69 @@ def softmax_mse(z, label, weight=1.0):
     return _SoftmaxMseFn.apply(z, label, weight)
 
 
+# Criterion kinds of the fused loss kernels (SRGAN_CRIT_* of srgan_hip.h): nn.MSELoss, or the slot's binary cross-entropy
+# (nn.BCEWithLogitsLoss on the discriminator's raw maps, nn.BCELoss on class probabilities).  losses.criterion_kind maps modules.
+CRIT_MSE, CRIT_BCE = 0, 1
+
+
+def _crit_kind(kind, who):
+    if kind not in (CRIT_MSE, CRIT_BCE):
+        raise ValueError(f"{who}: kind is ops.CRIT_MSE (0) or ops.CRIT_BCE (1), got {kind!r}")
+    return int(kind)
+
+
+class _CritConstFn(Function):
+    @staticmethod
+    def forward(ctx, o, target, weight, kind):
+        _require_gpu(o, "crit_const")
+        o = o if (o.is_contiguous() or is_nhwc_dense(o)) else o.contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=o.device)
+        d_o = torch.empty_like(o)
+        _lib.check(_lib.load().srgan_crit_const(_ptr(o), o.numel(), float(target), float(weight), kind, _ptr(loss), _ptr(d_o),
+                                                _stream()), "crit_const")
+        ctx.save_for_backward(d_o)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (d_o,) = ctx.saved_tensors
+        return d_o * g, None, None, None
+
+
+def crit_const(o, target, weight=1.0, kind=CRIT_MSE):
+    """weight * criterion(o, full_like(o, target)): mean((o - target)^2) (CRIT_MSE, the arithmetic of ``mse_const``) or
+    nn.BCEWithLogitsLoss on the raw logits o (CRIT_BCE; any real target)."""
+    return _CritConstFn.apply(o, target, weight, _crit_kind(kind, "crit_const"))
+
+
+class _SoftmaxCritFn(Function):
+    @staticmethod
+    def forward(ctx, z, label, weight, kind):
+        _require_gpu(z, "softmax_crit")
+        z = _dense2d(z)
+        b, nc = z.shape
+        label = label.to(device=z.device, dtype=torch.int64).contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=z.device)
+        q = torch.empty_like(z)
+        dz = torch.empty_like(z)
+        _lib.check(_lib.load().srgan_softmax_crit(_ptr(z), _ptr(label), b, nc, float(weight), kind, _ptr(q), _ptr(loss),
+                                                  _ptr(dz), _stream()), "softmax_crit")
+        ctx.save_for_backward(dz)
+        ctx.mark_non_differentiable(q)
+        return loss, q
+
+    @staticmethod
+    def backward(ctx, g, _gq):
+        (dz,) = ctx.saved_tensors
+        return dz * g, None, None, None
+
+
+def softmax_crit(z, label, weight=1.0, kind=CRIT_MSE):
+    """-> (weight * criterion(softmax(z), onehot(label)), softmax(z)): nn.MSELoss (CRIT_MSE, the arithmetic of ``softmax_mse``)
+    or nn.BCELoss with its -100 log clamp and 1e-12 gradient floor (CRIT_BCE)."""
+    return _SoftmaxCritFn.apply(z, label, weight, _crit_kind(kind, "softmax_crit"))
+
+
 class _SoftmaxXentFn(Function):
     @staticmethod
     def forward(ctx, z, label, weight):
@@ -2240,9 +2303,36 @@ def mse_pair(a, b, weight=1.0):
     return _MsePairFn.apply(a, b, weight)
 
 
+class _CritPairFn(Function):
+    @staticmethod
+    def forward(ctx, a, b, weight, kind):
+        _require_gpu(a, "crit_pair")
+        if kind == CRIT_BCE and ctx.needs_input_grad[1]:
+            raise _lib.SrganHipError("crit_pair: nn.BCELoss has no gradient w.r.t. its targets on the HIP path")
+        a, b = a.contiguous(), b.contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=a.device)
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.load().srgan_crit_pair(_ptr(a), _ptr(b), a.numel(), float(weight), kind, _ptr(loss), _ptr(da), _ptr(db),
+                                               _stream()), "crit_pair")
+        ctx.save_for_backward(da, db)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        da, db = ctx.saved_tensors
+        return (da * g if da is not None else None, db * g if db is not None else None, None, None)
+
+
+def crit_pair(a, b, weight=1.0, kind=CRIT_MSE):
+    """weight * criterion(a, b) for two small tensors of equal shape: nn.MSELoss (CRIT_MSE, the arithmetic of ``mse_pair``) or
+    nn.BCELoss of the probabilities a against the targets b (CRIT_BCE; the targets take no gradient)."""
+    return _CritPairFn.apply(a, b, weight, _crit_kind(kind, "crit_pair"))
+
+
 class _DLossesFn(Function):
     @staticmethod
-    def forward(ctx, label, rows_first, t_first, t_rest, w_class, n_scales, *tensors):
+    def forward(ctx, label, rows_first, t_first, t_rest, w_class, n_scales, gan_kind, class_kind, *tensors):
         outs, logits = tensors[:n_scales], tensors[n_scales:]
         lib = _lib.load()
         dev = outs[0].device
@@ -2262,10 +2352,10 @@ class _DLossesFn(Function):
         per = (ctypes.c_longlong * S)(*[t.numel() // rows for t in o])
         if label is not None:
             label = label.to(device=dev, dtype=torch.int64).contiguous()
-        _lib.check(lib.srgan_d_losses(arr(*[t.data_ptr() for t in o]), per, arr(*[t.data_ptr() for t in z]) if z else None, S, rows,
-                                      int(rows_first), int(nc), _ptr(label), float(t_first), float(t_rest), float(w_class),
-                                      _ptr(vals), arr(*[t.data_ptr() for t in d_o]), arr(*[t.data_ptr() for t in dz]) if z else None,
-                                      _stream()), "d_losses")
+        _lib.check(lib.srgan_d_losses_crit(arr(*[t.data_ptr() for t in o]), per, arr(*[t.data_ptr() for t in z]) if z else None, S,
+                                           rows, int(rows_first), int(nc), _ptr(label), float(t_first), float(t_rest),
+                                           float(w_class), gan_kind, class_kind, _ptr(vals), arr(*[t.data_ptr() for t in d_o]),
+                                           arr(*[t.data_ptr() for t in dz]) if z else None, _stream()), "d_losses")
         ctx.save_for_backward(*d_o, *dz)
         total, parts = vals[3], vals[:3]
         ctx.mark_non_differentiable(parts)
@@ -2274,15 +2364,17 @@ class _DLossesFn(Function):
     @staticmethod
     def backward(ctx, g, _gp):
         grads = torch._foreach_mul(list(ctx.saved_tensors), g)      # one multi-tensor launch
-        return (None,) * 6 + tuple(grads)
+        return (None,) * 8 + tuple(grads)
 
 
-def d_losses(outs, logits, label, rows_first, t_first, t_rest, w_class):
-    """Every loss of one discriminator evaluation in one launch -> (total, tensor([lsgan_first, class, lsgan_rest])):
-    the first ``rows_first`` rows against ``t_first`` (+ softmax / class-MSE against ``label``), the rest against ``t_rest``;
-    total = lsgan_first + w_class * class + lsgan_rest, each term the mean over the scales (util.py:457-468)."""
+def d_losses(outs, logits, label, rows_first, t_first, t_rest, w_class, gan_kind=CRIT_MSE, class_kind=CRIT_MSE):
+    """Every loss of one discriminator evaluation in one launch -> (total, tensor([gan_first, class, gan_rest])):
+    the first ``rows_first`` rows against ``t_first`` (+ softmax / class loss against ``label``), the rest against ``t_rest``;
+    total = gan_first + w_class * class + gan_rest, each term the mean over the scales (util.py:457-468).  ``gan_kind``:
+    nn.MSELoss (LSGAN, the default) or nn.BCEWithLogitsLoss on the maps; ``class_kind``: nn.MSELoss or nn.BCELoss on softmax(z)."""
     logits = list(logits) if logits else []
-    return _DLossesFn.apply(label, rows_first, t_first, t_rest, w_class, len(outs), *outs, *logits)
+    return _DLossesFn.apply(label, rows_first, t_first, t_rest, w_class, len(outs), _crit_kind(gan_kind, "d_losses"),
+                            _crit_kind(class_kind, "d_losses"), *outs, *logits)
 
 
 class _LincombFn(Function):

@@ -27,7 +27,7 @@ import torch.nn as nn
 import torch.optim as optim
 
 from . import _lib, dp, ema, ops
-from .losses import class_encode, get_domainloss_D, get_loss_D, histogram_imitation
+from .losses import class_encode, criterion_kind, get_domainloss_D, get_loss_D, has_fused_kind, histogram_imitation
 from .model import SingleGenerator, _cpu_normal_like, _is_batch_stat, _is_synced, batch_stats_synced, host_to_device, per_sample
 from .optim import Adam
 
@@ -50,7 +50,8 @@ def _frozen(params):
 class SRGAN_training():
     """
     net            : [G, D, E] nn.Modules          opt : [optG, optD, optE] (None -> fused HIP Adam)
-    criterion      : [criterion, criterion_class]   (nn.MSELoss in every reference notebook)
+    criterion      : [criterion, criterion_class]   (nn.MSELoss in every reference notebook; nn.BCEWithLogitsLoss / nn.BCELoss
+                     are the other kinds with fused kernels: losses.criterion_kind)
     lbd            : dict of loss weights: class, cycle, idt, reg, idt_reg, KL, batch_KL, corr_enc, hist
     unrolled_k     : number of D updates per G/E update
     device         : "cuda" / torch.device           ref_label : np.array (class_num, dim), usually one-hot
@@ -196,29 +197,37 @@ class SRGAN_training():
         return list(self.E(image))
 
     def _fused_paths(self):
-        """The batched / fused execution needs this package's own modules (feature / logit entry points)."""
+        """The batched / fused execution needs this package's own modules (feature / logit entry points) and a fused kernel
+        kind for BOTH criteria: a criterion without one takes the generic path, whose loss helpers refuse it."""
         return (hasattr(dp.unwrap(self.D), "forward_logits") and self._ref_is_onehot
-                and hasattr(dp.unwrap(self.E), "features") and self._class_is_mse())
+                and hasattr(dp.unwrap(self.E), "features") and has_fused_kind(self.criterion, "gan")
+                and has_fused_kind(self.criterion_class, "class"))
 
     def _class_is_mse(self):
-        """The fused class-loss kernel is softmax + MSE (nn.MSELoss in every reference notebook, 05-train cell 13); any other
-        criterion_class takes the generic path through the criterion itself."""
+        """criterion_class is nn.MSELoss() with mean reduction (05-train cell 13): the softmax + MSE instantiation of the fused
+        class-loss kernels."""
         c = self.criterion_class
         return isinstance(c, nn.MSELoss) and getattr(c, "reduction", "mean") == "mean"
 
+    def _kinds(self):
+        """(gan_kind, class_kind) of the two criteria for the fused loss kernels (raises for a criterion without one)."""
+        return (criterion_kind(self.criterion, "gan", "SRGAN_training"),
+                criterion_kind(self.criterion_class, "class", "SRGAN_training"))
+
     def _d_losses(self, image, gan_target, class_which, want_class):
-        """LSGAN (+ class MSE) of D(image) through the fused head/loss kernels."""
+        """GAN loss (+ class loss) of D(image) through the fused head/loss kernels."""
         D = dp.unwrap(self.D)
-        if hasattr(D, "forward_logits") and self._ref_is_onehot and self._class_is_mse():
+        if hasattr(D, "forward_logits") and self._ref_is_onehot and has_fused_kind(self.criterion_class, "class"):
             outs, logits = D.forward_logits(image)
             gan = get_loss_D(outs, gan_target, self.criterion, self.device)
             cls = None
             if want_class:
                 lab = self._label_dev(class_which)
                 w = 1.0 / len(logits)
+                ck = criterion_kind(self.criterion_class, "class", "SRGAN_training")
                 cls = 0.0
                 for z in logits:
-                    cls = cls + ops.softmax_mse(z, lab, w)[0]
+                    cls = cls + (ops.softmax_mse(z, lab, w)[0] if ck == ops.CRIT_MSE else ops.softmax_crit(z, lab, w, ck)[0])
             return gan, cls
         outs, probs = self.D(image)
         gan = get_loss_D(outs, gan_target, self.criterion, self.device)
@@ -265,8 +274,8 @@ class SRGAN_training():
             # real and fake halves through D as ONE batch (per-sample network: exact; 2x the rows per GEMM launch)
             B = self.source_image.shape[0]
             outs, logits = dp.unwrap(self.D).forward_logits(ops.cat_batch([self.source_image, self.target_image.detach()]))
-            # LSGAN(real, 1) + class MSE * lbd + LSGAN(fake, 0) over both scales, values and gradients: one launch
-            errD, parts = ops.d_losses(outs, logits, self._label_dev("source"), B, 1., 0., self.lbd["class"])
+            # criterion(real, 1) + class loss * lbd + criterion(fake, 0) over both scales, values and gradients: one launch
+            errD, parts = ops.d_losses(outs, logits, self._label_dev("source"), B, 1., 0., self.lbd["class"], *self._kinds())
             errD_real, errD_class, errD_fake = parts[0], parts[1], parts[2]
         else:
             errD_real, errD_class = self._d_losses(self.source_image, 1., "source", True)
@@ -341,7 +350,8 @@ class SRGAN_training():
             with _frozen(list(self.D.parameters())):       # D's weight grads would be discarded
                 if fused:
                     outs, logits = dp.unwrap(self.D).forward_logits(t_img)
-                    d_total, parts = ops.d_losses(outs, logits, self._label_dev("target"), self.target_image.shape[0], 1., 0., L["class"])
+                    d_total, parts = ops.d_losses(outs, logits, self._label_dev("target"), self.target_image.shape[0], 1., 0., L["class"],
+                                                  *self._kinds())
                     errG_dis, errG_class = parts[0], parts[1]
                     g_terms.append((d_total, 1.0))
                 else:
@@ -781,7 +791,8 @@ class _StepGraph:
     def unsupported_reason(self):
         sg = self.sg
         if not sg._fused_paths():
-            return "needs this package's own G / D / E modules, a one-hot ref_label and nn.MSELoss criteria"
+            return ("needs this package's own G / D / E modules, a one-hot ref_label and criteria with a fused kernel (nn.MSELoss, "
+                    "nn.BCEWithLogitsLoss / nn.BCELoss)")
         for name in ("optG", "optD", "optE"):
             if not isinstance(getattr(sg, name), Adam):
                 return f"{name} is not srgan_amd.optim.Adam (call opt_sche_initialization(), or pass that class)"
@@ -814,6 +825,8 @@ class _StepGraph:
         sg = self.sg
         fp = [sg.k, sg.n_batch, sg.ndim, sg.encoded_feature, tuple(sorted((k, float(v)) for k, v in sg.lbd.items())),
               type(sg.criterion), type(sg.criterion_class), np.asarray(sg.ref_label, dtype=np.float64).tobytes()]
+        # the kernel kinds follow from the types, but a criterion edited in place (reduction, weight) can lose its kind
+        fp.append((has_fused_kind(sg.criterion, "gan"), has_fused_kind(sg.criterion_class, "class")))
         for opt in (sg.optG, sg.optD, sg.optE):
             fp.append(id(opt))
             for g in getattr(opt, "param_groups", ()):
