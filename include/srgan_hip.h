@@ -514,6 +514,31 @@ int srgan_grad_guard_reduce(const void* table, int n_records, long long total_ch
 int srgan_adam_multi_dev_guard(const void* table, int n_tensors, long long max_numel, void* adam_state, void* guard_state,
                                void* stream);
 
+/* Spectral normalisation of convolution weights (Miyato et al., 2018; torch.nn.utils.spectral_norm with one forward per
+ * optimiser step) for the discriminator.  Extension, no counterpart in the reference; fp32 in both compute modes.  A layer is
+ * W[O][I][kh][kw] viewed as Wm[O][K], K = I * kh * kw.  One record of srgan_spectral_record_bytes() = sixteen 64-bit words per
+ * layer: {W, W_sn, u, v, sigma, O, K, slab0, col0, elem0, ws_part, ws_t, ws_nsq, ws_y, ws_dot, 0} -- the caller fills the five
+ * device pointers (fp32, 4-byte aligned; 16-byte aligned ones take the 16-byte loads) and O, K (O * K < 2^31) in a HOST copy,
+ * srgan_spectral_plan checks them, fills the other words (first work item of the layer in each of the three flat work lists,
+ * float offsets into the workspace) and writes the host-side plan (srgan_spectral_plan_bytes(): {int n_records, pad; long long
+ * slab_items, col_items, elem_items, ws_floats}); the caller then uploads the table once.  srgan_spectral_workspace(plan): bytes
+ * of the workspace (16-byte aligned) both operations take.
+ * srgan_spectral_refresh, iterate = 1: n_power_iterations times {v <- Wm^T u / max(|Wm^T u|, eps); u <- Wm v / max(|Wm v|, eps)},
+ * then sigma = u^T Wm v and W_sn = W / sigma, for all records: 4 launches per iteration + 1.  iterate = 0: sigma and W_sn from the
+ * stored u, v (3 launches).  srgan_spectral_project: grads = n_records device pointers (0: the layer has no gradient and is left
+ * alone), each the gradient G of W_sn, replaced IN PLACE by (G - <G, W_sn> u v^T) / sigma, the gradient of W with u, v, sigma held
+ * constant: 2 launches.  The launch counts do not depend on the number of layers; no atomics and no workgroup waits on another,
+ * every sum has a fixed order (csrc/spectral.hip), so results do not depend on the grid.  -1 with srgan_last_error() before any
+ * launch: NULL table / plan / workspace, a plan of zero records, a workspace too small or misaligned, eps not > 0,
+ * n_power_iterations < 1. */
+size_t srgan_spectral_record_bytes(void);
+size_t srgan_spectral_plan_bytes(void);
+int srgan_spectral_plan(void* host_table, int n_records, void* plan);
+size_t srgan_spectral_workspace(const void* plan);
+int srgan_spectral_refresh(const void* table, const void* plan, int iterate, int n_power_iterations, float eps, void* ws,
+                           size_t ws_bytes, void* stream);
+int srgan_spectral_project(const void* table, const void* plan, const void* grads, void* ws, size_t ws_bytes, void* stream);
+
 /* Small host -> device upload (pointer tables: <= 1 MiB, multiple of 4 bytes) carried in kernel arguments: nothing to keep
  * alive on the host after the call returns, and a captured hipGraph stores the bytes in its node instead of re-reading a host
  * address at replay (no reference counterpart; plumbing of the multi-tensor ops above). */

@@ -185,6 +185,12 @@ SIGNATURES = {
     "srgan_grad_guard_workspace": (c_size_t, [c_longlong]),
     "srgan_grad_guard_reduce": (c_int, [P, c_int, c_longlong, P, c_size_t, P, P]),
     "srgan_adam_multi_dev_guard": (c_int, [P, c_int, c_longlong, P, P, P]),
+    "srgan_spectral_record_bytes": (c_size_t, []),
+    "srgan_spectral_plan_bytes": (c_size_t, []),
+    "srgan_spectral_plan": (c_int, [P, c_int, P]),
+    "srgan_spectral_workspace": (c_size_t, [P]),
+    "srgan_spectral_refresh": (c_int, [P, P, c_int, c_int, c_float, P, c_size_t, P]),
+    "srgan_spectral_project": (c_int, [P, P, P, P, c_size_t, P]),
     "srgan_upload_small": (c_int, [P, P, c_size_t, P]),
     "srgan_maxpool2_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "srgan_pairwise_dist": (c_int, [P, c_int, P, c_int, c_int, P, P]),

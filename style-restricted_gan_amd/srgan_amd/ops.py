@@ -2595,3 +2595,40 @@ def ema_multi_dev_(table_dev, n_records, total_chunks, state):
     dst += c * (src - dst) (kind 0) or dst <- src bit for bit (kind 1).  hipGraph-capturable; writes through raw pointers."""
     _lib.check(_lib.load().srgan_ema_multi_dev(_ptr(table_dev), int(n_records), int(total_chunks), _ptr(state), _stream()),
                "ema_multi_dev")
+
+
+# ---- spectral normalisation of conv weights (srgan_amd.spectral; extension, no counterpart in the reference) ----------------
+SPECTRAL_REC_WORDS = 16        # 64-bit words per record: {W, W_sn, u, v, sigma, O, K} + seven words srgan_spectral_plan fills
+
+
+def spectral_table(layers, device):
+    """``layers``: [(W ptr, W_sn ptr, u ptr, v ptr, sigma ptr, O, K)] -> (device table, host plan, workspace).  The library checks
+    the records and fills in the work lists' prefix sums and the workspace offsets; the table is uploaded once."""
+    lib = _lib.load()
+    if lib.srgan_spectral_record_bytes() != 8 * SPECTRAL_REC_WORDS:
+        raise _lib.SrganHipError("spectral_table: record layout mismatch")
+    rows = []
+    for rec in layers:
+        rows.extend(tuple(int(x) for x in rec) + (0,) * (SPECTRAL_REC_WORDS - len(rec)))
+    host = (ctypes.c_char * (8 * len(rows))).from_buffer_copy(struct.pack(f"{len(rows)}Q", *rows))
+    plan = (ctypes.c_char * lib.srgan_spectral_plan_bytes())()
+    _lib.check(lib.srgan_spectral_plan(ctypes.byref(host), len(layers), ctypes.byref(plan)), "spectral_plan")
+    nbytes = lib.srgan_spectral_workspace(ctypes.byref(plan))
+    if nbytes == 0:
+        _lib.check(-1, "spectral_workspace")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return upload_small(bytes(host), device), plan, ws
+
+
+def spectral_refresh_(table_dev, plan, ws, iterate=True, n_power_iterations=1, eps=1e-12):
+    """sigma and W_sn = W / sigma of every record, after ``n_power_iterations`` power iterations on (u, v) (``iterate``) or from
+    the stored (u, v): 4 n + 1 / 3 launches whatever the number of layers.  hipGraph-capturable; writes through raw pointers."""
+    _lib.check(_lib.load().srgan_spectral_refresh(_ptr(table_dev), ctypes.byref(plan), int(bool(iterate)), int(n_power_iterations),
+                                                  float(eps), _ptr(ws), ws.numel(), _stream()), "spectral_refresh")
+
+
+def spectral_project_(table_dev, plan, grads_dev, ws):
+    """G <- (G - <G, W_sn> u v^T) / sigma in place for the gradient pointers of ``grads_dev`` (one 64-bit word per record, 0 = no
+    gradient): 2 launches."""
+    _lib.check(_lib.load().srgan_spectral_project(_ptr(table_dev), ctypes.byref(plan), _ptr(grads_dev), _ptr(ws), ws.numel(),
+                                                  _stream()), "spectral_project")

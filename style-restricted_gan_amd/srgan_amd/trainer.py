@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.optim as optim
 
-from . import _lib, dp, ema, ops
+from . import _lib, dp, ema, ops, spectral
 from .losses import class_encode, criterion_kind, get_domainloss_D, get_loss_D, has_fused_kind, histogram_imitation
 from .model import SingleGenerator, _cpu_normal_like, _is_batch_stat, _is_synced, batch_stats_synced, host_to_device, per_sample
 from .optim import Adam
@@ -101,6 +101,7 @@ class SRGAN_training():
                 f"{dp.world_size()} ranks; nn.DataParallel gives per-replica statistics and rank-0 running buffers, which this "
                 "package does not build (one process, or norm_type='instance'). Statistics of the global batch are an opt-in: "
                 "mark both networks with dp.sync_batch_stats(net).")
+        self._sn()
 
     # ------------------------------------------------------------------------------------------
     def opt_sche_initialization(self, lr=[0.0001, 0.0001, 0.0001]):
@@ -162,8 +163,52 @@ class SRGAN_training():
 
     def _step(self, opt):
         """optimiser step + one launch that re-packs the cached conv operands of the weights it just changed"""
+        sn = self._sn() if opt is self.optD else None
+        if sn is None:
+            opt.step()
+            ops.refresh_packed(self._opt_params(opt))
+            return
+        # spectrally normalised D: the gradients of the normalised weights are mapped to the parameters first (the gradient guard
+        # then sees the projected ones); the power iteration follows the step -- also a skipped one, on the unchanged weights, so
+        # that a recorded launch sequence stays static -- and the operands re-packed are those of the normalised weights
+        sn.project()
         opt.step()
-        ops.refresh_packed(self._opt_params(opt))
+        sn.refresh(iterate=True)
+        ops.refresh_packed(sn.step_params(self._opt_params(opt)))
+
+    def _sn(self):
+        """The spectral-norm controller of a marked ``self.D`` (``spectral.spectral_norm(sg.D)``), or None; refuses the marks this
+        trainer does not serve."""
+        key = (spectral.marks_epoch(), id(self.G), id(self.D), id(self.E), dp.world_size())
+        hit = self.__dict__.get("_sn_cache")
+        if hit is None or hit[0] != key:
+            hit = self._sn_cache = (key, self._sn_lookup())
+        return hit[1]
+
+    def _sn_lookup(self):
+        for name in ("G", "E"):
+            if spectral.find(dp.unwrap(getattr(self, name))):
+                raise NotImplementedError(f"SRGAN_training: {name} is marked with spectral_norm; only the discriminator's step maps "
+                                          "the gradients and runs the power iteration (spectral.remove_spectral_norm(sg." + name + "))")
+        D = dp.unwrap(self.D)
+        marks = spectral.find(D)
+        if not marks:
+            return None
+        sn = spectral.controller(D)
+        if sn is None or len(marks) != 1:
+            raise NotImplementedError("SRGAN_training: a part of D is marked with spectral_norm; one table serves the step -- remove "
+                                      "the marks and apply spectral.spectral_norm(sg.D) to the whole discriminator")
+        if dp.world_size() > 1:
+            raise NotImplementedError(f"SRGAN_training: D is marked with spectral_norm and the process group has {dp.world_size()} "
+                                      "ranks; the normalised weights are not in the gradient reducer's buckets yet (run one "
+                                      "process, or spectral.remove_spectral_norm(sg.D))")
+        return sn
+
+    def _d_frozen(self):
+        """What phase 1's pass through D must not compute gradients for: D's parameters and, for a marked D, the normalised
+        weights the convolutions read."""
+        sn = self._sn()
+        return list(self.D.parameters()) + (sn.leaves if sn is not None else [])
 
     def _reducer(self, name, opt):
         red = self._reducers.get(name)
@@ -265,6 +310,9 @@ class SRGAN_training():
         all-reduce and the optimiser step to ``_finish_D()`` so that the caller can put more independent work in between."""
         self._finish_D()
         self.D.zero_grad()
+        sn = self._sn()
+        if sn is not None:
+            sn.zero_grad()                                 # the normalised weights are not parameters: D.zero_grad() misses them
         if _fake is None:
             self.target_image, self.c_rand = self.G_transformation("target", self.source_image, False)
         else:
@@ -347,7 +395,7 @@ class SRGAN_training():
             # loss terms as (device scalar, weight) lists: the optimised sums and the two reported sums are each ONE launch
             # (ops.lincomb) instead of one launch per python-level `+` / `*`
             g_terms, e_terms, rep_terms = [], [], []
-            with _frozen(list(self.D.parameters())):       # D's weight grads would be discarded
+            with _frozen(self._d_frozen()):                # D's weight grads would be discarded
                 if fused:
                     outs, logits = dp.unwrap(self.D).forward_logits(t_img)
                     d_total, parts = ops.d_losses(outs, logits, self._label_dev("target"), self.target_image.shape[0], 1., 0., L["class"],
@@ -571,6 +619,9 @@ class SRGAN_training():
         self.label = label
         self.loss_terms = {}
         g = self._graph
+        sn = self._sn()
+        if sn is not None:
+            sn._ensure()               # a state dict loaded since the last step: sigma and the normalised weights follow it
         if g is not None and g.accepts(source_image, label):
             return g.run(source_image, label)
         if g is not None:
@@ -847,6 +898,10 @@ class _StepGraph:
         # the gradient guards: their reduce launches, the guarded update and the records (enable / disable between steps); the
         # clipping threshold is device state
         fp.append(tuple(opt.grad_guard_fingerprint() if isinstance(opt, Adam) else None for opt in (sg.optG, sg.optD, sg.optE)))
+        # spectral normalisation of D: the projection and the refresh, their table, workspace and buffers (applied or removed
+        # between steps); u, v, sigma and the normalised weights are device state
+        sn = sg._sn() if hasattr(sg, "_sn") else None
+        fp.append(sn.fingerprint() if sn is not None else None)
         return tuple(fp)
 
     def _opt_steps(self):
@@ -1031,6 +1086,8 @@ class _StepGraph:
         self._keep = ops.graph_keepalive() + [t for opt in (sg.optG, sg.optD, sg.optE) for t in opt.graph_keepalive()]
         if sg._ema is not None:
             self._keep += sg._ema.graph_keepalive()
+        if sg._sn() is not None:
+            self._keep += sg._sn().graph_keepalive()
         self._baked = self._fingerprint()
 
     def _abandon(self, err, snap, keep_graph_mode=False):
@@ -1254,6 +1311,14 @@ class SingleGAN_training():
             self.hi = histogram_imitation(device)
         self.loss_terms = {}
         self.noise_fn = torch.randn
+        self._refuse_spectral()
+
+    def _refuse_spectral(self):
+        nets = [self.G, self.E] + (list(self.D) if isinstance(self.D, (list, tuple)) else [self.D])
+        if any(spectral.find(dp.unwrap(n)) for n in nets if isinstance(n, nn.Module)):
+            raise NotImplementedError("SingleGAN_training: a network is marked with spectral_norm; this trainer's optimiser steps "
+                                      "neither map the gradients nor run the power iteration (use SRGAN_training, or "
+                                      "spectral.remove_spectral_norm(net))")
 
     def opt_sche_initialization(self, lr=[0.0001, 0.0001, 0.0001]):
         lr_G, lr_D, lr_E = lr
@@ -1398,6 +1463,7 @@ class SingleGAN_training():
         return [errorG, errorD, errorE]
 
     def train(self, source_image, label):
+        self._refuse_spectral()
         self.source_image = ops.to_nhwc(source_image)
         self.label = label
         self.loss_terms = {}
