@@ -413,7 +413,9 @@ int srgan_l1_mean(const float* a, const float* b, long long n, float weight, flo
                   float* da, float* db, void* ws, size_t ws_bytes, void* stream);
 /* batch-KL + correlation + histogram-imitation on mu[B,d] (util_notebook.py:644-662, util.py:470-553).
  * vals[4] = (bKL, corr, hist, w_bkl*bKL + w_corr*corr + w_hist*hist); dmu = gradient of vals[3].
- * hist_target: [bins] device floats.  d <= 16, bins <= 64, B <= 4096. */
+ * A term whose weight is exactly 0 contributes exactly 0 to vals[3] and dmu, whatever its raw value (which vals[0..2] keep
+ * reporting: it may be Inf / NaN on inputs only the other terms are asked about).
+ * hist_target: [bins] device floats.  2 <= B, 2 <= d <= 16, 1 <= bins <= 64, B*d <= 16384 (one workgroup, mu staged in LDS). */
 int srgan_latent_losses(const float* mu, int B, int d, float n_batch, const float* hist_target, int bins,
                         float range_max, float sigma, float w_bkl, float w_corr, float w_hist,
                         float* vals, float* dmu, float* corr_out /* [d*d] Pearson matrix or NULL */, void* stream);

@@ -472,7 +472,10 @@ __global__ __launch_bounds__(256) void latent_losses_kernel(const float* mu_g, i
     float L = 0.f;
     for (int j = 0; j < d; ++j) L += scal[8 + j];
     vals[0] = scal[0]; vals[1] = scal[1]; vals[2] = L;
-    vals[3] = w_bkl * scal[0] + w_corr * scal[1] + w_hist * L;
+    // a term whose weight is exactly 0 adds exactly 0: its raw value may be Inf / NaN on inputs that only the OTHER terms are
+    // asked about (a constant column under the histogram term alone, a column outside the histogram range under batch-KL
+    // alone), and 0 * NaN is NaN.  The select is on the operand, so the sum keeps its shape (and its bits) for non-zero weights.
+    vals[3] = w_bkl * (w_bkl != 0.f ? scal[0] : 0.f) + w_corr * (w_corr != 0.f ? scal[1] : 0.f) + w_hist * (w_hist != 0.f ? L : 0.f);
   }
   if (!dmu) return;
   // gradient per element
@@ -494,7 +497,7 @@ __global__ __launch_bounds__(256) void latent_losses_kernel(const float* mu_g, i
       const float dd = x - ck;
       gh += dh[j * LAT_MAX_BINS + k] * (-knorm * expf(-dd * dd * inv2s2) * dd / (sigma * sigma));
     }
-    dmu[p] = w_bkl * gb + w_corr * gc + w_hist * gh;
+    dmu[p] = w_bkl * (w_bkl != 0.f ? gb : 0.f) + w_corr * (w_corr != 0.f ? gc : 0.f) + w_hist * (w_hist != 0.f ? gh : 0.f);
   }
 }
 

@@ -1933,8 +1933,7 @@ class _TanhFn(Function):
     @staticmethod
     def backward(ctx, gy):
         (y,) = ctx.saved_tensors
-        if y.dim() == 4:
-            gy = to_nhwc(gy)
+        gy = to_nhwc(gy) if y.dim() == 4 else gy.contiguous()      # (y.sum().backward() hands over a stride-0 gradient)
         dx = torch.empty_like(y)
         _lib.check(_lib.load().srgan_tanh_bwd(_ptr(y), _ptr(gy), _ptr(dx), y.numel(), _stream()), "tanh_bwd")
         return dx
@@ -1958,8 +1957,7 @@ class _ActFn(Function):
     @staticmethod
     def backward(ctx, gy):
         (y,) = ctx.saved_tensors
-        if y.dim() == 4:
-            gy = to_nhwc(gy)
+        gy = to_nhwc(gy) if y.dim() == 4 else gy.contiguous()
         return _act_bwd(y, gy, ctx.act, ctx.slope), None, None
 
 
