@@ -49,5 +49,5 @@ for name, ci, h, co, k, s, p in shapes:
     fl = 2.0 * B * ho * ho * co * k * k * ci
     t_f = timeit(lambda: ops._run_conv_fwd(desc, x, w, None, y, 0, 0.0))
     t_d = timeit(lambda: ops._run_conv_dgrad(desc, gy, w, dx))
-    t_w = timeit(lambda: ops._run_conv_wgrad(desc, x, gy, dw, None))
+    t_w = timeit(lambda: ops._run_conv_wgrad(desc, x, gy, dw, None, *ops._conv_ws(desc, x.device)))
     print(f"{name:28s} GFLOP {fl/1e9:7.2f} | fwd {t_f*1e3:7.1f} us {fl/t_f/1e9:6.1f} TF | dgrad {t_d*1e3:7.1f} us {fl/t_d/1e9:6.1f} TF | wgrad {t_w*1e3:7.1f} us {fl/t_w/1e9:6.1f} TF")

@@ -22,4 +22,4 @@ for (B, ci, h, co) in ((64, 64, 64, 128), (64, 128, 32, 256), (64, 256, 16, 512)
     desc = ops._conv_desc(B, h, h, ci, h // 2, h // 2, co, 4, 4, 2, 1, 0, w)
     dw = torch.empty_like(w)
     fl = 2.0 * B * (h // 2) ** 2 * co * 16 * ci
-    print(f"B={B} {ci}->{co} {h}^2  {fl/1e9:.2f} GF:", kernel_time(lambda: ops._run_conv_wgrad(desc, x, gy, dw, None)), flush=True)
+    print(f"B={B} {ci}->{co} {h}^2  {fl/1e9:.2f} GF:", kernel_time(lambda: ops._run_conv_wgrad(desc, x, gy, dw, None, *ops._conv_ws(desc, x.device))), flush=True)

@@ -18,5 +18,5 @@ for B in (32, 64):
     dw = torch.empty_like(w)
     fl = 2.0 * B * 128 * 128 * 3 * 49 * 64
     tf = timeit(lambda: ops._run_conv_fwd(desc, x, w, None, y, 0, 0.0))
-    tw = timeit(lambda: ops._run_conv_wgrad(desc, x, gy, dw, None))
+    tw = timeit(lambda: ops._run_conv_wgrad(desc, x, gy, dw, None, *ops._conv_ws(desc, x.device)))
     print(f"B={B} narrow fwd {tf*1e3:7.1f} us {fl/tf/1e9:5.1f} TF | wgrad {tw*1e3:7.1f} us {fl/tw/1e9:5.1f} TF")

@@ -22,7 +22,7 @@ for B in (8, 16, 32, 64, 128, 256):
     desc = ops._conv_desc(B, h, h, ci, h, h, co, k, k, 1, 1, 0, w)
     dw = torch.empty_like(w)
     fl = 2.0 * B * h * h * co * k * k * ci
-    t = kernel_time(lambda: ops._run_conv_wgrad(desc, x, gy, dw, None))
+    t = kernel_time(lambda: ops._run_conv_wgrad(desc, x, gy, dw, None, *ops._conv_ws(desc, x.device)))
     M = B*h*h
     splits = min(-(-1024//36), -(-M//256)); rps = -(-(-(-M//splits))//32)*32; splits = -(-M//rps)
     print(f"B={B:4d} M={M:7d} splits={splits:3d} ktiles/block={rps//32:4d} blocks={36*splits:5d} kernel {t:8.1f} us  {fl/t/1e6:6.1f} TF")

@@ -12,7 +12,7 @@ for B in (32, 64, 128):
     desc = ops._conv_desc(B, h, h, ci, h, h, co, k, k, 1, 1, 0, w)
     dw = torch.empty_like(w)
     fl = 2.0 * B * h * h * co * k * k * ci
-    fn = lambda: ops._run_conv_wgrad(desc, x, gy, dw, None)
+    fn = lambda: ops._run_conv_wgrad(desc, x, gy, dw, None, *ops._conv_ws(desc, x.device))
     for _ in range(3): fn()
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()

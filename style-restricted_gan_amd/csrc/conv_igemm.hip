@@ -2793,6 +2793,36 @@ static bool igemm16_io_ok(const srgan_conv_desc* d, int act) {
   const WgradPlan w = plan_wgrad(d);
   return w.vec && !w.rows && w.BMc >= 64 && w.BNn >= 64;
 }
+
+// The implicit-GEMM route of srgan_igemm16_conv and srgan_conv2d_io_fwd / _dgrad.  `scratch`: the checked workspace, or null.
+static int igemm16_io_fwd(const srgan_conv_desc* d, const void* src, int src_bf16, const void* packed, const float* bias, void* dst,
+                          int dst_bf16, int act, float slope, float* scratch, hipStream_t st) {
+  IgemmParams p{};
+  fwd_geometry(d, PATH_IGEMM, p);
+  p.src = static_cast<const float*>(src); p.bias = bias; p.dst = static_cast<float*>(dst); p.act = act; p.slope = slope;
+  p.wp = static_cast<const float*>(packed); p.src16 = src_bf16 != 0; p.dst16 = dst_bf16 != 0;
+  return run_igemm(p, 1, st, conv_flops(d), scratch);
+}
+
+static int igemm16_io_dgrad(const srgan_conv_desc* d, const void* src, int src_bf16, const void* packed, void* dst, int dst_bf16,
+                            float* scratch, hipStream_t st) {
+  DgradGeom g = dgrad_geometry(d);
+  g.p.src = static_cast<const float*>(src); g.p.wp = static_cast<const float*>(packed); g.p.src16 = src_bf16 != 0;
+  // reflect: the gradient with respect to the padded image stays an fp32 temp; the fold writes the tensor's type
+  g.p.dst = g.reflect ? scratch : static_cast<float*>(dst); g.p.dst16 = !g.reflect && dst_bf16 != 0;
+  float* slab = scratch ? (g.reflect ? scratch + round_up((long long)d->N * g.Hd * g.Wd * d->I, 64) : scratch) : nullptr;
+  if (int e = run_igemm(g.p, g.phases, st, conv_flops(d), slab)) return e;
+  if (!g.reflect) return 0;
+  const long long n = (long long)d->N * d->Hi * d->Wi * d->I;
+  const dim3 fg((unsigned)std::min<long long>(ceil_div(n, 256), 8192));
+  if (dst_bf16)
+    hipLaunchKernelGGL(reflect_fold_kernel<true>, fg, dim3(256), 0, st, (const float*)scratch, static_cast<float*>(dst), d->N, d->Hi,
+                       d->Wi, d->I, d->pad);
+  else
+    hipLaunchKernelGGL(reflect_fold_kernel<false>, fg, dim3(256), 0, st, (const float*)scratch, static_cast<float*>(dst), d->N, d->Hi,
+                       d->Wi, d->I, d->pad);
+  return check_launch("reflect_fold_kernel");
+}
 }  // namespace srgan
 
 extern "C" int srgan_conv2d_wgrad(const srgan_conv_desc* d, const float* x, const float* dy, float* dw,
@@ -2824,7 +2854,7 @@ extern "C" int srgan_conv2d_wgrad(const srgan_conv_desc* d, const float* x, cons
 
 // ---- bf16 mode, the generic layers (igemm16_kernel, wgrad_kernel<BF>) with bf16 TENSORS on either side: the 3x3 reflect-padded
 // convolutions of the style encoder's blocks (pyfiles/model.py:413-437), whose normalised inputs, outputs and the gradients of
-// both live in HBM as bf16 (srgan_amd.ops._ConvIoFn).  `packed`: the ordinary packed operand of (d, kind, act) in bf16 mode.
+// both live in HBM as bf16 (srgan_amd.ops.conv2d_io).  `packed`: the ordinary packed operand of (d, kind, act) in bf16 mode.
 extern "C" int srgan_igemm16_io_applicable(const srgan_conv_desc* d, int act) {
   if (validate(d) != 0) return 0;
   return igemm16_io_ok(d, act) ? 1 : 0;
@@ -2841,33 +2871,9 @@ extern "C" int srgan_igemm16_conv(const srgan_conv_desc* d, int kind, const void
   const size_t need = srgan_conv2d_packed_scratch(d, kind);
   SRGAN_REQUIRE(need == 0 || (ws && ws_bytes >= need), "igemm16_conv: workspace too small (srgan_conv2d_packed_scratch)");
   hipStream_t st = as_stream(stream);
-  if (kind == 0) {
-    IgemmParams p{};
-    fwd_geometry(d, PATH_IGEMM, p);
-    p.src = static_cast<const float*>(src); p.bias = bias; p.dst = static_cast<float*>(dst); p.act = act; p.slope = slope;
-    p.wp = static_cast<const float*>(packed); p.src16 = src_bf16 != 0; p.dst16 = dst_bf16 != 0;
-    return run_igemm(p, 1, st, conv_flops(d), need ? static_cast<float*>(ws) : nullptr);
-  }
-  DgradGeom g = dgrad_geometry(d);
   float* scratch = need ? static_cast<float*>(ws) : nullptr;
-  g.p.src = static_cast<const float*>(src); g.p.wp = static_cast<const float*>(packed); g.p.src16 = src_bf16 != 0;
-  // reflect: the gradient with respect to the padded image stays an fp32 temp; the fold writes the tensor's type
-  g.p.dst = g.reflect ? scratch : static_cast<float*>(dst);
-  g.p.dst16 = g.reflect ? 0 : (dst_bf16 != 0);
-  float* slab = scratch ? (g.reflect ? scratch + round_up((long long)d->N * g.Hd * g.Wd * d->I, 64) : scratch) : nullptr;
-  if (int e = run_igemm(g.p, g.phases, st, conv_flops(d), slab)) return e;
-  if (g.reflect) {
-    const long long n = (long long)d->N * d->Hi * d->Wi * d->I;
-    const dim3 fg((unsigned)std::min<long long>(ceil_div(n, 256), 8192));
-    if (dst_bf16)
-      hipLaunchKernelGGL(reflect_fold_kernel<true>, fg, dim3(256), 0, st, (const float*)scratch, static_cast<float*>(dst), d->N, d->Hi,
-                         d->Wi, d->I, d->pad);
-    else
-      hipLaunchKernelGGL(reflect_fold_kernel<false>, fg, dim3(256), 0, st, (const float*)scratch, static_cast<float*>(dst), d->N, d->Hi,
-                         d->Wi, d->I, d->pad);
-    return check_launch("reflect_fold_kernel");
-  }
-  return 0;
+  if (kind == 0) return igemm16_io_fwd(d, src, src_bf16, packed, bias, dst, dst_bf16, act, slope, scratch, st);
+  return igemm16_io_dgrad(d, src, src_bf16, packed, dst, dst_bf16, scratch, st);
 }
 
 // x, dy: bf16 tensors.  Same workspace, gradient sink and deferred slab sum as srgan_conv2d_wgrad.
@@ -2954,11 +2960,7 @@ extern "C" int srgan_conv2d_io_fwd(const srgan_conv_desc* d, const void* x, int 
   if (f == 1) return halo16s_run(d, x, packed, bias, y, act, slope, conv_flops(d), st, x_bf16 != 0, y_bf16 != 0);
   const size_t need = srgan_conv2d_packed_scratch(d, 0);
   SRGAN_REQUIRE(need == 0 || (ws && ws_bytes >= need), "conv2d_io_fwd: workspace too small (srgan_conv2d_packed_scratch)");
-  IgemmParams p{};
-  fwd_geometry(d, PATH_IGEMM, p);
-  p.src = static_cast<const float*>(x); p.bias = bias; p.dst = static_cast<float*>(y); p.act = act; p.slope = slope;
-  p.wp = static_cast<const float*>(packed); p.src16 = x_bf16 != 0; p.dst16 = y_bf16 != 0;
-  return run_igemm(p, 1, st, conv_flops(d), need ? static_cast<float*>(ws) : nullptr);
+  return igemm16_io_fwd(d, x, x_bf16, packed, bias, y, y_bf16, act, slope, need ? static_cast<float*>(ws) : nullptr, st);
 }
 
 extern "C" int srgan_conv2d_io_dgrad(const srgan_conv_desc* d, const void* dy, int dy_bf16, const void* packed, void* dx, int dx_bf16,
@@ -2985,10 +2987,7 @@ extern "C" int srgan_conv2d_io_dgrad(const srgan_conv_desc* d, const void* dy, i
   if (b == 1) return halo16t_run(d, dy, packed, dx, conv_flops(d), st, dy_bf16 != 0, dx_bf16 != 0);
   const size_t need = srgan_conv2d_packed_scratch(d, 1);
   SRGAN_REQUIRE(need == 0 || (ws && ws_bytes >= need), "conv2d_io_dgrad: workspace too small (srgan_conv2d_packed_scratch)");
-  DgradGeom g = dgrad_geometry(d);
-  g.p.src = static_cast<const float*>(dy); g.p.wp = static_cast<const float*>(packed); g.p.src16 = dy_bf16 != 0;
-  g.p.dst = static_cast<float*>(dx); g.p.dst16 = dx_bf16 != 0;
-  return run_igemm(g.p, g.phases, st, conv_flops(d), need ? static_cast<float*>(ws) : nullptr);
+  return igemm16_io_dgrad(d, dy, dy_bf16, packed, dx, dx_bf16, need ? static_cast<float*>(ws) : nullptr, st);
 }
 
 // A weight used more than once in one backward pass (the generator runs twice inside util_notebook.py:664 and :689) gets its

@@ -60,7 +60,7 @@ class _Conv2d(nn.Conv2d):
 
     def forward_io(self, x, out_bf16=True):
         """bf16 mode, io_applicable layers: the input may be a bf16 tensor, the output is written as bf16 / fp32 (the style
-        encoder's blocks, ops.py "16-bit activations around the generic convolutions")."""
+        encoder's blocks, ops.py "bf16 activation storage outside the residual trunk")."""
         mode = PAD_REFLECT if self.padding_mode == "reflect" else PAD_ZERO
         return ops.conv2d_io(x, self.weight, self.padding[0], mode, out_bf16)
 

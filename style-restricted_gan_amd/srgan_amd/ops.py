@@ -462,8 +462,8 @@ def _run_conv_dgrad(desc, dy, weight, dx, res=None, mask=None, mask_slope=0.0):
         _lib.check(lib.srgan_add(_ptr(dx), _ptr(res), _ptr(dx), dx.numel(), _stream()), "add")
 
 
-def _run_conv_wgrad(desc, x, dy, dw, dbias, v_image=None):
-    ws, nb = _conv_ws(desc, dy.device)
+def _run_conv_wgrad(desc, x, dy, dw, dbias, ws, nb, v_image=None):
+    """``(ws, nb)``: the workspace of ``_conv_ws(desc, ...)`` (``_wgrad_to_sink`` fetches it)."""
     if v_image is not None:
         _lib.check(_lib.load().srgan_conv2d_wgrad_v(ctypes.byref(desc), _ptr(v_image), _ptr(dy), _ptr(dw), _ptr(dbias), _ptr(ws),
                                                     nb, _stream()), "conv2d_wgrad_v")
@@ -626,6 +626,25 @@ class _wgrad_accumulate:
         return False
 
 
+def _wgrad_to_sink(desc, params, launch):
+    """The weight (and bias) gradient of the convolution ``desc``, through the gradient sink of the current scope when it takes
+    ``params`` = (weight,) or (weight, bias), else into fresh buffers.  ``launch(dd, dw, db, ws, nb)`` makes the one library
+    call: ``dd`` is ``desc`` with the strides of the buffer ``dw``, ``(ws, nb)`` the workspace of ``srgan_conv2d_workspace``.
+    -> (dw, db), both None when the sink took them (the Function then returns no gradient for the parameters)."""
+    slots = _sink_slots(*params)
+    if slots is not None:
+        bufs, acc = slots
+    else:
+        bufs, acc = [torch.empty(p.shape, dtype=torch.float32, device=p.device) for p in params], False
+    dw, db = bufs[0], (bufs[1] if len(bufs) > 1 else None)
+    dd = ConvDesc.from_buffer_copy(desc)
+    dd.sO, dd.sI, dd.sH, dd.sW = dw.stride()
+    ws, nb = _conv_ws(dd, dw.device)
+    with _wgrad_accumulate(acc, slots is not None):
+        launch(dd, dw, db, ws, nb)
+    return (None, None) if slots is not None else (dw, db)
+
+
 def _act_bwd(y, gy, act, slope):
     g = torch.empty_like(gy)
     _lib.check(_lib.load().srgan_act_bwd(_ptr(y), _ptr(gy), _ptr(g), gy.numel(), act, float(slope), _stream()), "act_bwd")
@@ -695,21 +714,8 @@ class _Conv2dFn(Function):
             else:
                 _run_conv_dgrad(ctx.desc, gy, weight, dx, res)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            slots = _sink_slots(*((weight, ctx.bias) if ctx.has_bias else (weight,)))
-            acc = False
-            if slots is not None:
-                (dw, *rest), acc = slots
-                db = rest[0] if rest else None
-            else:
-                dw = torch.empty(weight.shape, dtype=torch.float32, device=weight.device)
-                if ctx.has_bias:
-                    db = torch.empty(weight.shape[0], dtype=torch.float32, device=weight.device)
-            desc = ConvDesc.from_buffer_copy(ctx.desc)
-            desc.sO, desc.sI, desc.sH, desc.sW = dw.stride()
-            with _wgrad_accumulate(acc, slots is not None):
-                _run_conv_wgrad(desc, x, gy, dw, db, ctx.v_image)
-            if slots is not None:
-                dw = db = None
+            dw, db = _wgrad_to_sink(ctx.desc, (weight, ctx.bias) if ctx.has_bias else (weight,),
+                                    lambda dd, dw, db, ws, nb: _run_conv_wgrad(dd, x, gy, dw, db, ws, nb, ctx.v_image))
         return dx, dw, db, None, None, None, None, None, None, None, None
 
 
@@ -755,14 +761,7 @@ class _ConvTranspose2dFn(Function):
             dx = torch.empty_like(x)
             _run_conv_fwd(ctx.desc, gy, weight, None, dx, ACT_NONE, 0.0)
         if ctx.needs_input_grad[1]:
-            slots = _sink_slots(weight)
-            (dw,), acc = slots if slots is not None else ([torch.empty(weight.shape, dtype=torch.float32, device=weight.device)], False)
-            desc = ConvDesc.from_buffer_copy(ctx.desc)
-            desc.sO, desc.sI, desc.sH, desc.sW = dw.stride()
-            with _wgrad_accumulate(acc, slots is not None):
-                _run_conv_wgrad(desc, gy, x, dw, None)
-            if slots is not None:
-                dw = None
+            dw, _ = _wgrad_to_sink(ctx.desc, (weight,), lambda dd, dw, db, ws, nb: _run_conv_wgrad(dd, gy, x, dw, None, ws, nb))
         return dx, dw, None, None
 
 
@@ -1130,18 +1129,13 @@ class _NormActConvFn(Function):
         n, c, h, w = x.shape
         dw = None
         if ctx.needs_input_grad[3]:
-            slots = _sink_slots(weight)
-            (dw,), acc = slots if slots is not None else ([torch.empty(weight.shape, dtype=torch.float32, device=weight.device)], False)
-            desc = ConvDesc.from_buffer_copy(ctx.desc)
-            desc.sO, desc.sI, desc.sH, desc.sW = dw.stride()
-            with _wgrad_accumulate(acc, slots is not None):
-                if ctx.v_image is not None:
-                    _run_conv_wgrad(desc, None, gy, dw, None, ctx.v_image)
-                else:   # no V kept (layer outside the F(4x4,3x3) weight-gradient geometry): recompute the normalised input
+            def launch(dd, dw, db, ws, nb):
+                hx = None
+                if ctx.v_image is None:   # no V kept (layer outside the F(4x4,3x3) weight-gradient geometry): recompute the normalised input
                     hx = _InstNormFn.apply(x.detach(), scale, shift, None, ctx.act, ctx.slope, ctx.eps)
-                    _run_conv_wgrad(desc, hx, gy, dw, None)
-            if slots is not None:
-                dw = None
+                _run_conv_wgrad(dd, hx, gy, dw, None, ws, nb, ctx.v_image)
+
+            dw, _ = _wgrad_to_sink(ctx.desc, (weight,), launch)
         dx = dscale = dshift = None
         if ctx.needs_input_grad[0] or (scale is not None and ctx.needs_input_grad[1]):
             dh = torch.empty_like(x)
@@ -1232,15 +1226,8 @@ class _ResBlockFn(Function):
             return vimg, zimg, dsc, dsh
 
         def wgrad_vz(desc, weight, v_fwd, zimg):
-            slots = _sink_slots(weight)
-            (dw,), acc = slots if slots is not None else ([torch.empty(weight.shape, dtype=torch.float32, device=dev)], False)
-            dd = ConvDesc.from_buffer_copy(desc)
-            dd.sO, dd.sI, dd.sH, dd.sW = dw.stride()
-            ws, nb = _conv_ws(dd, dev)
-            with _wgrad_accumulate(acc, slots is not None):
-                _lib.check(lib.srgan_conv2d_wgrad_vz(ctypes.byref(dd), _ptr(v_fwd), _ptr(zimg), _ptr(dw), _ptr(ws), nb, st),
-                           "conv2d_wgrad_vz")
-            return None if slots is not None else dw
+            return _wgrad_to_sink(desc, (weight,), lambda dd, dw, db, ws, nb: _lib.check(
+                lib.srgan_conv2d_wgrad_vz(ctypes.byref(dd), _ptr(v_fwd), _ptr(zimg), _ptr(dw), _ptr(ws), nb, st), "conv2d_wgrad_vz"))[0]
 
         def dgrad_from_v(desc, weight, vimg, res, ch):
             hit, _ = _packed(desc, weight, 1, ACT_NONE)
@@ -1331,24 +1318,13 @@ class _ResBlockBf16Fn(Function):
                        "instnorm_bwd_io")
             return dy, dsc, dsh
 
-        def wgrad(desc, weight, xin, xin16, dy):
-            slots = _sink_slots(weight)
-            (dw,), acc = slots if slots is not None else ([torch.empty(weight.shape, dtype=torch.float32, device=dev)], False)
-            dd = ConvDesc.from_buffer_copy(desc)
-            dd.sO, dd.sI, dd.sH, dd.sW = dw.stride()
-            ws, nb = _conv_ws(dd, dev)
-            with _wgrad_accumulate(acc, slots is not None):
-                _lib.check(lib.srgan_halo16_wgrad(ctypes.byref(dd), _ptr(xin), xin16, _ptr(dy), 1, _ptr(dw), _ptr(ws), nb, st),
-                           "halo16_wgrad")
-            return None if slots is not None else dw
-
         dy2, ds2, dh2 = norm_bwd(y2, g, 0, s2, h2, mean2, rstd2, ACT_NONE)
-        dw2 = wgrad(d2, w2, hh, 1, dy2) if ctx.needs_input_grad[6] else None
+        dw2 = _io_wgrad(_PatchRoute, d2, w2, hh, dy2) if ctx.needs_input_grad[6] else None
         hit2, _ = _packed(d2, w2, 1, ACT_NONE)
         dh = b16()
         _lib.check(lib.srgan_halo16_conv(ctypes.byref(d2), 1, _ptr(dy2), 1, _ptr(hit2.buf), None, _ptr(dh), 1, st), "halo16_conv")
         dy1, ds1, dh1 = norm_bwd(y1, dh, 1, s1, h1, mean1, rstd1, ACT_RELU)
-        dw1 = wgrad(d1, w1, x, 0, dy1) if ctx.needs_input_grad[5] else None
+        dw1 = _io_wgrad(_PatchRoute, d1, w1, x, dy1) if ctx.needs_input_grad[5] else None
         dx = None
         if ctx.needs_input_grad[0]:
             hit1, _ = _packed(d1, w1, 1, ACT_NONE)
@@ -1357,28 +1333,50 @@ class _ResBlockBf16Fn(Function):
         return dx, ds1, dh1, ds2, dh2, dw1, dw2, None
 
 
-# ---- bf16 activation storage outside the residual trunk (round 4) -------------------------------------------------------
-# In the bf16 mode the generator's down / up path keeps the tensors BETWEEN its stride-2 convolutions and their norms in bf16
-# (pyfiles/model.py:212-215, 227-231, 245-246):
+# ---- bf16 activation storage outside the residual trunk ----------------------------------------------------------------
+# In the bf16 mode, inside a packed-weight scope, the tensors BETWEEN the layers of four chains live in HBM as bf16; the residual
+# stream, the statistics, the weight gradients and the master weights stay fp32:
+#   generator down / up path (pyfiles/model.py:212-215, 227-231, 245-246), 4x4 / stride-2 convolutions and their norms:
 #     norm0 out (fp32 -> bf16) -> down1 (bf16 -> bf16) -> norm1 (bf16 -> bf16) -> down2 (bf16 -> bf16) -> norm2 (bf16 -> fp32) -> trunk
 #     trunk out (fp32) -> up0 (fp32 -> bf16) -> norm (bf16 -> bf16) -> up1 (bf16 -> bf16) -> norm (bf16 -> fp32) -> RGB head
+#   style-encoder block (pyfiles/model.py:413-437; reflect-padded 3x3 convolutions on 62 / 31 / 15 / 7-pixel maps):
+#     x (fp32, residual stream) -> norm1 (fp32 -> bf16) -> conv1 (bf16 -> bf16) -> norm2 (bf16 -> bf16) -> conv2 (bf16 -> bf16)
+#       -> AvgPool2d (bf16 -> fp32) -> + shortcut (fp32)
+#   discriminator trunk (pyfiles/model.py:302-309): [conv 4x4 / stride 2 without bias -> LeakyReLU] x num_cls with no norm between,
+#     each tensor written by one convolution's epilogue and read by the next one's gather;
+#   RGB ends: the generator's 7x7 input and output layers, whose 64-channel side may be bf16 (the 3-channel side is fp32).
 # The convolutions round their operands to bf16 anyway, so a bf16 norm OUTPUT changes no product; a bf16 conv OUTPUT is what
 # torch.autocast stores (its statistics are then taken from the rounded values, as in the residual-block node above).  The
-# gradients take the types of the tensors they belong to.  Served by the LDS-resident-patch kernels (csrc/conv_halo16.hip:
-# halo16s / halo16t / halo16s2_wgrad with IN16 / OUT16) and the instance-norm kernels with 16-bit I/O (srgan_instnorm_fwd_io /
-# _bwd_io): half the bytes in the norm passes, region loads without conversion in the convolutions.
+# gradients take the types of the tensors they belong to.  One Function (_ConvBf16Fn) serves every such convolution; a ROUTE names
+# the C entry family that runs it: the LDS-resident-patch kernels (csrc/conv_halo16.hip: halo16s / halo16t / halo16s2_wgrad with
+# IN16 / OUT16) for the generator, the implicit GEMM with 64-deep K tiles and the vector weight-gradient kernel (csrc/
+# conv_igemm.hip: igemm16_kernel; with fp32 tensors those layers are bound by their own result and by the fp32 -> bf16 conversion
+# on the way into LDS, profiles/LOG.md round 4) for the encoder, whichever kernel serves the direction (srgan_conv2d_io_*) for the
+# discriminator and the RGB ends.  The norms are the instance-norm kernels with 16-bit I/O (srgan_instnorm_fwd_io / _bwd_io).
 STORAGE_BF16 = True               # tests switch it off to compare against the fp32-tensor chain
+_NO_D_IO16 = _lib.ab("SRGAN_NO_D_IO16")          # A/B (experiment build only): the discriminators on fp32 tensors
+_NO_RGB_IO16 = _lib.ab("SRGAN_NO_RGB_IO16")      # A/B (experiment build only): fp32 tensors around the generator's 7x7 RGB layers
+_NO_CONV_IO16 = _lib.ab("SRGAN_NO_CONV_IO16")      # A/B (experiment build only): the encoder's blocks on fp32 tensors
 
 
 def _is16(t):
     return 1 if t.dtype == torch.bfloat16 else 0
 
 
+def _to16(t):
+    return t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)
+
+
+def _io_gate(weight):
+    """What every bf16-tensor convolution needs: storage switch on, packed-weight scope, bf16 mode, a device weight."""
+    return bool(STORAGE_BF16 and _pack_cache_on and get_compute_dtype() == "bf16" and weight.is_cuda)
+
+
 def s2_io_applicable(n, ci, hi, wi, co, weight, transposed):
     """True when a 4x4 / stride-2 / pad-1 Conv2d (ci -> co, hi x wi -> half) -- or, transposed=True, the ConvTranspose2d
     (ci -> co, hi x wi -> double) -- can take / write bf16 tensors: bf16 mode, packed-weight scope, all three directions on the
     patch kernels."""
-    if not (STORAGE_BF16 and _pack_cache_on and get_compute_dtype() == "bf16" and weight.is_cuda):
+    if not _io_gate(weight):
         return False
     if tuple(weight.shape[2:]) != (4, 4):
         return False
@@ -1391,69 +1389,11 @@ def s2_io_applicable(n, ci, hi, wi, co, weight, transposed):
     return bool(_lib.load().srgan_halo16s2_applicable(ctypes.byref(desc)))
 
 
-def norm_io_applicable(n, c, h, w):
-    return bool(STORAGE_BF16 and get_compute_dtype() == "bf16" and _lib.load().srgan_instnorm_io_applicable(n, h * w, c))
-
-
-def _s2_wgrad(desc, weight, xin, dy, needs):
-    """dW of conv C (desc) from xin (C's input side) and dy (C's output side), either fp32 or bf16; through the gradient sink."""
-    if not needs:
-        return None
-    slots = _sink_slots(weight)
-    (dw,), acc = slots if slots is not None else ([torch.empty(weight.shape, dtype=torch.float32, device=weight.device)], False)
-    dd = ConvDesc.from_buffer_copy(desc)
-    dd.sO, dd.sI, dd.sH, dd.sW = dw.stride()
-    ws, nb = _conv_ws(dd, xin.device)
-    with _wgrad_accumulate(acc, slots is not None):
-        _lib.check(_lib.load().srgan_halo16_wgrad(ctypes.byref(dd), _ptr(xin), _is16(xin), _ptr(dy), _is16(dy), _ptr(dw), _ptr(ws), nb,
-                                                   _stream()), "halo16_wgrad")
-    return None if slots is not None else dw
-
-
-class _ConvS2IoFn(Function):
-    """4x4 / stride-2 / pad-1 Conv2d without bias in the bf16 mode, input fp32 or bf16, output bf16 or fp32 (see above)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, out_bf16):
-        x = to_nhwc(x)
-        n, i, hi, wi = x.shape
-        o = weight.shape[0]
-        desc = _conv_desc(n, hi, wi, i, hi // 2, wi // 2, o, 4, 4, 2, 1, PAD_ZERO, weight)
-        hit, _ = _packed(desc, weight, 0, ACT_NONE)
-        y = nhwc_empty(n, o, hi // 2, wi // 2, x.device, torch.bfloat16 if out_bf16 else torch.float32)
-        _lib.check(_lib.load().srgan_halo16_conv(ctypes.byref(desc), 0, _ptr(x), _is16(x), _ptr(hit.buf), None, _ptr(y), _is16(y),
-                                                 _stream()), "halo16_conv")
-        ctx.desc, ctx.weight = desc, weight
-        ctx.save_for_backward(x)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        (x,) = ctx.saved_tensors
-        gy = to_nhwc(gy)
-        weight = ctx.weight
-        dx = None
-        if ctx.needs_input_grad[0]:
-            hit, _ = _packed(ctx.desc, weight, 1, ACT_NONE)
-            dx = torch.empty_like(x)
-            _lib.check(_lib.load().srgan_halo16_conv(ctypes.byref(ctx.desc), 1, _ptr(gy), _is16(gy), _ptr(hit.buf), None, _ptr(dx),
-                                                     _is16(dx), _stream()), "halo16_conv")
-        dw = _s2_wgrad(ctx.desc, weight, x, gy, ctx.needs_input_grad[1])
-        return dx, dw, None
-
-
-# ---- round 6: 16-bit activations in the discriminator trunks (conv 4x4 / stride 2 without bias -> LeakyReLU, model.py:302-309) ----
-_NO_D_IO16 = _lib.ab("SRGAN_NO_D_IO16")          # A/B (experiment build only): the discriminators on fp32 tensors
-
-
-_NO_RGB_IO16 = _lib.ab("SRGAN_NO_RGB_IO16")      # A/B (experiment build only): fp32 tensors around the generator's 7x7 RGB layers
-
-
 def conv_act_io_applicable(n, ci, hi, wi, weight, act, k=4, stride=2, pad=1):
     """True when a Conv2d without bias followed by `act` can take and write bf16 tensors in all three directions (bf16 mode,
     packed-weight scope; ``srgan_conv2d_io_applicable``): the 4x4 / stride-2 / pad-1 layers of the discriminator trunks, and --
     (k, stride, pad) = (7, 1, 3), act none -- the generator's RGB input and output layers, whose 64-channel side may be bf16."""
-    if not (STORAGE_BF16 and _pack_cache_on and get_compute_dtype() == "bf16" and weight.is_cuda):
+    if not _io_gate(weight):
         return False
     if (_NO_D_IO16 and k == 4) or (_NO_RGB_IO16 and k == 7):
         return False
@@ -1464,88 +1404,134 @@ def conv_act_io_applicable(n, ci, hi, wi, weight, act, k=4, stride=2, pad=1):
     return bool(_lib.load().srgan_conv2d_io_applicable(ctypes.byref(desc), act))
 
 
-class _ConvActIoFn(Function):
-    """Conv2d without bias + activation (fused epilogue) in the bf16 mode with fp32 or bf16 tensors on either side (the layers of
-    ``conv_act_io_applicable``).  Backward: the activation's derivative is applied to the incoming gradient by one 16-bit
-    elementwise pass whose result -- always bf16: both kernels that read it round it to bf16 anyway -- feeds the input-gradient
-    and the weight-gradient kernel; dx has x's type."""
+def conv_io_applicable(n, ci, hi, wi, weight, pad, pad_mode):
+    """True when a stride-1 Conv2d without bias (ci -> weight.shape[0], hi x wi) can take and write bf16 tensors in all three
+    directions: bf16 mode, packed-weight scope, every direction on the generic bf16 kernels."""
+    if not _io_gate(weight) or _NO_CONV_IO16:
+        return False
+    co, _, kh, kw = weight.shape
+    ho, wo = hi + 2 * pad - kh + 1, wi + 2 * pad - kw + 1
+    if ho < 1 or wo < 1:
+        return False
+    desc = _conv_desc(n, hi, wi, ci, ho, wo, co, kh, kw, 1, pad, pad_mode, weight)
+    return bool(_lib.load().srgan_igemm16_io_applicable(ctypes.byref(desc), ACT_NONE))
+
+
+def norm_io_applicable(n, c, h, w):
+    return bool(STORAGE_BF16 and get_compute_dtype() == "bf16" and _lib.load().srgan_instnorm_io_applicable(n, h * w, c))
+
+
+# The routes: ``what`` names the public wrapper in error messages, ``scratch`` says whether the family takes the packed operand's
+# per-call scratch, ``conv(desc, kind, src, hit, dst, act, slope, ws, nb)`` runs conv C forward (kind 0) or its input gradient
+# (kind 1) and ``wgrad(dd, xin, dy, dw, ws, nb)`` its weight gradient from C's input side and output side, fp32 or bf16.
+class _PatchRoute:
+    """srgan_halo16_conv / srgan_halo16_wgrad: the generator's down / up path (and the bf16 residual-block node)."""
+    what, scratch = "conv2d_s2_io", False
 
     @staticmethod
-    def forward(ctx, x, weight, act, slope, out_bf16, k, stride, pad):
+    def conv(desc, kind, src, hit, dst, act, slope, ws, nb):
+        _lib.check(_lib.load().srgan_halo16_conv(ctypes.byref(desc), kind, _ptr(src), _is16(src), _ptr(hit.buf), None, _ptr(dst),
+                                                 _is16(dst), _stream()), "halo16_conv")
+
+    @staticmethod
+    def wgrad(dd, xin, dy, dw, ws, nb):
+        _lib.check(_lib.load().srgan_halo16_wgrad(ctypes.byref(dd), _ptr(xin), _is16(xin), _ptr(dy), _is16(dy), _ptr(dw), _ptr(ws), nb,
+                                                  _stream()), "halo16_wgrad")
+
+
+class _GenericRoute:
+    """srgan_igemm16_conv / srgan_igemm16_wgrad: the style encoder's blocks."""
+    what, scratch = "conv2d_io", True
+
+    @staticmethod
+    def conv(desc, kind, src, hit, dst, act, slope, ws, nb):
+        _lib.check(_lib.load().srgan_igemm16_conv(ctypes.byref(desc), kind, _ptr(src), _is16(src), _ptr(hit.buf), None, _ptr(dst),
+                                                  _is16(dst), act, slope, _ptr(ws), nb, _stream()), "igemm16_conv")
+
+    @staticmethod
+    def wgrad(dd, xin, dy, dw, ws, nb):
+        # both operands as bf16 tensors (the kernel rounds them to bf16 anyway; an fp32 side -- a block boundary -- is rounded by
+        # one elementwise pass here)
+        x16, g16 = _to16(xin), _to16(dy)
+        _lib.check(_lib.load().srgan_igemm16_wgrad(ctypes.byref(dd), _ptr(x16), _ptr(g16), _ptr(dw), _ptr(ws), nb, _stream()),
+                   "igemm16_wgrad")
+
+
+class _AnyRoute:
+    """srgan_conv2d_io_fwd / srgan_conv2d_io_dgrad on whatever kernel serves the direction, srgan_halo16_wgrad: the discriminator
+    trunks and the RGB ends."""
+    what, scratch = "conv2d_act_io", True
+    wgrad = staticmethod(_PatchRoute.wgrad)      # (halo16s2_wgrad_kernel takes bf16 x / dy)
+
+    @staticmethod
+    def conv(desc, kind, src, hit, dst, act, slope, ws, nb):
+        lib = _lib.load()
+        if kind == 0:
+            _lib.check(lib.srgan_conv2d_io_fwd(ctypes.byref(desc), _ptr(src), _is16(src), _ptr(hit.buf), None, _ptr(dst), _is16(dst), act,
+                                               slope, _ptr(ws), nb, _stream()), "conv2d_io_fwd")
+        else:
+            _lib.check(lib.srgan_conv2d_io_dgrad(ctypes.byref(desc), _ptr(src), _is16(src), _ptr(hit.buf), _ptr(dst), _is16(dst), _ptr(ws),
+                                                 nb, _stream()), "conv2d_io_dgrad")
+
+
+def _io_operand(route, desc, kind, weight, act=ACT_NONE):
+    """-> (packed operand, scratch workspace, its bytes) for ``route.conv`` of direction ``kind``; (.., None, 0) when the route
+    takes no scratch or the operand wants none."""
+    hit, scratch = _packed(desc, weight, kind, act)
+    if not (route.scratch and scratch):
+        return hit, None, 0
+    return hit, workspace(weight.device, scratch), scratch
+
+
+def _io_wgrad(route, desc, weight, xin, dy):
+    return _wgrad_to_sink(desc, (weight,), lambda dd, dw, db, ws, nb: route.wgrad(dd, xin, dy, dw, ws, nb))[0]
+
+
+class _ConvBf16Fn(Function):
+    """Conv2d without bias (+ activation in the epilogue) -- or, ``transposed``, the ConvTranspose2d that is the input-gradient
+    form of the conv C whose weight is w viewed as [O = Cin][I = Cout] (as _ConvTranspose2dFn) -- in the bf16 mode with fp32 or
+    bf16 tensors on either side, on ``route``.  Backward: an activation's derivative is applied to the incoming gradient by one
+    16-bit elementwise pass whose result -- always bf16: both kernels that read it round it to bf16 anyway -- feeds the
+    input-gradient and the weight-gradient kernel; dx has x's type.  The weight is held by reference and read at backward time."""
+
+    @staticmethod
+    def forward(ctx, x, weight, route, transposed, k, stride, pad, pad_mode, act, slope, out_bf16):
         x = to_nhwc(x)
         n, i, hi, wi = x.shape
-        o, i2 = weight.shape[:2]
+        kh, kw = k
+        o, i2 = weight.shape[1 if transposed else 0], weight.shape[0 if transposed else 1]
         if i != i2:
-            raise _lib.SrganHipError(f"conv2d_act_io: input has {i} channels, weight expects {i2}")
-        ho, wo = (hi + 2 * pad - k) // stride + 1, (wi + 2 * pad - k) // stride + 1
-        desc = _conv_desc(n, hi, wi, i, ho, wo, o, k, k, stride, pad, PAD_ZERO, weight)
-        hit, scratch = _packed(desc, weight, 0, act)
-        ws = workspace(x.device, scratch) if scratch else None
+            raise _lib.SrganHipError(f"{'conv_transpose2d_io' if transposed else route.what}: input has {i} channels, weight expects {i2}")
+        if transposed:      # conv C: input = y-space [n, o, ho, wo], output = x-space [n, i, hi, wi]
+            ho, wo = (hi - 1) * stride - 2 * pad + kh, (wi - 1) * stride - 2 * pad + kw
+            desc = _conv_desc(n, ho, wo, o, hi, wi, i, kh, kw, stride, pad, pad_mode, weight)
+        else:
+            ho, wo = (hi + 2 * pad - kh) // stride + 1, (wi + 2 * pad - kw) // stride + 1
+            desc = _conv_desc(n, hi, wi, i, ho, wo, o, kh, kw, stride, pad, pad_mode, weight)
+        hit, ws, nb = _io_operand(route, desc, int(transposed), weight, act)
         y = nhwc_empty(n, o, ho, wo, x.device, torch.bfloat16 if out_bf16 else torch.float32)
-        _lib.check(_lib.load().srgan_conv2d_io_fwd(ctypes.byref(desc), _ptr(x), _is16(x), _ptr(hit.buf), None, _ptr(y), _is16(y), act,
-                                                   float(slope), _ptr(ws), scratch, _stream()), "conv2d_io_fwd")
-        ctx.desc, ctx.weight, ctx.act, ctx.slope = desc, weight, act, slope
+        route.conv(desc, int(transposed), x, hit, y, act, float(slope), ws, nb)
+        ctx.desc, ctx.weight, ctx.route, ctx.transposed, ctx.act, ctx.slope = desc, weight, route, transposed, act, slope
         ctx.save_for_backward(x, y if act != ACT_NONE else None)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, y = ctx.saved_tensors
-        gy = to_nhwc(gy)
+        g = gy = to_nhwc(gy)
         weight = ctx.weight
-        lib = _lib.load()
         if ctx.act != ACT_NONE:
             g = torch.empty_like(gy, dtype=torch.bfloat16)          # (keeps gy's NHWC-dense strides: no copy)
-            _lib.check(lib.srgan_act_bwd_io(_ptr(y), _is16(y), _ptr(gy), _is16(gy), _ptr(g), 1, gy.numel(), ctx.act, float(ctx.slope),
-                                            _stream()), "act_bwd_io")
-        else:
-            g = gy
-        dx = None
+            _lib.check(_lib.load().srgan_act_bwd_io(_ptr(y), _is16(y), _ptr(gy), _is16(gy), _ptr(g), 1, gy.numel(), ctx.act,
+                                                    float(ctx.slope), _stream()), "act_bwd_io")
+        dx = dw = None
         if ctx.needs_input_grad[0]:
-            hit, scratch = _packed(ctx.desc, weight, 1, ACT_NONE)
-            ws = workspace(g.device, scratch) if scratch else None
+            hit, ws, nb = _io_operand(ctx.route, ctx.desc, int(not ctx.transposed), weight)
             dx = torch.empty_like(x)
-            _lib.check(lib.srgan_conv2d_io_dgrad(ctypes.byref(ctx.desc), _ptr(g), _is16(g), _ptr(hit.buf), _ptr(dx), _is16(dx), _ptr(ws),
-                                                 scratch, _stream()), "conv2d_io_dgrad")
-        dw = _s2_wgrad(ctx.desc, weight, x, g, ctx.needs_input_grad[1])
-        return dx, dw, None, None, None, None, None, None
-
-
-def conv2d_act_io(x, weight, act, slope, out_bf16, k=4, stride=2, pad=1):
-    return _ConvActIoFn.apply(x, weight, act, slope, bool(out_bf16), k, stride, pad)
-
-
-class _ConvT2IoFn(Function):
-    """4x4 / stride-2 / pad-1 ConvTranspose2d in the bf16 mode with fp32 or bf16 tensors on either side: the transposed form of
-    the conv C whose weight is w viewed as [O = Cin][I = Cout] (as _ConvTranspose2dFn)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, out_bf16):
-        x = to_nhwc(x)
-        n, ci, hi, wi = x.shape
-        co = weight.shape[1]
-        desc = _conv_desc(n, 2 * hi, 2 * wi, co, hi, wi, ci, 4, 4, 2, 1, PAD_ZERO, weight)
-        hit, _ = _packed(desc, weight, 1, ACT_NONE)
-        y = nhwc_empty(n, co, 2 * hi, 2 * wi, x.device, torch.bfloat16 if out_bf16 else torch.float32)
-        _lib.check(_lib.load().srgan_halo16_conv(ctypes.byref(desc), 1, _ptr(x), _is16(x), _ptr(hit.buf), None, _ptr(y), _is16(y),
-                                                 _stream()), "halo16_conv")
-        ctx.desc, ctx.weight = desc, weight
-        ctx.save_for_backward(x)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        (x,) = ctx.saved_tensors
-        gy = to_nhwc(gy)
-        weight = ctx.weight
-        dx = None
-        if ctx.needs_input_grad[0]:
-            hit, _ = _packed(ctx.desc, weight, 0, ACT_NONE)
-            dx = torch.empty_like(x)
-            _lib.check(_lib.load().srgan_halo16_conv(ctypes.byref(ctx.desc), 0, _ptr(gy), _is16(gy), _ptr(hit.buf), None, _ptr(dx),
-                                                     _is16(dx), _stream()), "halo16_conv")
-        dw = _s2_wgrad(ctx.desc, weight, gy, x, ctx.needs_input_grad[1])      # C's input side is y-space
-        return dx, dw, None
+            ctx.route.conv(ctx.desc, int(not ctx.transposed), g, hit, dx, ACT_NONE, 0.0, ws, nb)
+        if ctx.needs_input_grad[1]:      # C's input side is y-space when transposed
+            dw = _io_wgrad(ctx.route, ctx.desc, weight, *((g, x) if ctx.transposed else (x, g)))
+        return dx, dw, None, None, None, None, None, None, None, None, None
 
 
 class _InstNormIoFn(Function):
@@ -1586,102 +1572,23 @@ class _InstNormIoFn(Function):
 
 
 def conv2d_s2_io(x, weight, out_bf16):
-    return _ConvS2IoFn.apply(x, weight, bool(out_bf16))
+    return _ConvBf16Fn.apply(x, weight, _PatchRoute, False, (4, 4), 2, 1, PAD_ZERO, ACT_NONE, 0.0, bool(out_bf16))
 
 
 def conv_transpose2d_io(x, weight, out_bf16):
-    return _ConvT2IoFn.apply(x, weight, bool(out_bf16))
+    return _ConvBf16Fn.apply(x, weight, _PatchRoute, True, (4, 4), 2, 1, PAD_ZERO, ACT_NONE, 0.0, bool(out_bf16))
+
+
+def conv2d_io(x, weight, padding=0, pad_mode=PAD_ZERO, out_bf16=True):
+    return _ConvBf16Fn.apply(x, weight, _GenericRoute, False, weight.shape[2:], 1, padding, pad_mode, ACT_NONE, 0.0, bool(out_bf16))
+
+
+def conv2d_act_io(x, weight, act, slope, out_bf16, k=4, stride=2, pad=1):
+    return _ConvBf16Fn.apply(x, weight, _AnyRoute, False, (k, k), stride, pad, PAD_ZERO, act, slope, bool(out_bf16))
 
 
 def instance_norm_act_io(x, scale, shift, act=ACT_NONE, slope=0.0, eps=1e-5, out_bf16=False):
     return _InstNormIoFn.apply(x, scale, shift, act, slope, eps, bool(out_bf16))
-
-
-# ---- bf16 compute mode: 16-bit activations around the GENERIC convolutions (round 5) --------------------------------------
-# The style encoder's blocks (reference pyfiles/model.py:413-437: norm -> LeakyReLU -> conv3x3 -> norm -> LeakyReLU -> conv3x3 ->
-# AvgPool2d, all reflect-padded, on 62 / 31 / 15 / 7-pixel maps) run on the implicit GEMM with 64-deep K tiles
-# (csrc/conv_igemm.hip: igemm16_kernel) and the vector weight-gradient kernel.  With fp32 tensors those layers are bound by their
-# own result and by the fp32 -> bf16 conversion on the way into LDS (profiles/LOG.md, round 4); here the tensors between the
-# norms, the convolutions and the pool are bf16:
-#     x (fp32, residual stream) -> norm1 (fp32 -> bf16) -> conv1 (bf16 -> bf16) -> norm2 (bf16 -> bf16) -> conv2 (bf16 -> bf16)
-#       -> AvgPool2d (bf16 -> fp32) -> + shortcut (fp32)
-# A bf16 norm OUTPUT changes no product (the convolution rounds its operand anyway), a bf16 conv OUTPUT is what torch.autocast
-# stores; gradients take the types of the tensors they belong to, and both operands of the weight gradient are bf16 tensors.
-
-
-_NO_CONV_IO16 = _lib.ab("SRGAN_NO_CONV_IO16")      # A/B (experiment build only): the encoder's blocks on fp32 tensors
-
-
-def conv_io_applicable(n, ci, hi, wi, weight, pad, pad_mode):
-    """True when a stride-1 Conv2d without bias (ci -> weight.shape[0], hi x wi) can take and write bf16 tensors in all three
-    directions: bf16 mode, packed-weight scope, every direction on the generic bf16 kernels."""
-    if not (STORAGE_BF16 and _pack_cache_on and get_compute_dtype() == "bf16" and weight.is_cuda) or _NO_CONV_IO16:
-        return False
-    co, _, kh, kw = weight.shape
-    ho, wo = hi + 2 * pad - kh + 1, wi + 2 * pad - kw + 1
-    if ho < 1 or wo < 1:
-        return False
-    desc = _conv_desc(n, hi, wi, ci, ho, wo, co, kh, kw, 1, pad, pad_mode, weight)
-    return bool(_lib.load().srgan_igemm16_io_applicable(ctypes.byref(desc), ACT_NONE))
-
-
-def _to16(t):
-    return t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)
-
-
-class _ConvIoFn(Function):
-    """Stride-1 Conv2d without bias in the bf16 mode, input fp32 or bf16, output bf16 or fp32 (see above)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, pad, pad_mode, out_bf16):
-        x = to_nhwc(x)
-        n, i, hi, wi = x.shape
-        o, i2, kh, kw = weight.shape
-        if i != i2:
-            raise _lib.SrganHipError(f"conv2d_io: input has {i} channels, weight expects {i2}")
-        ho, wo = hi + 2 * pad - kh + 1, wi + 2 * pad - kw + 1
-        desc = _conv_desc(n, hi, wi, i, ho, wo, o, kh, kw, 1, pad, pad_mode, weight)
-        hit, scratch = _packed(desc, weight, 0, ACT_NONE)
-        ws = workspace(x.device, scratch) if scratch else None
-        y = nhwc_empty(n, o, ho, wo, x.device, torch.bfloat16 if out_bf16 else torch.float32)
-        _lib.check(_lib.load().srgan_igemm16_conv(ctypes.byref(desc), 0, _ptr(x), _is16(x), _ptr(hit.buf), None, _ptr(y), _is16(y),
-                                                  ACT_NONE, 0.0, _ptr(ws), scratch, _stream()), "igemm16_conv")
-        ctx.desc, ctx.weight = desc, weight
-        ctx.save_for_backward(x)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        (x,) = ctx.saved_tensors
-        gy = to_nhwc(gy)
-        weight = ctx.weight
-        lib = _lib.load()
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            hit, scratch = _packed(ctx.desc, weight, 1, ACT_NONE)
-            ws = workspace(gy.device, scratch) if scratch else None
-            dx = torch.empty_like(x)
-            _lib.check(lib.srgan_igemm16_conv(ctypes.byref(ctx.desc), 1, _ptr(gy), _is16(gy), _ptr(hit.buf), None, _ptr(dx), _is16(dx),
-                                              ACT_NONE, 0.0, _ptr(ws), scratch, _stream()), "igemm16_conv")
-        if ctx.needs_input_grad[1]:
-            slots = _sink_slots(weight)
-            (dw,), acc = slots if slots is not None else ([torch.empty(weight.shape, dtype=torch.float32, device=weight.device)], False)
-            dd = ConvDesc.from_buffer_copy(ctx.desc)
-            dd.sO, dd.sI, dd.sH, dd.sW = dw.stride()
-            ws, nb = _conv_ws(dd, gy.device)
-            # both operands as bf16 tensors (the kernel rounds them to bf16 anyway; an fp32 side -- a block boundary -- is
-            # rounded by one elementwise pass here)
-            x16, g16 = _to16(x), _to16(gy)
-            with _wgrad_accumulate(acc, slots is not None):
-                _lib.check(lib.srgan_igemm16_wgrad(ctypes.byref(dd), _ptr(x16), _ptr(g16), _ptr(dw), _ptr(ws), nb, _stream()),
-                           "igemm16_wgrad")
-            if slots is not None:
-                dw = None
-        return dx, dw, None, None, None
-
-
-def conv2d_io(x, weight, padding=0, pad_mode=PAD_ZERO, out_bf16=True):
-    return _ConvIoFn.apply(x, weight, padding, pad_mode, bool(out_bf16))
 
 
 class _AvgPool2IoFn(Function):

@@ -1321,9 +1321,57 @@ def test_sink_slot_that_aliases_a_live_gradient_accumulates(ops):
         ops._sink_alloc = prev
 
 
+@pytest.mark.parametrize("defer", ["arena", "immediate"])
+@pytest.mark.parametrize("case", ["conv2d_io", "conv2d_act_io"])
+def test_sink_equals_autograd_for_encoder_and_discriminator_convs(ops, case, defer):
+    """The generator drives the gradient sink in test_fused_param_grads_equal_autograd_accumulation; the bf16-tensor convolutions
+    of the style encoder (ops.conv2d_io: srgan_igemm16_wgrad) and of the discriminator trunks (ops.conv2d_act_io with LeakyReLU:
+    srgan_act_bwd_io + srgan_halo16_wgrad) reach it here.  One weight applied to two inputs (one fp32, one bf16) in one backward
+    call: with the sink the second contribution is added by the weight-gradient kernel's slab sum, without it by autograd --
+    the same operands and the same single addition, so the weight gradient and both input gradients are bit-identical, with the
+    slab sums deferred to the end of the scope or immediate.  Shapes: the smallest of test_generic_conv_io_every_dtype_pair and
+    test_conv_act_io_every_dtype_pair."""
+    if case == "conv2d_io":
+        n, ci, co, h, w, k, ho, wo = 2, 128, 64, 12, 20, 3, 12, 20
+    else:
+        n, ci, co, h, w, k, ho, wo = 2, 64, 128, 16, 16, 4, 8, 8
+    wt = (rnd(co, ci, k, k, seed=52) / np.sqrt(ci * k * k)).cuda()
+    xs = [rnd(n, ci, h, w, seed=53 + j).cuda().contiguous(memory_format=torch.channels_last) for j in (0, 1)]
+    gs = [rnd(n, co, ho, wo, seed=55 + j).cuda().contiguous(memory_format=torch.channels_last) for j in (0, 1)]
+    saved = ops._NO_WGRAD_DEFER
+    ops._NO_WGRAD_DEFER = defer == "immediate"
+    ops.set_compute_dtype("bf16")
+    try:
+        out = {}
+        for fused in (True, False):
+            wd = wt.clone().requires_grad_(True)
+            x1, x2 = xs[0].clone().requires_grad_(True), xs[1].to(torch.bfloat16).requires_grad_(True)
+            ops.invalidate_packed()
+            with ops.pack_cache():
+                if case == "conv2d_io":         # (asserted, not skipped: the fp32-tensor path must not stand in for this one)
+                    assert ops.conv_io_applicable(n, ci, h, w, wd, 1, ops.PAD_ZERO)
+                    y1, y2 = (ops.conv2d_io(x, wd, 1, ops.PAD_ZERO, True) for x in (x1, x2))
+                else:
+                    assert ops.conv_act_io_applicable(n, ci, h, w, wd, ops.ACT_LRELU)
+                    y1, y2 = (ops.conv2d_act_io(x, wd, ops.ACT_LRELU, 0.01, True) for x in (x1, x2))
+                assert y1.dtype == y2.dtype == torch.bfloat16
+                loss = (y1.float() * gs[0]).sum() + (y2.float() * gs[1]).sum()
+                with ops.fused_param_grads(fused):
+                    loss.backward()
+                    # the sink took the weight (its gradient is bound when the scope closes), autograd did when it is off
+                    assert (wd.grad is None and id(wd) in ops._grad_sink) if fused else wd.grad is not None
+            out[fused] = (wd.grad, x1.grad, x2.grad)
+    finally:
+        ops._NO_WGRAD_DEFER = saved
+        ops.set_compute_dtype("fp32")
+        ops.invalidate_packed()
+    for name, a, b in zip(("weight", "x1", "x2"), out[True], out[False]):
+        assert a is not None and a.dtype == b.dtype and torch.equal(a, b), name
+
+
 def test_encoder_bf16_activation_storage_vs_fp32_tensors(ops):
     """Round 5: in the bf16 mode the tensors inside the style encoder's blocks (norm -> conv -> norm -> conv -> pool) live in
-    HBM as bf16 (ops.py "16-bit activations around the generic convolutions").  The full-width encoder on 64 x 64 images (30 /
+    HBM as bf16 (ops.py "bf16 activation storage outside the residual trunk").  The full-width encoder on 64 x 64 images (30 /
     15 / 7 / 3-pixel maps: the first three blocks are served, the 3 x 3 map's reflect convolutions too) runs forward + backward
     with the storage on and off; both are bf16-mode results, so they are held to each other and, for scale, to the fp32-tensor
     chain's own distance from the exact-fp32 mode and to the exact-fp32 mode with the operands rounded to bf16 once."""
