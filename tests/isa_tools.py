@@ -62,9 +62,10 @@ def _with_file(elf, fn):
 
 
 def kernel_descriptors(lib_path):
-    """[{name, lds, scratch, vgpr, sgpr, agpr, spill_vgpr, spill_sgpr, max_wg, kernarg, dynamic_stack}] over all code objects."""
+    """[{name, object, lds, scratch, vgpr, sgpr, agpr, spill_vgpr, spill_sgpr, max_wg, kernarg, dynamic_stack}] over all code objects;
+    `object` is the index of the code object (one per translation unit, in link order) that holds the kernel."""
     ks = []
-    for _, elf in code_objects(lib_path):
+    for obj, elf in code_objects(lib_path):
         txt = _with_file(elf, lambda p: subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", p], capture_output=True,
                                                        text=True, check=True).stdout)
         for block in re.split(r"\n\s*- \.agpr_count:", "\n" + txt)[1:]:
@@ -76,7 +77,7 @@ def kernel_descriptors(lib_path):
                 v = m.group(1).strip("'\"")
                 return conv(v) if conv is not int else int(v, 0)
             ks.append({
-                "name": g("name", "", str), "lds": g("group_segment_fixed_size"), "scratch": g("private_segment_fixed_size"),
+                "name": g("name", "", str), "object": obj, "lds": g("group_segment_fixed_size"), "scratch": g("private_segment_fixed_size"),
                 "vgpr": g("vgpr_count"), "sgpr": g("sgpr_count"), "agpr": g("agpr_count"),
                 "spill_vgpr": g("vgpr_spill_count"), "spill_sgpr": g("sgpr_spill_count"),
                 "max_wg": g("max_flat_workgroup_size"), "kernarg": g("kernarg_segment_size"),

@@ -33,78 +33,10 @@ def rnd(*shape, seed=0):
     return torch.randn(*shape, generator=g)
 
 
-CONV_CASES = [
-    # N, I, H, W, O, k, s, p, reflect, bias
-    (2, 3, 20, 20, 8, 7, 1, 3, False, False),     # G first layer shape class (Cin=3)
-    (2, 64, 16, 16, 128, 4, 2, 1, False, False),  # k4 s2 down conv (vector path)
-    (2, 32, 12, 12, 64, 3, 1, 1, False, False),   # 3x3 residual conv class
-    (1, 256, 8, 8, 256, 3, 1, 1, False, False),   # exact G res conv channels
-    (2, 64, 14, 14, 3, 7, 1, 3, False, False),    # G last layer (Cout=3)
-    (2, 3, 32, 32, 64, 4, 2, 1, False, False),    # D first layer
-    (3, 128, 8, 8, 1, 4, 1, 1, False, True),      # D last_layer (Cout=1, bias)
-    (3, 64, 8, 8, 4, 8, 1, 0, False, True),       # D classification head (valid 8x8)
-    (2, 3, 33, 33, 16, 7, 2, 1, False, True),     # E first layer (k7 s2 p1, odd sizes)
-    (2, 32, 9, 9, 64, 3, 1, 1, True, False),      # E reflect conv (vector path)
-    (2, 4, 7, 7, 8, 3, 1, 1, True, False),        # reflect, generic-channel path
-    (2, 8, 3, 3, 16, 3, 1, 1, True, False),       # reflect on a 3x3 map (both mirrors hit row 1)
-    (2, 32, 6, 6, 64, 1, 1, 0, False, True),      # 1x1 shortcut with bias
-    (1, 16, 10, 10, 32, 4, 2, 1, False, False),   # generic channels, stride 2
-    (2, 160, 6, 6, 96, 3, 1, 1, False, False),    # non power-of-two channels (vector path, N mask)
-    (2, 64, 64, 64, 3, 7, 1, 3, False, False),    # narrow-output direct kernels (G RGB head), exact tiles
-    (2, 32, 67, 45, 1, 4, 1, 1, False, True),     # narrow-output, ragged tiles, Cout=1 + bias
-    (3, 16, 40, 72, 4, 3, 1, 1, False, True),     # narrow-output, Cout=4, one channel chunk
-    (4, 128, 48, 48, 256, 3, 1, 1, False, False), # 128x128 block tiles on both GEMM kernels, split-K > 1
-    (8, 64, 64, 64, 64, 4, 2, 1, False, False),   # 128x64 tiles, many M tiles
-    (4, 64, 32, 32, 128, 3, 1, 1, False, False),  # row-aligned weight-gradient path (Wo % 32 == 0), zero pad
-    (2, 32, 32, 64, 64, 3, 1, 1, True, False),    # row-aligned weight-gradient path with reflect padding
-    (2, 128, 64, 64, 128, 4, 2, 1, False, False), # row-aligned path, stride 2, 128x128 tiles, several splits
-    (32, 256, 16, 16, 256, 3, 1, 1, False, False),# 8-wave 256x128 forward / dgrad tiles
-    (3, 48, 7, 11, 40, 3, 1, 1, False, True),     # Winograd path: odd sizes, ragged tile / channel blocks, bias
-    (2, 48, 5, 4, 72, 3, 1, 1, True, True),       # Winograd path: reflect padding, bias, 2 output-channel blocks
-    (5, 64, 32, 32, 64, 3, 1, 1, False, False),   # Winograd path: tiles not a multiple of 64 per image boundary
-    (8, 64, 18, 14, 128, 3, 1, 1, False, True),   # Winograd weight gradient: 63 tile positions (ragged last group), bias
-    (4, 128, 17, 9, 128, 3, 1, 1, True, False),   # Winograd weight gradient: odd sizes (half tiles), reflect padding
-    (16, 256, 16, 16, 128, 3, 1, 1, False, False),# Winograd weight gradient: several groups per split
-    (8, 128, 40, 44, 128, 4, 2, 1, False, True),  # F(3x3,2x2) Winograd of a 4x4 stride-2 layer: fwd and input gradient, ragged 3x3 tiles
-    (48, 128, 58, 62, 128, 4, 2, 1, False, True), # same + its Winograd weight gradient (needs >= 192 workgroups, >= 48 chunks), ragged tiles
-    (32, 64, 32, 32, 64, 4, 2, 1, False, False),  # same, one cout tile, many images per tile-position group
-    (64, 64, 64, 64, 128, 4, 2, 1, False, False), # D trunk at batch 64: Winograd weight gradient split over groups AND images (16 x 2)
-    (50, 128, 32, 32, 256, 4, 2, 1, False, False),# same: 5 groups x 8 batch ranges, ragged last range (50 = 7 x 7 + 1)
-    (2, 3, 24, 70, 64, 7, 1, 3, False, False),    # RGB 7x7 layer: input gradient through the narrow-output kernel (flipped filter)
-    (2, 3, 12, 13, 32, 5, 1, 2, False, True),     # same route, generic narrow kernel (5x5), bias
-    (2, 64, 20, 72, 3, 7, 1, 3, False, True),     # RGB head through the 7x1 row convolution + shift-add, bias, ragged rows
-    (32, 64, 32, 32, 128, 3, 1, 1, False, True),  # F(4x4,3x3) Winograd by default dispatch (128 workgroups), bias
-    (3, 64, 8, 12, 96, 3, 1, 1, False, True),     # F(4x4,3x3) when forced: 18 tiles (ragged block), 8 chunks, 3 channel blocks
-    (2, 3, 40, 33, 128, 7, 1, 3, False, True),    # RGB-input 7x7 layer on the MFMA (LDS halo): ragged tiles, 2 channel blocks, bias
-    (9, 3, 128, 128, 64, 7, 1, 3, False, False),  # RGB-input layer: MFMA weight gradient, 288 pixel tiles on 256 persistent workgroups
-    (3, 64, 32, 64, 3, 7, 1, 3, False, False),    # RGB-output layer: MFMA weight gradient (swapped roles, flipped taps), 12 tiles
-    (2, 3, 32, 40, 64, 7, 2, 1, False, True),     # E first layer at even sizes: input gradient as four stride-1 phase convs (3 / 4 taps)
-    (3, 3, 33, 31, 32, 7, 2, 1, False, False),    # same, odd sizes (phase images of different heights / widths)
-    (2, 4, 18, 22, 48, 6, 2, 2, False, False),    # same route: 4 input channels, 6x6 taps, pad 2
-    (2, 3, 16, 16, 16, 5, 2, 0, False, False),    # same route: odd kernel, no padding
-    (2, 256, 32, 32, 256, 3, 1, 1, False, False), # residual-trunk layer at full width (bf16 mode: LDS-resident patch kernel, C = 256)
-    (1, 128, 8, 64, 128, 3, 1, 1, False, True),   # same kernel family: C = 128, two patches per row, bias
-    (1, 256, 64, 64, 256, 3, 1, 1, False, False), # the 256x256 configuration's trunk map (64 x 64): 32 patches of one image
-    (2, 64, 16, 64, 128, 4, 2, 1, False, False),  # 64 -> 128 down conv on an 8 x 32 output map (bf16 mode: input gradient on the transposed patch kernel)
-    (1, 128, 8, 64, 256, 4, 2, 1, False, False),  # 128 -> 256 down conv, one output patch (same kernel, C = 256 reduce channels)
-    (3, 64, 64, 128, 128, 4, 2, 1, False, True),  # same layer class on a wider map: 8 x 2 patches per image, bias
-    (2, 64, 40, 70, 3, 7, 1, 3, False, True),     # round 3: RGB head on the 4x4x1 MFMA (direct, LDS halo): ragged 32 x 64 tiles, bias
-    (3, 3, 128, 128, 64, 7, 1, 3, False, False),  # RGB input layer at full size: its input gradient on the same kernel (flipped, transposed filter)
-    (2, 32, 64, 96, 3, 7, 1, 3, False, False),    # same kernel, 32 reduce channels (8 channel quads), 2 column tiles
-    (4, 64, 62, 62, 128, 3, 1, 1, True, False),   # the encoder's own shapes (round 3): E.layers.0.cmp, 62 x 62, reflect padding
-    (4, 128, 31, 31, 128, 3, 1, 1, True, True),   # E.layers.1 on 31 x 31, reflect, bias
-    (8, 64, 30, 22, 64, 3, 1, 1, False, True),    # even but not multiple-of-4 map, zero padding, bias
-    (6, 32, 15, 15, 64, 3, 1, 1, True, False),    # E.layers.2 map size, reflect
-    (2, 96, 13, 18, 32, 3, 1, 1, True, True),     # odd sizes in both directions, 3 channel groups, one cout block, bias
-    (16, 64, 66, 66, 64, 3, 1, 1, True, False),   # bf16 mode: 545 pixel tiles of igemm16_kernel on <= 512 persistent workgroups (reflect, 64 couts)
-    (9, 256, 64, 16, 64, 4, 2, 1, False, False),  # round 5: 256 input channels keep the strided 4x4 / stride-2 form OFF F(4x4,2x2) (1024 reduce terms: 2.07e-5 there); its input gradient (64 reduce channels) takes it
-    (4, 128, 32, 48, 192, 4, 2, 1, False, True),  # round 5: F(4x4,2x2) both directions, 3 channel blocks forward, 24 tiles per image (ragged 32-tile blocks), bias
-    (3, 3, 128, 128, 64, 4, 2, 1, False, False),  # round 6: D's first layer at full size on the LDS-halo MFMA kernel, stride 2 (rgbin_conv_kernel<4, 4, 3, 2>)
-    (2, 3, 70, 90, 128, 4, 2, 1, False, True),    # same kernel: ragged 16 x 32 output tiles (35 x 45 map), two channel blocks, bias
-    (3, 3, 128, 128, 64, 7, 2, 1, False, True),   # round 6: E's first layer at full size (7x7 / stride 2 / pad 1 -> 62 x 62), bias (rgbin_conv_kernel<7, 7, 3, 2>)
-    (2, 3, 71, 77, 64, 7, 2, 1, False, False),    # same kernel, odd sizes (33 x 36 map)
-    (40, 64, 16, 16, 64, 4, 2, 1, False, False),  # round 5: F(4x4,2x2) transposed form on 160 tiles x 4 phases = 20 items over persistent workgroups
-]
+# the case tables, what each case is there to launch, and the seeded generators live in tests/conv_common.py (pinned against the
+# library's real launches by tests/test_conv_refs_cpu.py)
+from tests import conv_common as cc                                          # noqa: E402
+from tests.conv_common import CONV_CASES, _random_conv_cases, _random_bf16_conv_cases      # noqa: E402,F401
 
 
 @pytest.fixture(params=["default-dispatch", "winograd-forced"])
@@ -145,26 +77,7 @@ def test_conv2d_fwd_bwd(ops, case, dispatch):
         close(bd.grad, b.grad, 5e-5)
 
 
-def _random_conv_cases(n_cases, seed):
-    """Seeded random layer geometries across every dispatch family (narrow / RGB / stride-2 phases / split-K / Winograd / GEMM)."""
-    rng = np.random.RandomState(seed)
-    cases = []
-    while len(cases) < n_cases:
-        k = int(rng.choice([1, 3, 3, 4, 4, 5, 7]))
-        s_ = int(rng.choice([1, 1, 2]))
-        i = int(rng.choice([3, 4, 16, 32, 48, 64, 96, 128, 256]))
-        o = int(rng.choice([1, 3, 4, 16, 32, 64, 96, 128, 512]))
-        h, w = int(rng.randint(max(k, 3), 41)), int(rng.randint(max(k, 3), 41))
-        p_ = int(rng.randint(0, k // 2 + 1))
-        reflect = bool(s_ == 1 and 0 < p_ < min(h, w) and k == 3 and rng.rand() < 0.4)
-        n = int(rng.randint(1, 7))
-        if (h + 2 * p_ - k) // s_ + 1 < 1 or (w + 2 * p_ - k) // s_ + 1 < 1 or n * i * h * w > 3_000_000:
-            continue
-        cases.append((n, i, h, w, o, k, s_, p_, reflect, bool(rng.rand() < 0.5)))
-    return cases
-
-
-@pytest.mark.parametrize("case", _random_conv_cases(48, seed=20260410))
+@pytest.mark.parametrize("case", cc.RANDOM_CASES)
 def test_conv2d_random_geometries(ops, case, dispatch):
     """The same check as test_conv2d_fwd_bwd on seeded random geometries, inside a packed-weight scope (the trainer's mode: packed
     operands, split-K slabs, kept V images) -- corners of the dispatch that the hand-picked cases may miss."""
@@ -190,8 +103,7 @@ def test_conv2d_random_geometries(ops, case, dispatch):
         close(bd.grad, b.grad, 5e-5)
 
 
-@pytest.mark.parametrize("case", [(32, 64, 32, 32, 128, True), (3, 64, 8, 12, 96, True), (5, 128, 16, 16, 64, False),
-                                  (2, 256, 32, 32, 256, False)])
+@pytest.mark.parametrize("case", cc.F43_CASES)
 def test_conv2d_f43_weight_gradient_from_kept_image(ops, case, dispatch):
     """Inside a pack-cache scope (the trainer's mode) the forward of an F(4x4,3x3) layer keeps its transformed input and the
     weight gradient is computed from it (srgan_conv2d_wgrad_v): ragged tile blocks, several splits, bias."""
@@ -218,7 +130,7 @@ def test_conv2d_f43_weight_gradient_from_kept_image(ops, case, dispatch):
         close(bd.grad, b.grad, 5e-5)
 
 
-@pytest.mark.parametrize("case", [(32, 64, 32, 32, 64), (3, 64, 8, 12, 64), (2, 16, 9, 7, 16), (2, 256, 32, 32, 256)])
+@pytest.mark.parametrize("case", cc.SKIP_CASES)
 @pytest.mark.parametrize("packed", [True, False])
 def test_conv2d_skip_gradient_rides_in_the_dgrad_epilogue(ops, case, packed, dispatch):
     """conv2d_skip returns (conv(x), x); the gradient of the second result (the residual connection of SingleResidualBlock,
@@ -250,7 +162,7 @@ def test_conv2d_skip_gradient_rides_in_the_dgrad_epilogue(ops, case, packed, dis
     close(xe.grad, gs)
 
 
-@pytest.mark.parametrize("n,c,o,affine", [(32, 256, 256, True), (4, 64, 64, True), (3, 64, 96, False)])
+@pytest.mark.parametrize("n,c,o,affine", cc.NORM_ACT_CONV_CASES)
 def test_instance_norm_act_conv_equals_the_unfused_chain(ops, n, c, o, affine):
     """instance_norm_act_conv (norm + ReLU written straight as the F(4x4,3x3) V image, multiply, weight gradient from V) against
     the chain it replaces on the HIP path and against PyTorch-CPU."""
@@ -302,7 +214,7 @@ def test_instance_norm_act_conv_equals_the_unfused_chain(ops, n, c, o, affine):
         close(res["fused"][4], shr.grad, 2e-4)
 
 
-@pytest.mark.parametrize("n,c", [(32, 256), (4, 64), (3, 128)])
+@pytest.mark.parametrize("n,c", cc.RESBLOCK_CASES)
 def test_residual_block_fused_node_vs_chain_and_cpu(ops, n, c):
     """ops.residual_block (one autograd node: V images in the forward, norm backwards writing the input-gradient / weight-gradient
     transforms, skip gradient in the epilogue) against the chain of separate ops on the HIP path and against PyTorch-CPU:
@@ -351,7 +263,7 @@ def test_residual_block_fused_node_vs_chain_and_cpu(ops, n, c):
         close_grad(a, b.grad, 3e-4, what=name)
 
 
-@pytest.mark.parametrize("n,c,hw", [(32, 256, 32), (64, 64, 32), (32, 128, 32), (8, 256, 64)])
+@pytest.mark.parametrize("n,c,hw", cc.RESBLOCK_BF16_CASES)
 def test_residual_block_bf16_storage(ops, n, c, hw):
     """bf16 mode: the residual block as one node with bf16 INTERMEDIATES in HBM (ops._ResBlockBf16Fn: conv outputs, normalised
     activation, conv-output gradients stored as bf16; residual stream, statistics, weight gradients fp32) against the unfused
@@ -491,7 +403,7 @@ def _bf16_round(t):
 
 
 # layers the bf16 kernels serve: vector-gather implicit GEMM (Cin % 32 == 0, Cout >= 32); RGB / 1-channel heads stay fp32
-@pytest.mark.parametrize("case", [c for c in CONV_CASES if c[1] % 32 == 0 and c[4] >= 32 and c[0] * c[2] * c[3] <= 70000])
+@pytest.mark.parametrize("case", cc.BF16_MODE_CASES)
 def test_conv2d_bf16_compute_mode(ops, case):
     """bf16 MFMA mode (BASELINE configs [2]-[4]): forward, input gradient and weight gradient multiply bf16-rounded operands
     (x * w, dy * w, dy * x) with fp32 accumulation, so each equals the fp32 convolution of the bf16-ROUNDED operands up to
@@ -529,27 +441,7 @@ def test_conv2d_bf16_compute_mode(ops, case):
         ops.set_compute_dtype("fp32")
 
 
-def _random_bf16_conv_cases(n_cases, seed):
-    """Seeded random geometries of the layers the bf16 kernels serve (Cin a multiple of 32, Cout >= 32): patch kernels, the
-    64-deep-K implicit GEMM (Cin % 64 == 0: ragged pixel / channel tiles, stride-2 phases, reflect, 1x1, split-K) and the rest."""
-    rng = np.random.RandomState(seed)
-    cases = []
-    while len(cases) < n_cases:
-        k = int(rng.choice([1, 3, 3, 4, 4]))
-        s_ = int(rng.choice([1, 1, 2]))
-        i = int(rng.choice([32, 64, 64, 96, 128, 128, 192, 256]))
-        o = int(rng.choice([32, 64, 96, 128, 160, 256, 512]))
-        h, w = int(rng.randint(max(k, 3), 41)), int(rng.randint(max(k, 3), 41))
-        p_ = int(rng.randint(0, k // 2 + 1))
-        reflect = bool(s_ == 1 and 0 < p_ < min(h, w) and k == 3 and rng.rand() < 0.4)
-        n = int(rng.randint(1, 9))
-        if (h + 2 * p_ - k) // s_ + 1 < 1 or (w + 2 * p_ - k) // s_ + 1 < 1 or n * i * h * w > 3_000_000:
-            continue
-        cases.append((n, i, h, w, o, k, s_, p_, reflect, bool(rng.rand() < 0.5)))
-    return cases
-
-
-@pytest.mark.parametrize("case", _random_bf16_conv_cases(32, seed=20261004))
+@pytest.mark.parametrize("case", cc.RANDOM_BF16_CASES)
 def test_conv2d_bf16_random_geometries(ops, case):
     """test_conv2d_bf16_compute_mode's check on seeded random geometries inside a packed-weight scope (the trainer's mode: bf16
     packed operands of igemm16_kernel, split-K slabs, persistent tile loop)."""
@@ -591,7 +483,7 @@ def test_conv2d_bf16_random_geometries(ops, case):
         ops.invalidate_packed()
 
 
-@pytest.mark.parametrize("case", [(3, 64, 8, 32, 64), (2, 256, 32, 32, 256), (1, 128, 12, 64, 128)])
+@pytest.mark.parametrize("case", cc.SKIP_BF16_CASES)
 def test_conv2d_skip_bf16_mode(ops, case):
     """bf16 mode on the residual-trunk shapes: the skip path's gradient is added in the epilogue of the LDS-resident-patch kernel
     (conv_halo16.hip) -- same bf16-rounded-operand references as test_conv2d_bf16_compute_mode, plus the fp32 skip gradient."""
@@ -1131,7 +1023,7 @@ def test_multi_pack_launch_equals_single_pack_implicit_gemm(ops, o, i, k, s, p):
         ops.invalidate_packed()
 
 
-@pytest.mark.parametrize("n,c0,c1,c2,hw,packed", [(8, 64, 128, 256, 64, True), (2, 8, 16, 24, 16, True), (2, 32, 64, 64, 32, False)])
+@pytest.mark.parametrize("n,c0,c1,c2,hw,packed", cc.LRELU_CHAIN_CASES)
 def test_leaky_relu_backward_in_the_consumers_input_gradient(ops, n, c0, c1, c2, hw, packed):
     """conv(4x4, s2) + LeakyReLU(0.2) -> conv(4x4, s2): the first layer is told that its activation's backward is done by its
     consumer (``act_bwd_by_consumer``), the second one multiplies its input gradient by LeakyReLU'(its input)
@@ -1445,7 +1337,7 @@ def test_stride2_io_functions_every_dtype_pair(ops, in16, out16):
     forward and failed in backward.  All four, both functions, forward + input gradient + weight gradient, against the fp32
     convolution of the bf16-rounded operands (a bf16 result is compared after the same rounding of the reference)."""
     torch.set_num_threads(16)
-    n, ci, co, h, w = 2, 64, 128, 16, 64
+    n, ci, co, h, w = cc.STRIDE2_IO_SHAPE
     x = rnd(n, ci, h, w, seed=21)
     wt = rnd(co, ci, 4, 4, seed=22) / np.sqrt(ci * 16)
     xt = rnd(n, co, h // 2, w // 2, seed=23)                   # input of the transposed conv (weight viewed [Cin = co][Cout = ci])
@@ -1488,8 +1380,7 @@ def test_stride2_io_functions_every_dtype_pair(ops, in16, out16):
 
 @pytest.mark.parametrize("in16", [False, True])
 @pytest.mark.parametrize("out16", [False, True])
-@pytest.mark.parametrize("shape", [(2, 64, 128, 64, 64), (3, 128, 256, 32, 32), (4, 256, 512, 16, 16), (2, 64, 128, 16, 16),
-                                   (2, 512, 512, 16, 16)])
+@pytest.mark.parametrize("shape", cc.CONV_ACT_IO_SHAPES)
 def test_conv_act_io_every_dtype_pair(ops, shape, in16, out16):
     """Round 6 (VERDICT r5 item 1 iii): the discriminator trunks' conv 4x4 / stride 2 / pad 1 (no bias) + LeakyReLU(0.01) layers
     (pyfiles/model.py:302-309; d1: 64 -> 128 @ 64, 128 -> 256 @ 32, 256 -> 512 @ 16, at 256 x 256 also 512 -> 512; d2: 64 -> 128
@@ -1538,7 +1429,7 @@ def test_conv_act_io_every_dtype_pair(ops, shape, in16, out16):
 
 @pytest.mark.parametrize("wide16", [False, True])
 @pytest.mark.parametrize("layer", ["in", "out"])
-@pytest.mark.parametrize("n,h,w", [(2, 32, 64), (3, 80, 96)])
+@pytest.mark.parametrize("n,h,w", cc.RGB_IO_SHAPES)
 def test_rgb_layers_with_a_bf16_64_channel_side(ops, n, h, w, layer, wide16):
     """Round 6: the generator's 7x7 / pad-3 RGB layers (pyfiles/model.py:212, 232) through ops.conv2d_act_io with their 64-channel
     side in bf16 (the 3-channel side is always fp32): input layer = rgbin16_conv_kernel<OUT16> forward, rgbout16_conv_kernel<IN16>
@@ -1640,16 +1531,7 @@ def test_discriminator_bf16_activation_storage_vs_fp32_tensors(ops):
 
 @pytest.mark.parametrize("in16", [False, True])
 @pytest.mark.parametrize("out16", [False, True])
-@pytest.mark.parametrize("shape", [(2, 64, 128, 30, 30, "reflect"), (3, 128, 128, 15, 15, "reflect"), (4, 256, 512, 7, 7, "reflect"),
-                                   (2, 128, 64, 12, 20, "zeros"),
-                                   # round 6: the same Functions with the encoder's large-map layers on halo16e_kernel (the
-                                   # dispatch threshold switched off so that these small batches take it): every (Cin, Cout) it
-                                   # is instantiated for, ragged patches in both directions, reflect (input gradient = padded
-                                   # gradient + fold) and zero padding (input gradient straight into the tensor)
-                                   (2, 64, 64, 30, 30, "reflect", "halo"), (2, 64, 128, 62, 62, "reflect", "halo"),
-                                   (3, 128, 128, 31, 31, "reflect", "halo"), (2, 128, 256, 31, 31, "reflect", "halo"),
-                                   (2, 64, 128, 20, 40, "zeros", "halo"), (1, 128, 128, 9, 33, "zeros", "halo"),
-                                   (2, 128, 256, 8, 64, "zeros", "halo"), (1, 64, 64, 33, 5, "reflect", "halo")])
+@pytest.mark.parametrize("shape", cc.GENERIC_IO_SHAPES)
 def test_generic_conv_io_every_dtype_pair(ops, shape, in16, out16):
     """Round 5: the 3x3 stride-1 layers of the style encoder (reflect-padded, 62 / 31 / 15 / 7-pixel maps; model.py:413-437) with
     bf16 tensors on either side in the bf16 mode (igemm16_kernel<IN16, OUT16>, its split-K sum, the reflect fold, wgrad_kernel
@@ -1724,7 +1606,7 @@ def test_avgpool2_io_every_dtype_pair(ops, in16, out16):
     assert torch.equal(xd.grad.float().cpu(), ref_g)
 
 
-@pytest.mark.parametrize("n,hh,ww", [(2, 32, 64), (5, 64, 416)])
+@pytest.mark.parametrize("n,hh,ww", cc.RGB_BF16_SHAPES)
 def test_rgb_input_form_bf16_compute_mode(ops, n, hh, ww):
     """Round 4: in the bf16 mode the 3 -> 64 channel 7x7 form -- the generator's RGB input layer forward and the input gradient
     of its RGB output layer -- runs on rgbin16_conv_kernel (bf16 MFMA, halo with 4 channels per pixel) and the 64 -> 3 head's
