@@ -541,6 +541,28 @@ int srgan_spectral_refresh(const void* table, const void* plan, int iterate, int
                            size_t ws_bytes, void* stream);
 int srgan_spectral_project(const void* table, const void* plan, const void* grads, void* ws, size_t ws_bytes, void* stream);
 
+/* Differentiable augmentation (DiffAugment: Zhao et al., 2020) of the images the discriminator reads.  Extension, no counterpart
+ * in the reference; fp32 NHWC-dense images with C = 3 in both compute modes.  Table layout: one row of 8 floats per sample,
+ * [b, s, a, ty, tx, cy, cx, 0] -- brightness offset, saturation and contrast factors, then the translation and the cutout
+ * centre as exact integers stored as floats; the eighth float is not read.  flags: colour 1, translation 2, cutout 4 (a group
+ * that is off is not read from the table and costs no arithmetic); cut_h x cut_w is the cutout window.  Per sample, in this order:
+ * x1 = x + b; x2 = (x1 - m) s + m with m the pixel's channel mean; x3 = (x2 - M) a + M with M = mean(x) + b; x4[i][j] =
+ * x3[i + ty][j + tx] or 0 outside the image; y = x4 with rows [cy - cut_h / 2, cy - cut_h / 2 + cut_h) x columns [cx - cut_w / 2,
+ * cx - cut_w / 2 + cut_w) zeroed.  srgan_diffaugment_fwd writes the n0 + n1 rows of y from two sources (x1 = NULL, n1 = 0 for
+ * one); table row r belongs to row r of y.  srgan_diffaugment_bwd writes gx from gy and the same table: with g' = gy zeroed in
+ * the window and moved back, gx[c] = a s g'[c] + a (1 - s) / 3 * sum_c g' + (1 - a) / (3 H W) * sum g'.  Two launches each with
+ * colour on (per-sample partial sums into the workspace of srgan_diffaugment_workspace(n, h, w) bytes, then one gather pass),
+ * one without; no atomics and a fixed summation order, so a sample's result depends neither on N nor on its position; with
+ * colour off y and gx are copies or zeros bit for bit.  -1 with srgan_last_error() before any launch: C != 3, a NULL pointer
+ * (the workspace only with colour on), n <= 0, an unknown flag bit, a workspace too small. */
+size_t srgan_diffaugment_workspace(int n, int h, int w);
+/* table: (n0 + n1) rows of 8 floats [b, s, a, ty, tx, cy, cx, 0], row r for row r of y */
+int srgan_diffaugment_fwd(const float* x0, int n0, const float* x1, int n1, const float* table, float* y, int c, int h, int w,
+                          int flags, int cut_h, int cut_w, void* ws, size_t ws_bytes, void* stream);
+/* table: the n rows of 8 floats [b, s, a, ty, tx, cy, cx, 0] the forward of these samples read */
+int srgan_diffaugment_bwd(const float* gy, const float* table, float* gx, int n, int c, int h, int w, int flags, int cut_h,
+                          int cut_w, void* ws, size_t ws_bytes, void* stream);
+
 /* Small host -> device upload (pointer tables: <= 1 MiB, multiple of 4 bytes) carried in kernel arguments: nothing to keep
  * alive on the host after the call returns, and a captured hipGraph stores the bytes in its node instead of re-reading a host
  * address at replay (no reference counterpart; plumbing of the multi-tensor ops above). */

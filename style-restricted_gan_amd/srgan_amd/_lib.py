@@ -191,6 +191,9 @@ SIGNATURES = {
     "srgan_spectral_workspace": (c_size_t, [P]),
     "srgan_spectral_refresh": (c_int, [P, P, c_int, c_int, c_float, P, c_size_t, P]),
     "srgan_spectral_project": (c_int, [P, P, P, P, c_size_t, P]),
+    "srgan_diffaugment_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "srgan_diffaugment_fwd": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    "srgan_diffaugment_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     "srgan_upload_small": (c_int, [P, P, c_size_t, P]),
     "srgan_maxpool2_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "srgan_pairwise_dist": (c_int, [P, c_int, P, c_int, c_int, P, P]),

@@ -1,0 +1,111 @@
+"""Differentiable augmentation of the discriminator's inputs (DiffAugment: Zhao et al., 2020) on the HIP path.
+
+Extension, no counterpart in the reference.  Every batch the discriminator sees -- real and fake -- goes through the same random
+colour change, translation and cutout, and the generator's gradient flows back through it; the standard remedy when D memorises a
+small training set.  The random parameters are drawn on the host from a generator THIS object owns (never the default one: the
+step's style and reparametrisation noise is the same with the feature on or off), one float32 row per sample:
+
+    [b, s, a, ty, tx, cy, cx, 0]      b = r_b - 0.5, s = 2 r_s, a = r_c + 0.5 with r ~ U[0, 1)          (colour)
+                                      ty in [-Sy, Sy], tx in [-Sx, Sx], S = int(size * translation + 0.5)  (translation)
+                                      cy in [0, H + (1 - ch % 2)), cx likewise, ch = int(H * cutout + 0.5) (cutout)
+
+and applied by ``ops.diffaugment`` (csrc/augment.hip).  A group that is off gets identity values (0, 1, 1 / 0, 0 / 0, 0) and is
+not launched.  ``SRGAN_training.enable_diffaugment`` wires it into the train step."""
+import torch
+
+from . import ops
+
+__all__ = ["DiffAugment", "GROUPS"]
+
+GROUPS = {"color": ops.AUG_COLOR, "translation": ops.AUG_TRANSLATION, "cutout": ops.AUG_CUTOUT}
+
+
+def parse_policy(policy):
+    """'color,translation,cutout' (any comma-separated subset; '' = identity) -> flag bits"""
+    if not isinstance(policy, str):
+        raise ValueError(f"DiffAugment: policy is a comma-separated string of {sorted(GROUPS)}, got {policy!r}")
+    flags = 0
+    for name in (p.strip() for p in policy.split(",")):
+        if name == "" and policy.strip() == "":
+            continue
+        if name not in GROUPS:
+            raise ValueError(f"DiffAugment: unknown policy entry {name!r} (a comma-separated subset of {sorted(GROUPS)})")
+        flags |= GROUPS[name]
+    return flags
+
+
+def _window(size, ratio):
+    return int(size * ratio + 0.5)
+
+
+class DiffAugment:
+    def __init__(self, policy="color,translation,cutout", translation=0.125, cutout=0.5, seed=None):
+        parse_policy(policy)                   # an unknown name raises here
+        self.policy = policy
+        if not (translation >= 0 and cutout >= 0):
+            raise ValueError(f"DiffAugment: translation = {translation}, cutout = {cutout} (ratios >= 0)")
+        self.translation = float(translation)
+        self.cutout = float(cutout)
+        self.generator = torch.Generator()
+        if seed is None:
+            self.generator.seed()
+        else:
+            self.generator.manual_seed(int(seed))
+        self.draw_fn = self.draw               # tests may inject callable(n, h, w) -> CPU float32 [n, 8]
+
+    @property
+    def flags(self):
+        return parse_policy(self.policy)
+
+    def cut(self, h, w):
+        """the cutout window (ch, cw) of an h x w image"""
+        return _window(h, self.cutout), _window(w, self.cutout)
+
+    def draw(self, n, h, w):
+        """One CPU float32 table [n, 8] for n images of h x w; groups that are off get identity values and draw nothing."""
+        g, flags = self.generator, self.flags
+        t = torch.zeros(n, ops.AUG_ROW, dtype=torch.float32)
+        t[:, 1:3] = 1.0
+        if flags & ops.AUG_COLOR:
+            r = torch.rand(n, 3, generator=g, dtype=torch.float32)
+            t[:, 0] = r[:, 0] - 0.5
+            t[:, 1] = r[:, 1] * 2.0
+            t[:, 2] = r[:, 2] + 0.5
+        if flags & ops.AUG_TRANSLATION:
+            sy, sx = _window(h, self.translation), _window(w, self.translation)
+            t[:, 3] = torch.randint(-sy, sy + 1, (n,), generator=g).to(torch.float32)
+            t[:, 4] = torch.randint(-sx, sx + 1, (n,), generator=g).to(torch.float32)
+        if flags & ops.AUG_CUTOUT:
+            ch, cw = self.cut(h, w)
+            t[:, 5] = torch.randint(0, h + (1 - ch % 2), (n,), generator=g).to(torch.float32)
+            t[:, 6] = torch.randint(0, w + (1 - cw % 2), (n,), generator=g).to(torch.float32)
+        return t
+
+    def apply(self, x, table):
+        """``table``: device float32 [n, 8]"""
+        flags = self.flags
+        if flags == 0:
+            return x
+        return ops.diffaugment(x, table, flags, self.cut(x.shape[2], x.shape[3]))
+
+    def __call__(self, x):
+        """Draw, copy to the device, apply: for a training loop of one's own (differentiable in x)."""
+        if self.flags == 0:
+            return x
+        n, _, h, w = x.shape
+        table = self.draw_fn(n, h, w).to(dtype=torch.float32).pin_memory().to(x.device, non_blocking=True)
+        return self.apply(x, table)
+
+    def fingerprint(self):
+        """what a recorded step bakes in: the groups launched, the window ratios, the draw source"""
+        return (id(self), self.flags, self.translation, self.cutout, id(getattr(self.draw_fn, "__func__", self.draw_fn)))
+
+    def state_dict(self):
+        return {"policy": self.policy, "translation": self.translation, "cutout": self.cutout,
+                "generator": self.generator.get_state().clone()}
+
+    def load_state_dict(self, sd):
+        parse_policy(sd["policy"])
+        self.policy = sd["policy"]
+        self.translation, self.cutout = float(sd["translation"]), float(sd["cutout"])
+        self.generator.set_state(sd["generator"])

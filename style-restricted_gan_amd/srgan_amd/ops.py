@@ -2537,3 +2537,87 @@ def spectral_project_(table_dev, plan, grads_dev, ws):
     gradient): 2 launches."""
     _lib.check(_lib.load().srgan_spectral_project(_ptr(table_dev), ctypes.byref(plan), _ptr(grads_dev), _ptr(ws), ws.numel(),
                                                   _stream()), "spectral_project")
+
+
+# ---- differentiable augmentation of the discriminator's inputs (srgan_amd.augment; extension, no counterpart in the reference) ----
+AUG_COLOR, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4
+AUG_ROW = 8                    # floats per table row: [b, s, a, ty, tx, cy, cx, 0]
+
+
+def _aug_args(what, xs, table, flags, cut):
+    """checked (sources, table, flags, (cut_h, cut_w), (n, h, w)) of one launch"""
+    xs = [to_nhwc(x) for x in xs]
+    for x in xs:
+        _require_gpu(x, what)
+        if x.shape[1] != 3 or x.shape[1:] != xs[0].shape[1:]:
+            raise _lib.SrganHipError(f"{what}: images of shape {tuple(x.shape)} (three channels, one size for all sources)")
+    n = sum(x.shape[0] for x in xs)
+    _require_gpu(table, what + " table")
+    if tuple(table.shape) != (n, AUG_ROW) or not table.is_contiguous():
+        raise _lib.SrganHipError(f"{what}: table of shape {tuple(table.shape)}, a contiguous [{n}, {AUG_ROW}] expected")
+    flags = int(flags)
+    if flags & ~7:
+        raise _lib.SrganHipError(f"{what}: flags = {flags} (colour 1, translation 2, cutout 4)")
+    return xs, table, flags, (int(cut[0]), int(cut[1])), (n, xs[0].shape[2], xs[0].shape[3])
+
+
+def _aug_workspace(lib, flags, n, h, w, device):
+    """partial sums of the colour group: (buffer or None, bytes)"""
+    if not flags & AUG_COLOR:
+        return None, 0
+    nb = lib.srgan_diffaugment_workspace(n, h, w)
+    if nb == 0:
+        _lib.check(-1, "diffaugment_workspace")
+    return workspace(device, nb), nb
+
+
+def _aug_fwd(xs, table, flags, cut, geom):
+    n, h, w = geom
+    lib = _lib.load()
+    y = nhwc_empty(n, 3, h, w, xs[0].device)
+    ws, nb = _aug_workspace(lib, flags, n, h, w, y.device)
+    x1 = xs[1] if len(xs) > 1 else None
+    _lib.check(lib.srgan_diffaugment_fwd(_ptr(xs[0]), xs[0].shape[0], _ptr(x1), x1.shape[0] if x1 is not None else 0, _ptr(table),
+                                         _ptr(y), 3, h, w, flags, cut[0], cut[1], _ptr(ws), nb, _stream()), "diffaugment_fwd")
+    return y
+
+
+class _DiffAugmentFn(Function):
+    @staticmethod
+    def forward(ctx, x, table, flags, cut):
+        xs, table, flags, cut, geom = _aug_args("diffaugment", [x], table, flags, cut)
+        ctx.save_for_backward(table)
+        ctx.aug = (flags, cut, geom)
+        return _aug_fwd(xs, table, flags, cut, geom)
+
+    @staticmethod
+    def backward(ctx, gy):
+        (table,) = ctx.saved_tensors
+        flags, cut, (n, h, w) = ctx.aug
+        gy = to_nhwc(gy)
+        lib = _lib.load()
+        gx = nhwc_empty(n, 3, h, w, gy.device)
+        ws, nb = _aug_workspace(lib, flags, n, h, w, gy.device)
+        _lib.check(lib.srgan_diffaugment_bwd(_ptr(gy), _ptr(table), _ptr(gx), n, 3, h, w, flags, cut[0], cut[1], _ptr(ws), nb,
+                                             _stream()), "diffaugment_bwd")
+        return gx, None, None, None
+
+
+def diffaugment(x, table, flags, cut):
+    """DiffAugment of a batch ``x[N, 3, H, W]``: colour, then translation, then cutout, whichever of them ``flags`` names
+    (AUG_COLOR | AUG_TRANSLATION | AUG_CUTOUT), from one device row ``[b, s, a, ty, tx, cy, cx, 0]`` of ``table[N, 8]`` per sample
+    and the cutout window ``cut = (ch, cw)``.  Differentiable in ``x`` only.  Two launches each way with colour on, one without;
+    hipGraph-capturable."""
+    return _DiffAugmentFn.apply(x, table, flags, cut)
+
+
+def diffaugment_cat(xs, table, flags, cut):
+    """``diffaugment`` of the batch ``cat_batch(xs)`` (one or two sources) written in the same pass -- the discriminator update's
+    real and fake halves.  Forward only: an input that requires grad is refused."""
+    if not 1 <= len(xs) <= 2:
+        raise _lib.SrganHipError(f"diffaugment_cat: {len(xs)} sources (one or two)")
+    if any(x.requires_grad for x in xs):
+        raise _lib.SrganHipError("diffaugment_cat: an input requires grad; this form has no backward (detach it, or use diffaugment)")
+    with torch.no_grad():
+        xs, table, flags, cut, geom = _aug_args("diffaugment_cat", list(xs), table, flags, cut)
+        return _aug_fwd(xs, table, flags, cut, geom)

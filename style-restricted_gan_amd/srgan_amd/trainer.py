@@ -27,6 +27,7 @@ import torch.nn as nn
 import torch.optim as optim
 
 from . import _lib, dp, ema, ops, spectral
+from .augment import DiffAugment
 from .losses import class_encode, criterion_kind, get_domainloss_D, get_loss_D, has_fused_kind, histogram_imitation
 from .model import SingleGenerator, _cpu_normal_like, _is_batch_stat, _is_synced, batch_stats_synced, host_to_device, per_sample
 from .optim import Adam
@@ -89,6 +90,7 @@ class SRGAN_training():
         self._ema = None               # averaged copies of G / E (enable_ema)
         self.G_ema = self.E_ema = None
         self._ema_scope = False        # inside ema_weights(): self.G / self.E are the copies
+        self.augment = None            # DiffAugment of the discriminator's inputs (enable_diffaugment)
         ref = np.asarray(ref_label)
         self._ref_is_onehot = ref.ndim == 2 and ref.shape[0] == ref.shape[1] and np.array_equal(ref, np.eye(ref.shape[0]))
         # norm_type="batch": G / E normalise with batch statistics, so batching several of the reference's calls into one is a
@@ -150,6 +152,31 @@ class SRGAN_training():
             return self._graph.next_noise()
         cpu = self.noise_fn(nb, self.ndim) if kind == "randn" else torch.FloatTensor(nb, self.ndim).normal_()
         return host_to_device(cpu, self.device)
+
+    def _aug_on(self):
+        """Does the step augment what D reads?  (an empty policy is the plain step: no draw, no launch)"""
+        return self.augment is not None and self.augment.flags != 0
+
+    def _aug_tables(self, count, nb, h, w):
+        """The next ``count`` parameter tables of the step as ONE device tensor [count * nb, 8].  Draw order of a step
+        (``_aug_draws``): per discriminator update the real rows' table, then the fake rows'; after the k updates phase 1's.  They
+        come from the augmentation's own generator, never the default one.  Graph mode: drawn up front in the same order and
+        staged; this hands out the next slice of the static buffer."""
+        if self._g_active:
+            return self._graph.next_aug(count)
+        tabs = [self.augment.draw_fn(nb, h, w).to(torch.float32) for _ in range(count)]
+        return host_to_device(tabs[0] if count == 1 else torch.cat(tabs, 0), self.device)
+
+    def _aug_draws(self):
+        """tables a step consumes: 2 per discriminator update, 1 for phase 1"""
+        return 2 * self.k + 1 if self._aug_on() else 0
+
+    def _aug(self, image):
+        """DiffAugment of one batch D is about to read (differentiable); the image itself with the feature off."""
+        if not self._aug_on():
+            return image
+        n, _, h, w = image.shape
+        return self.augment.apply(image, self._aug_tables(1, n, h, w))
 
     def _noise_kinds(self):
         """The step's noise draws in order (fused execution paths)."""
@@ -321,13 +348,20 @@ class SRGAN_training():
         if self._fused_paths():
             # real and fake halves through D as ONE batch (per-sample network: exact; 2x the rows per GEMM launch)
             B = self.source_image.shape[0]
-            outs, logits = dp.unwrap(self.D).forward_logits(ops.cat_batch([self.source_image, self.target_image.detach()]))
+            if self._aug_on():
+                # both halves augmented and concatenated in ONE pass (no gradient needed: real rows have none, fake rows are detached)
+                _, _, h, w = self.source_image.shape
+                d_in = ops.diffaugment_cat([self.source_image.detach(), self.target_image.detach()], self._aug_tables(2, B, h, w),
+                                           self.augment.flags, self.augment.cut(h, w))
+            else:
+                d_in = ops.cat_batch([self.source_image, self.target_image.detach()])
+            outs, logits = dp.unwrap(self.D).forward_logits(d_in)
             # criterion(real, 1) + class loss * lbd + criterion(fake, 0) over both scales, values and gradients: one launch
             errD, parts = ops.d_losses(outs, logits, self._label_dev("source"), B, 1., 0., self.lbd["class"], *self._kinds())
             errD_real, errD_class, errD_fake = parts[0], parts[1], parts[2]
         else:
-            errD_real, errD_class = self._d_losses(self.source_image, 1., "source", True)
-            errD_fake, _ = self._d_losses(self.target_image.detach(), 0., None, False)
+            errD_real, errD_class = self._d_losses(self._aug(self.source_image), 1., "source", True)
+            errD_fake, _ = self._d_losses(self._aug(self.target_image.detach()), 0., None, False)
             errD = errD_real + errD_class * self.lbd["class"] + errD_fake
         self._reduce_arm("D", self.optD)
         with ops.fused_param_grads(not dp.hooks_need_live_grads(), self.device):
@@ -396,14 +430,15 @@ class SRGAN_training():
             # (ops.lincomb) instead of one launch per python-level `+` / `*`
             g_terms, e_terms, rep_terms = [], [], []
             with _frozen(self._d_frozen()):                # D's weight grads would be discarded
+                d_img = self._aug(t_img)                   # (the step's last table; the generator's gradient flows back through it)
                 if fused:
-                    outs, logits = dp.unwrap(self.D).forward_logits(t_img)
+                    outs, logits = dp.unwrap(self.D).forward_logits(d_img)
                     d_total, parts = ops.d_losses(outs, logits, self._label_dev("target"), self.target_image.shape[0], 1., 0., L["class"],
                                                   *self._kinds())
                     errG_dis, errG_class = parts[0], parts[1]
                     g_terms.append((d_total, 1.0))
                 else:
-                    errG_dis, errG_class = self._d_losses(t_img, 1., "target", True)
+                    errG_dis, errG_class = self._d_losses(d_img, 1., "target", True)
                     g_terms += [(errG_dis, 1.0), (errG_class, L["class"])]
             errG_cycle = ops.l1_mean(src, recon_image, 1.0)
             g_terms.append((errG_cycle, L["cycle"]))
@@ -714,6 +749,25 @@ class SRGAN_training():
         self._ema.load_state_dict(sd)
 
     # ------------------------------------------------------------------------------------------
+    # differentiable augmentation of what D reads (extension, no counterpart in the reference; srgan_amd.augment)
+    def enable_diffaugment(self, policy="color,translation,cutout", translation=0.125, cutout=0.5, seed=None):
+        """From now on every batch the discriminator reads -- the real and the fake rows of each of the k discriminator updates and
+        phase 1's D(target_image) -- goes through DiffAugment (random colour, translation, cutout per sample; ``policy``: any
+        comma-separated subset, '' = none), and the generator's gradient flows back through it.  ``self.augment`` is the
+        ``augment.DiffAugment`` that draws the parameters: 2k + 1 tables of [B, 8] per step (per update real, then fake; then phase
+        1) from its OWN generator (``seed``), so the step's style and reparametrisation noise is what it is with the feature off.
+        2(k + 1) + 2 launches per step; captured with the step in graph mode, where the tables are staged like the noise (a
+        recording made before is dropped).  With the feature off, or an empty policy, the step is bit-identical to the plain one.
+        Data parallel: the operation is per sample, every rank draws its own tables."""
+        self.augment = DiffAugment(policy, translation, cutout, seed)
+        self._guard_changed()
+        return self
+
+    def disable_diffaugment(self):
+        self.augment = None
+        self._guard_changed()
+
+    # ------------------------------------------------------------------------------------------
     # device-side gradient guard (extension, no counterpart in the reference; srgan_amd.optim.Adam.enable_grad_guard)
     _GUARD_NETS = ("G", "D", "E")
 
@@ -818,6 +872,8 @@ class _StepGraph:
         self.key = None          # input signature the eager warm-up ran with
         self.graph = None
         self.x = self.noise = self.out = None
+        self.aug = None          # staged DiffAugment tables [2k + 1, B, 8] (None with the feature off)
+        self._aug_i = 0
         self.lab = {}
         self._onehot = {}
         self._noise_i = 0
@@ -902,6 +958,10 @@ class _StepGraph:
         # between steps); u, v, sigma and the normalised weights are device state
         sn = sg._sn() if hasattr(sg, "_sn") else None
         fp.append(sn.fingerprint() if sn is not None else None)
+        # DiffAugment of D's inputs: its launches (the groups of the policy, the cutout window), the static table buffer and the
+        # number of tables a step consumes (enabled, disabled or edited between steps); the tables themselves are staged
+        aug = getattr(sg, "augment", None)
+        fp.append(aug.fingerprint() if aug is not None else None)
         return tuple(fp)
 
     def _opt_steps(self):
@@ -911,7 +971,7 @@ class _StepGraph:
 
     def _drop(self):
         self.graph, self.key, self._keep, self._baked, self._steps = None, None, None, None, None
-        self.x = self.noise = self.out = None
+        self.x = self.noise = self.out = self.aug = None
 
     def _local_mode(self, source_image, label):
         """2: replay the recording, 1: record (the eager warm-up of this input shape has run), 0: eager."""
@@ -1009,6 +1069,14 @@ class _StepGraph:
         self._noise_i += 1
         return t
 
+    def next_aug(self, count):
+        """the next ``count`` staged tables as one [count * B, 8] view of the static buffer"""
+        t = self.aug[self._aug_i:self._aug_i + count]
+        if t.shape[0] != count:
+            raise RuntimeError(f"the step asks for more DiffAugment tables than the {self.aug.shape[0]} staged")
+        self._aug_i += count
+        return t.reshape(-1, t.shape[-1])
+
     # -- staging (outside the graph, stream-ordered before the replay) ---------------------------------------------
     def _stage(self, source_image, label):
         sg = self.sg
@@ -1023,6 +1091,14 @@ class _StepGraph:
             self.noise = torch.empty(len(kinds), nb, sg.ndim, dtype=torch.float32, device=dev)
             self.lab = {w: torch.empty(nb, dtype=torch.int64, device=dev) for w in ("source", "target")}
             self.table = torch.tensor(np.asarray(sg.ref_label), dtype=torch.float32).to(dev)
+        n_aug = sg._aug_draws()
+        if n_aug:
+            # the step's 2k + 1 tables, drawn up front in the order the eager step draws them (SRGAN_training._aug_tables)
+            _, _, h, w = x.shape
+            host_aug = torch.stack([sg.augment.draw_fn(nb, h, w).to(torch.float32) for _ in range(n_aug)]).pin_memory()
+            if self.aug is None:
+                self.aug = torch.empty(n_aug, nb, ops.AUG_ROW, dtype=torch.float32, device=dev)
+            self.aug.copy_(host_aug, non_blocking=True)
         self.x.copy_(x)
         self.noise.copy_(host_noise, non_blocking=True)
         for w in ("source", "target"):
@@ -1064,7 +1140,7 @@ class _StepGraph:
         self._last_single = g.single
         epoch0 = ops.structure_epoch()    # a buffer replaced DURING the recording (the weight-gradient arena grown
         sg._g_active = True               # between two segments) would leave earlier segments pointing at freed memory
-        self._noise_i, self._onehot = 0, {}
+        self._noise_i, self._aug_i, self._onehot = 0, 0, {}
         sg.source_image = self.x
         try:
             with g:
@@ -1077,6 +1153,8 @@ class _StepGraph:
             sg._g_active = False
         if self._noise_i != self.noise.shape[0]:
             raise RuntimeError(f"captured step consumed {self._noise_i} noise draws, staged {self.noise.shape[0]}")
+        if self._aug_i != sg._aug_draws():
+            raise RuntimeError(f"captured step consumed {self._aug_i} DiffAugment tables, staged {sg._aug_draws()}")
         if ops.structure_epoch() != epoch0:
             raise RuntimeError("a workspace the step points at was replaced while the step was being recorded "
                                "(ops.structure_epoch moved): the recording is dropped")
@@ -1105,7 +1183,7 @@ class _StepGraph:
                       + (f" (this rank: {type(err).__name__}: {err})" if err is not None else "")
                       + ("; this step runs eagerly, the next one is recorded as segments" if keep_graph_mode else "; running eagerly from here on"))
         self.graph = self._keep = self._baked = self._steps = None
-        self._noise_i, self._onehot = 0, {}
+        self._noise_i, self._aug_i, self._onehot = 0, 0, {}     # (the staged noise and DiffAugment tables are used again)
         sg.target_image = sg.recon_image = sg.c_rand = None
         sg.loss_terms = {}
         sg.__dict__.get("_label_cache", {}).clear()
@@ -1319,6 +1397,10 @@ class SingleGAN_training():
             raise NotImplementedError("SingleGAN_training: a network is marked with spectral_norm; this trainer's optimiser steps "
                                       "neither map the gradients nor run the power iteration (use SRGAN_training, or "
                                       "spectral.remove_spectral_norm(net))")
+
+    def enable_diffaugment(self, *args, **kwargs):
+        raise NotImplementedError("SingleGAN_training: DiffAugment is not wired into this trainer's discriminator passes (per-domain "
+                                  "sub-batches); use SRGAN_training.enable_diffaugment, or augment.DiffAugment in a loop of your own")
 
     def opt_sche_initialization(self, lr=[0.0001, 0.0001, 0.0001]):
         lr_G, lr_D, lr_E = lr
