@@ -563,6 +563,29 @@ int srgan_diffaugment_fwd(const float* x0, int n0, const float* x1, int n1, cons
 int srgan_diffaugment_bwd(const float* gy, const float* table, float* gx, int n, int c, int h, int w, int flags, int cut_h,
                           int cut_w, void* ws, size_t ws_bytes, void* stream);
 
+/* R1 gradient penalty on real samples (Mescheder et al., 2018), gamma / 2 * E_x |grad_x D(x)|^2, for the two-scale discriminator.
+ * Extension, no counterpart in the reference.  The convolution passes are the ordinary entry points above (srgan_amd/r1.py drives
+ * them); these are the record and the one pass in between.  Record (srgan_r1_state_bytes() = 32 bytes, device memory):
+ * {float gamma, int every, float c, float penalty, float mean_sq_norm, int updates, int n, int pad}; c = gamma * every / n.
+ * srgan_r1_state_init writes gamma, every, n, c and zeroes the rest; srgan_r1_state_set rewrites gamma, every, n and c between
+ * steps and keeps the counters (a recorded step reads them from the record).  srgan_r1_seed: h1 = the input gradient of the first
+ * scale [n, h, w, 3], h2 = that of the second scale [n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, 3] (fp32 NHWC-dense); one launch
+ * writes g = h1 + pool^T(h2) scaled, u0 = c * g (pool = the 3x3 / stride-2 / padding-1 average with count_include_pad = false:
+ * divisors 4, 6 or 9 by position), and one fp32 partial of sum g^2 per 4096 consecutive floats of a sample into `ws`
+ * (srgan_r1_workspace(n, h, w) bytes; add depth 24 per partial: 16 serial fused multiply-adds per thread, 6 butterfly levels,
+ * (w0 + w1) + (w2 + w3)); 16-byte accesses when 3 h w % 4 == 0 and h1 / u0 are 16-byte aligned, else a scalar path with the same
+ * owner and order per element (same bits).  srgan_r1_finalize: one workgroup sums the partials in double in a fixed order and
+ * writes mean_sq_norm = S / n, penalty = gamma * every / 2 * S / n, updates += 1.  No atomics: a sample's u0 and partials depend
+ * neither on n nor on its position.  -1 with srgan_last_error() before any launch: c != 3, a NULL pointer, n / h / w <= 0,
+ * gamma < 0 or not finite, every < 1, a workspace too small, u0 aliasing h1 or h2. */
+size_t srgan_r1_state_bytes(void);
+int srgan_r1_state_init(void* state, float gamma, int every, int n, void* stream);
+int srgan_r1_state_set(void* state, float gamma, int every, int n, void* stream);
+size_t srgan_r1_workspace(int n, int h, int w);
+int srgan_r1_seed(const float* h1, const float* h2, const void* state, float* u0, int n, int c, int h, int w, void* ws,
+                  size_t ws_bytes, void* stream);
+int srgan_r1_finalize(const void* ws, size_t ws_bytes, int n, int h, int w, void* state, void* stream);
+
 /* Small host -> device upload (pointer tables: <= 1 MiB, multiple of 4 bytes) carried in kernel arguments: nothing to keep
  * alive on the host after the call returns, and a captured hipGraph stores the bytes in its node instead of re-reading a host
  * address at replay (no reference counterpart; plumbing of the multi-tensor ops above). */

@@ -2621,3 +2621,59 @@ def diffaugment_cat(xs, table, flags, cut):
     with torch.no_grad():
         xs, table, flags, cut, geom = _aug_args("diffaugment_cat", list(xs), table, flags, cut)
         return _aug_fwd(xs, table, flags, cut, geom)
+
+
+# ---- R1 gradient penalty on real samples (srgan_amd.r1; extension, no counterpart in the reference) ----------------------------
+R1_CHUNK = 4096                # floats of a sample per partial sum of |g|^2
+
+
+def _r1_args(gamma, every, n):
+    return float(gamma), int(every), int(n)
+
+
+def r1_state_new(device, gamma, every, n):
+    """Device-resident record {gamma, every, c, penalty, mean_sq_norm, updates, n, pad}, c = gamma * every / n, counters at zero."""
+    lib = _lib.load()
+    st = torch.empty(lib.srgan_r1_state_bytes(), dtype=torch.uint8, device=device)
+    _lib.check(lib.srgan_r1_state_init(_ptr(st), *_r1_args(gamma, every, n), _stream()), "r1_state_init")
+    return st
+
+
+def r1_state_set(state, gamma, every, n):
+    """Rewrite gamma, every, n and c between steps; the counters stay (a recorded step reads the record)."""
+    _lib.check(_lib.load().srgan_r1_state_set(_ptr(state), *_r1_args(gamma, every, n), _stream()), "r1_state_set")
+
+
+def r1_state_read(state):
+    """The record as a dict; synchronises the current stream (the only host read of the penalty)."""
+    torch.cuda.current_stream(state.device).synchronize()
+    gamma, every, c, penalty, msn, updates, n, _ = struct.unpack("fifffiii", state.cpu().numpy().tobytes()[:32])
+    return dict(gamma=gamma, every=every, c=c, penalty=penalty, mean_sq_norm=msn, updates=updates, n=n)
+
+
+def r1_workspace_bytes(n, h, w):
+    nb = int(_lib.load().srgan_r1_workspace(int(n), int(h), int(w)))
+    if nb == 0:
+        _lib.check(-1, "r1_workspace")
+    return nb
+
+
+def r1_seed_(h1, h2, state, u0, ws):
+    """One launch: ``u0 = c * (h1 + pool^T(h2))`` and one partial of ``sum g^2`` per 4096 floats of a sample into ``ws``
+    (``h1``, ``u0``: [N, 3, H, W]; ``h2``: [N, 3, (H - 1) // 2 + 1, (W - 1) // 2 + 1]; NHWC-dense fp32).  hipGraph-capturable."""
+    for t, what in ((h1, "r1_seed h1"), (h2, "r1_seed h2"), (u0, "r1_seed u0")):
+        _require_gpu(t, what)
+        if not is_nhwc_dense(t):
+            raise _lib.SrganHipError(f"{what}: an NHWC-dense tensor expected")
+    n, c, h, w = h1.shape
+    if tuple(u0.shape) != (n, c, h, w) or tuple(h2.shape) != (n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1):
+        raise _lib.SrganHipError(f"r1_seed: h1 {tuple(h1.shape)}, h2 {tuple(h2.shape)}, u0 {tuple(u0.shape)} do not belong together")
+    _lib.check(_lib.load().srgan_r1_seed(_ptr(h1), _ptr(h2), _ptr(state), _ptr(u0), n, c, h, w, _ptr(ws),
+                                         ws.numel() * ws.element_size(), _stream()), "r1_seed")
+
+
+def r1_finalize_(ws, n, h, w, state):
+    """One workgroup: the partials of ``r1_seed_`` summed in double in a fixed order; mean_sq_norm, penalty and updates written
+    into the record.  hipGraph-capturable; nothing comes back to the host."""
+    _lib.check(_lib.load().srgan_r1_finalize(_ptr(ws), ws.numel() * ws.element_size(), int(n), int(h), int(w), _ptr(state),
+                                             _stream()), "r1_finalize")

@@ -28,6 +28,7 @@ import torch.optim as optim
 
 from . import _lib, dp, ema, ops, spectral
 from .augment import DiffAugment
+from . import r1 as _r1mod
 from .losses import class_encode, criterion_kind, get_domainloss_D, get_loss_D, has_fused_kind, histogram_imitation
 from .model import SingleGenerator, _cpu_normal_like, _is_batch_stat, _is_synced, batch_stats_synced, host_to_device, per_sample
 from .optim import Adam
@@ -91,6 +92,7 @@ class SRGAN_training():
         self.G_ema = self.E_ema = None
         self._ema_scope = False        # inside ema_weights(): self.G / self.E are the copies
         self.augment = None            # DiffAugment of the discriminator's inputs (enable_diffaugment)
+        self._r1 = None                # R1 gradient penalty on the real rows (enable_r1)
         ref = np.asarray(ref_label)
         self._ref_is_onehot = ref.ndim == 2 and ref.shape[0] == ref.shape[1] and np.array_equal(ref, np.eye(ref.shape[0]))
         # norm_type="batch": G / E normalise with batch statistics, so batching several of the reference's calls into one is a
@@ -330,11 +332,12 @@ class SRGAN_training():
         return target_image, info
 
     # ------------------------------------------------------------------------------------------
-    def update_D(self, _fake=None, _next_fake=None, _defer=False):
+    def update_D(self, _fake=None, _next_fake=None, _defer=False, _index=0):
         """One discriminator update (util_notebook.py:563-594); returns errD.
         Data parallel: ``_fake`` hands in a pre-computed translation, ``_next_fake`` is work to run UNDER this update's gradient
         all-reduce (the next translation: G does not change during the discriminator loop), ``_defer`` leaves the wait for the
-        all-reduce and the optimiser step to ``_finish_D()`` so that the caller can put more independent work in between."""
+        all-reduce and the optimiser step to ``_finish_D()`` so that the caller can put more independent work in between.
+        ``_index``: which of the step's k updates this is (the R1 penalty runs on update i iff i % every == 0)."""
         self._finish_D()
         self.D.zero_grad()
         sn = self._sn()
@@ -353,19 +356,28 @@ class SRGAN_training():
                 _, _, h, w = self.source_image.shape
                 d_in = ops.diffaugment_cat([self.source_image.detach(), self.target_image.detach()], self._aug_tables(2, B, h, w),
                                            self.augment.flags, self.augment.cut(h, w))
+                d_real = d_in[:B]                          # what D read as the real rows (the R1 penalty is taken there)
             else:
                 d_in = ops.cat_batch([self.source_image, self.target_image.detach()])
+                d_real = self.source_image
             outs, logits = dp.unwrap(self.D).forward_logits(d_in)
             # criterion(real, 1) + class loss * lbd + criterion(fake, 0) over both scales, values and gradients: one launch
             errD, parts = ops.d_losses(outs, logits, self._label_dev("source"), B, 1., 0., self.lbd["class"], *self._kinds())
             errD_real, errD_class, errD_fake = parts[0], parts[1], parts[2]
         else:
-            errD_real, errD_class = self._d_losses(self._aug(self.source_image), 1., "source", True)
+            d_real = self._aug(self.source_image)
+            errD_real, errD_class = self._d_losses(d_real, 1., "source", True)
             errD_fake, _ = self._d_losses(self._aug(self.target_image.detach()), 0., None, False)
             errD = errD_real + errD_class * self.lbd["class"] + errD_fake
         self._reduce_arm("D", self.optD)
         with ops.fused_param_grads(not dp.hooks_need_live_grads(), self.device):
             errD.backward()
+        if self._r1 is not None and _index % self._r1.every == 0:
+            # R1 on the real rows D just read: dP/dW is added to the gradients the backward left, before the optimiser step (and
+            # so before the spectral-norm projection and the gradient guard); errD is unchanged
+            self._r1_check()
+            _r1mod.r1_accumulate(dp.unwrap(self.D), d_real.detach(), self._r1)
+            self.loss_terms["errD_r1"] = self._r1.penalty()
         self._d_pending = self._reduce_start("D", self.optD) or True
         dp.launch_pending()                                         # recorded step: the all-reduces start here ...
         nxt = _next_fake() if _next_fake is not None else None      # ... and this runs under them
@@ -608,7 +620,7 @@ class SRGAN_training():
             fake = translate(0)
             for i in range(k):
                 nxt = (lambda j=i + 1: translate(j)) if i + 1 < k else None
-                out = self.update_D(_fake=fake, _next_fake=nxt, _defer=(i == k - 1))
+                out = self.update_D(_fake=fake, _next_fake=nxt, _defer=(i == k - 1), _index=i)
                 errD, fake = out if nxt is not None else (out, None)
                 if i == 0:
                     errorD = errD.detach()
@@ -634,7 +646,7 @@ class SRGAN_training():
                 fakes = [(self.G(src, torch.cat([oh, z], 1)), z) for z in noises[:-1]]
         fakes.append((self.G(src, torch.cat([oh, noises[-1]], 1)), noises[-1]))
         for i in range(k):
-            errD = self.update_D(_fake=fakes[i])
+            errD = self.update_D(_fake=fakes[i], _index=i)
             fakes[i] = None
             if i == 0:
                 errorD = errD.detach()
@@ -766,6 +778,53 @@ class SRGAN_training():
     def disable_diffaugment(self):
         self.augment = None
         self._guard_changed()
+
+    # ------------------------------------------------------------------------------------------
+    # R1 gradient penalty on the real rows (extension, no counterpart in the reference; srgan_amd.r1)
+    def _r1_check(self):
+        if dp.world_size() > 1:
+            raise NotImplementedError(f"SRGAN_training: the R1 penalty is on and the process group has {dp.world_size()} ranks; the "
+                                      "penalty's gradients are not ordered against the gradient reducer's buckets (run one "
+                                      "process, or disable_r1())")
+        _r1mod._layers(dp.unwrap(self.D))
+
+    def enable_r1(self, gamma=10.0, every=1):
+        """From now on discriminator update ``i`` of a step's k adds the gradient of the R1 penalty ``gamma_eff / 2 * mean_n
+        |grad_x S_n|^2`` (``S_n``: the patch MEAN of the two GAN heads at real row n, ``gamma_eff = gamma * every``: lazy
+        regularisation) to D's gradients iff ``i % every == 0``, between ``errD.backward()`` and the optimiser step; the gradient
+        guard and the spectral-norm projection see the penalised gradients.  ``errD`` and the returned losses are unchanged;
+        ``loss_terms["errD_r1"]`` is the penalty of the step's last penalised update (a device scalar).  With DiffAugment on the
+        penalty is taken at the AUGMENTED real rows D read in that update (same table) -- a departure from the DiffAugment
+        paper, which penalises at the raw images.  Closed form on the existing convolution kernels plus ``csrc/r1.hip``
+        (``srgan_amd.r1``), no double backward; captured with the step in graph mode (a recording made before is dropped).  Off:
+        no launch, no allocation, the step is bit-identical to the plain one.  Refused: more than one rank, the bf16 compute
+        mode (when the step runs), a discriminator other than ``SingleDiscriminator_solo_multi``, images whose H or W is not a
+        multiple of 16 (when the step runs)."""
+        state = _r1mod.R1Penalty(gamma, every)
+        self._r1 = state
+        try:
+            self._r1_check()
+        except NotImplementedError:
+            self._r1 = None
+            raise
+        self._guard_changed()
+        return self
+
+    def disable_r1(self):
+        self._r1 = None
+        self._guard_changed()
+
+    def set_r1_gamma(self, gamma):
+        """Write a new ``gamma`` into the penalty's device record, between steps; a recorded step reads it from there and stays
+        valid."""
+        if self._r1 is None:
+            raise RuntimeError("set_r1_gamma: the R1 penalty is off (enable_r1)")
+        self._r1.set_gamma(gamma)
+
+    def r1_stats(self):
+        """The penalty's device record as a dict (``gamma``, ``every``, ``c``, ``penalty``, ``mean_sq_norm``, ``updates``, ``n``), or
+        None with the feature off.  The only host look at the record: SYNCHRONISES the stream."""
+        return self._r1.stats() if self._r1 is not None else None
 
     # ------------------------------------------------------------------------------------------
     # device-side gradient guard (extension, no counterpart in the reference; srgan_amd.optim.Adam.enable_grad_guard)
@@ -962,6 +1021,9 @@ class _StepGraph:
         # number of tables a step consumes (enabled, disabled or edited between steps); the tables themselves are staged
         aug = getattr(sg, "augment", None)
         fp.append(aug.fingerprint() if aug is not None else None)
+        # the R1 penalty: its schedule (every) and launches, the record, the constant seeds and the workspace; gamma is device state
+        r1 = getattr(sg, "_r1", None)
+        fp.append(r1.fingerprint() if r1 is not None else None)
         return tuple(fp)
 
     def _opt_steps(self):
@@ -1166,6 +1228,8 @@ class _StepGraph:
             self._keep += sg._ema.graph_keepalive()
         if sg._sn() is not None:
             self._keep += sg._sn().graph_keepalive()
+        if getattr(sg, "_r1", None) is not None:
+            self._keep += sg._r1.graph_keepalive()
         self._baked = self._fingerprint()
 
     def _abandon(self, err, snap, keep_graph_mode=False):
@@ -1401,6 +1465,10 @@ class SingleGAN_training():
     def enable_diffaugment(self, *args, **kwargs):
         raise NotImplementedError("SingleGAN_training: DiffAugment is not wired into this trainer's discriminator passes (per-domain "
                                   "sub-batches); use SRGAN_training.enable_diffaugment, or augment.DiffAugment in a loop of your own")
+
+    def enable_r1(self, *args, **kwargs):
+        raise NotImplementedError("SingleGAN_training: the R1 penalty is not wired into this trainer's discriminator passes (per-domain "
+                                  "sub-batches); use SRGAN_training.enable_r1, or r1.r1_accumulate in a loop of your own")
 
     def opt_sche_initialization(self, lr=[0.0001, 0.0001, 0.0001]):
         lr_G, lr_D, lr_E = lr
