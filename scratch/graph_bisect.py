@@ -118,7 +118,7 @@ elif stage.startswith("part_"):
 
     def body():
         sg._g_active = True
-        gr._noise_i, gr._onehot = 0, {}
+        gr._rewind()
         sg.source_image = gr.x
         with ops.pack_cache(refresh_on_entry=False):
             oh = sg._onehot("target")

@@ -100,6 +100,10 @@ class DiffAugment:
         """what a recorded step bakes in: the groups launched, the window ratios, the draw source"""
         return (id(self), self.flags, self.translation, self.cutout, id(getattr(self.draw_fn, "__func__", self.draw_fn)))
 
+    def graph_keepalive(self):
+        """device buffers a recorded step points at: none (the tables are staged by the recording's owner)"""
+        return []
+
     def state_dict(self):
         return {"policy": self.policy, "translation": self.translation, "cutout": self.cutout,
                 "generator": self.generator.get_state().clone()}

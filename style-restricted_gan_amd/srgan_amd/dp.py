@@ -97,7 +97,7 @@ def unwrap(net):
     return net.module if hasattr(net, "module") and isinstance(getattr(net, "module"), nn.Module) else net
 
 
-# Segmented step recording (trainer._StepGraph under data parallelism): while a step is being RECORDED into hipGraphs the
+# Segmented step recording (step_graph._StepGraph under data parallelism): while a step is being RECORDED into hipGraphs the
 # collectives are not issued -- each one ends the graph segment being recorded, is remembered as a host callable over static
 # device buffers, and a new segment begins.  A replay launches segment, collective, segment, ...: the collectives stay the
 # plain eager RCCL calls (nothing of RCCL is captured), everything between them is one graph launch.
@@ -575,7 +575,7 @@ def comm_stream(device):
 
 
 class _Comm:
-    """A host callable between two graph segments of a recorded step (``trainer._Recording``), with a name for the trace."""
+    """A host callable between two graph segments of a recorded step (``step_graph._Recording``), with a name for the trace."""
     __slots__ = ("kind", "fn")
 
     def __init__(self, kind, fn):
@@ -663,7 +663,7 @@ def control_group():
         if dist.get_backend() == "gloo":
             _control = dist.group.WORLD
         else:
-            # (a bounded wait: a rank that reaches a vote its peers never join -- see trainer._StepGraph.accepts -- raises
+            # (a bounded wait: a rank that reaches a vote its peers never join -- see step_graph._StepGraph.accepts -- raises
             #  after this instead of sitting in it for the default half hour)
             import datetime
             with _stdout_to_stderr():

@@ -106,7 +106,17 @@ class WeightEMA:
         self.updates += 1
         ops.mark_stale(self._params)
 
-    def after_replay(self, delta):
+    # -- the host mirror of n, under the names of optim.Adam's step counters: a recording moves both without running anything
+    def host_counters(self):
+        return self.updates
+
+    def restore_host_counters(self, snap):
+        self.updates = snap
+
+    def counters_since(self, snap):
+        return self.updates - snap
+
+    def advance_host(self, delta):
         """A replayed graph ran ``delta`` updates on the device: move the host mirror and drop the copies' cached operands."""
         self.updates += delta
         ops.mark_stale(self._params)

@@ -12,6 +12,9 @@ Same constructor / method signatures and return values as the reference class
 * under ``torch.distributed`` (one process per GPU) gradients are averaged with bucketed RCCL
   all-reduce (``srgan_amd.dp``) and the batch-statistics losses see the all-gathered mu.
 
+This module chooses the launches (the step body, ``_step``, the ``enable_*`` switches, ``SingleGAN_training``); how a fixed launch
+sequence is recorded into a hipGraph and replayed (``_StepGraph``, ``_Recording``) lives in ``srgan_amd.step_graph``.
+
 Semantics kept on purpose: stale ``target_image`` graph re-used after
 ``optG.step()`` with weights read at backward time; the no-op "unrolled" restore of D; corr/hist
 nested under batch_KL; the n/(n-1) double correction with the constructor's batch size; errE returned
@@ -19,19 +22,19 @@ is the reporting sum; CPU-generator RNG order (k x randn, then normal_ x2, then 
 """
 import contextlib
 import gc
-import os
 
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.optim as optim
 
-from . import _lib, dp, ema, ops, spectral
+from . import dp, ema, ops, spectral
 from .augment import DiffAugment
 from . import r1 as _r1mod
 from .losses import class_encode, criterion_kind, get_domainloss_D, get_loss_D, has_fused_kind, histogram_imitation
-from .model import SingleGenerator, _cpu_normal_like, _is_batch_stat, _is_synced, batch_stats_synced, host_to_device, per_sample
+from .model import SingleGenerator, batch_stats_synced, host_to_device, per_sample
 from .optim import Adam
+from .step_graph import _Recording, _StepGraph, lib_prof_off  # noqa: F401  (graph mode: how the step below is recorded / replayed)
 
 __all__ = ["SRGAN_training", "SingleGAN_training"]
 
@@ -93,6 +96,9 @@ class SRGAN_training():
         self._ema_scope = False        # inside ema_weights(): self.G / self.E are the copies
         self.augment = None            # DiffAugment of the discriminator's inputs (enable_diffaugment)
         self._r1 = None                # R1 gradient penalty on the real rows (enable_r1)
+        self._label_cache = {}         # (kind, which) -> (label tensor, its device form): _cached
+        self._d_pending = None         # an update_D left its all-reduce / optimiser step to _finish_D: the reducer, or True
+        self._sn_cache = (None, None)  # (key, spectral controller or None): _sn
         ref = np.asarray(ref_label)
         self._ref_is_onehot = ref.ndim == 2 and ref.shape[0] == ref.shape[1] and np.array_equal(ref, np.eye(ref.shape[0]))
         # norm_type="batch": G / E normalise with batch statistics, so batching several of the reference's calls into one is a
@@ -127,11 +133,10 @@ class SRGAN_training():
     # helpers
     def _cached(self, kind, which, make):
         """Per-label-tensor cache (labels are fixed during a step; class_encode forces a host sync)."""
-        cache = self.__dict__.setdefault("_label_cache", {})
         lab = self.label[which]
-        hit = cache.get((kind, which))
+        hit = self._label_cache.get((kind, which))
         if hit is None or hit[0] is not lab:
-            hit = cache[(kind, which)] = (lab, make(lab))
+            hit = self._label_cache[(kind, which)] = (lab, make(lab))
         return hit[1]
 
     def _onehot(self, which):
@@ -151,7 +156,7 @@ class SRGAN_training():
         encoder call (model.py:461).  Graph mode: the draws were made up front (same order) and staged; this hands out the
         next slice of the static buffer."""
         if self._g_active:
-            return self._graph.next_noise()
+            return self._graph.staged_noise.next(1)
         cpu = self.noise_fn(nb, self.ndim) if kind == "randn" else torch.FloatTensor(nb, self.ndim).normal_()
         return host_to_device(cpu, self.device)
 
@@ -165,7 +170,7 @@ class SRGAN_training():
         come from the augmentation's own generator, never the default one.  Graph mode: drawn up front in the same order and
         staged; this hands out the next slice of the static buffer."""
         if self._g_active:
-            return self._graph.next_aug(count)
+            return self._graph.staged_aug.next(count)
         tabs = [self.augment.draw_fn(nb, h, w).to(torch.float32) for _ in range(count)]
         return host_to_device(tabs[0] if count == 1 else torch.cat(tabs, 0), self.device)
 
@@ -190,6 +195,30 @@ class SRGAN_training():
     def _opt_params(opt):
         return [p for g in opt.param_groups for p in g["params"]]
 
+    # What the step is made of, for graph mode (srgan_amd.step_graph).  An optional feature joins a recording's fingerprint and
+    # keep-alive list by being in _extensions(), in a fixed order: it needs fingerprint() and graph_keepalive().
+    def _opts(self):
+        return (self.optG, self.optD, self.optE)
+
+    def _extensions(self):
+        return [x for x in (self._ema, self._sn(), self.augment, self._r1) if x is not None]
+
+    def _mirrors(self):
+        """who mirrors, on the host, a device-side count that the step advances: Adam's step counts, the EMA's update count"""
+        return list(self._opts()) + ([self._ema] if self._ema is not None else [])
+
+    def _forget_step(self):
+        """Drop what the last step left behind.  It keeps its last autograd graph on purpose (``target_image`` is back-propagated
+        twice); a parameter's AccumulateGrad node lives as long as any graph that points at it and remembers the stream it was
+        made on, which an eager step and a recorded one must not share (step_graph).  Every retained reference pins such a
+        graph, so all go: the images, the loss terms, the label cache, the optimisers' keep-alives.  All are rebuilt on demand."""
+        self.target_image = self.recon_image = self.c_rand = self.enc_info = self.target_cenc = None
+        self.loss_terms = {}
+        self._label_cache.clear()
+        for opt in self._opts():
+            opt._keep_alive = None
+        gc.collect()
+
     def _step(self, opt):
         """optimiser step + one launch that re-packs the cached conv operands of the weights it just changed"""
         sn = self._sn() if opt is self.optD else None
@@ -209,10 +238,9 @@ class SRGAN_training():
         """The spectral-norm controller of a marked ``self.D`` (``spectral.spectral_norm(sg.D)``), or None; refuses the marks this
         trainer does not serve."""
         key = (spectral.marks_epoch(), id(self.G), id(self.D), id(self.E), dp.world_size())
-        hit = self.__dict__.get("_sn_cache")
-        if hit is None or hit[0] != key:
-            hit = self._sn_cache = (key, self._sn_lookup())
-        return hit[1]
+        if self._sn_cache[0] != key:
+            self._sn_cache = (key, self._sn_lookup())
+        return self._sn_cache[1]
 
     def _sn_lookup(self):
         for name in ("G", "E"):
@@ -269,6 +297,17 @@ class SRGAN_training():
             eps = noise if noise is not None else self._noise("normal", mu.shape[0])
             return [E.reparam_with(mu, logvar, eps), mu, logvar, E.fcclass(feat), None]
         return list(self.E(image))
+
+    def _mu_pair(self, a, make_b, noise_a, noise_b):
+        """mu of E(a) and of E(b), b = make_b(), with pre-drawn reparametrisation noise (fused paths).  Per-sample encoder: b is
+        made first and both go through the trunk as ONE batch.  Batch statistics: each forward normalises its own batch and
+        advances the running buffers once, so they run one by one in the reference's order -- E(a), what make_b runs, E(b)."""
+        if not self._e_per_sample:
+            mu_a = self._encode(a, noise=noise_a)[1]
+            return mu_a, self._encode(make_b(), noise=noise_b)[1]
+        feats = dp.unwrap(self.E).features(ops.cat_batch([a, make_b()]))
+        nb = a.shape[0]
+        return self._encode(None, feats[:nb], noise_a)[1], self._encode(None, feats[nb:], noise_b)[1]
 
     def _fused_paths(self):
         """The batched / fused execution needs this package's own modules (feature / logit entry points) and a fused kernel
@@ -384,16 +423,13 @@ class SRGAN_training():
         if not _defer:
             self._finish_D()
         self.loss_terms.update(errD_real=errD_real.detach(), errD_class=errD_class.detach(), errD_fake=errD_fake.detach())
-        if _next_fake is not None:
-            return errD, nxt
-        return errD
+        return (errD, nxt) if _next_fake is not None else errD
 
     def _finish_D(self):
         """Wait for the discriminator's gradient all-reduce (if any) and take its optimiser step, if an ``update_D`` left them."""
-        red = self.__dict__.get("_d_pending")
+        red, self._d_pending = self._d_pending, None
         if red is None:
             return
-        self._d_pending = None
         if red is not True:
             red.finish()
         self._step(self.optD)
@@ -520,12 +556,11 @@ class SRGAN_training():
             redE.finish()
         self._step(self.optE)
         do_idt_reg = L["idt_reg"] * L["idt"] > 0
-        early_info = None
+        info = reg_noise = None
         if redG is not None and do_idt_reg and self._fused_paths() and self._e_per_sample:
-            nb = src.shape[0]
-            early_noise = [self._noise("normal", nb) for _ in range(3)]     # reference order: E(target_image), E(source), E(idt_random_image)
+            reg_noise = [self._noise("normal", src.shape[0]) for _ in range(3)]     # reference order: E(target_image), E(source), E(idt_random_image)
             with _frozen(list(self.E.parameters())), torch.no_grad():
-                early_info = self._encode(src, noise=early_noise[1])
+                info = self._encode(src, noise=reg_noise[1])
         if redG is not None:
             redG.finish()
         self._step(self.optG)
@@ -534,33 +569,18 @@ class SRGAN_training():
         self.G.zero_grad()
         self.E.zero_grad()
         with _frozen(list(self.E.parameters())):           # only optG steps: E's weight grads are discarded
-            if do_idt_reg and self._fused_paths() and not self._e_per_sample:
-                # batch statistics: E's three forwards one by one, in the reference's order (E(target_image), E(source),
-                # E(idt_random_image)) -- each normalises its own batch and advances the running buffers once
-                nb = src.shape[0]
-                n1, n2, n3 = (self._noise("normal", nb) for _ in range(3))
-                target_cenc = self._encode(self.target_image, noise=n1)[1]
-                with torch.no_grad():                       # its gradient only reaches E's parameters
-                    info = self._encode(src, noise=n2)
-                idt_random_image, info = self.G_transformation("source", src, True, src, _enc_info=info)
-                idt_cenc_rand = self._encode(idt_random_image, noise=n3)[1]
-                errG_reg = ops.l1_mean(self.c_rand, target_cenc, 1.0)
-                errG_idt_reg = ops.l1_mean(info[1], idt_cenc_rand, 1.0)
-                errG_ex = ops.lincomb([(errG_reg, L["reg"]), (errG_idt_reg, L["idt_reg"] * (L["idt"] / L["cycle"]))])
-                terms["errG_reg"], terms["errG_idt_reg"] = errG_reg, errG_idt_reg
-            elif do_idt_reg and self._fused_paths():
-                # reference order of the noise draws: E(target_image), E(source), E(idt_random_image)
-                nb = src.shape[0]
-                if early_info is not None:                  # (data parallel: drawn and encoded under G's all-reduce, above)
-                    (n1, n2, n3), info = early_noise, early_info
-                else:
-                    n1, n2, n3 = (self._noise("normal", nb) for _ in range(3))
-                    with torch.no_grad():                   # its gradient only reaches E's parameters
-                        info = self._encode(src, noise=n2)
-                idt_random_image, info = self.G_transformation("source", src, True, src, _enc_info=info)
-                feats = E.features(ops.cat_batch([self.target_image, idt_random_image]))    # ONE batch through E
-                target_cenc = self._encode(None, feats[:nb], n1)[1]
-                idt_cenc_rand = self._encode(None, feats[nb:], n3)[1]
+            if do_idt_reg and self._fused_paths():
+                # reference order of the noise draws: E(target_image), E(source), E(idt_random_image); data parallel: drawn above
+                n1, n2, n3 = reg_noise or [self._noise("normal", src.shape[0]) for _ in range(3)]
+
+                def translate_source():
+                    nonlocal info
+                    if info is None:
+                        with torch.no_grad():               # its gradient only reaches E's parameters
+                            info = self._encode(src, noise=n2)
+                    return self.G_transformation("source", src, True, src, _enc_info=info)[0]
+
+                target_cenc, idt_cenc_rand = self._mu_pair(self.target_image, translate_source, n1, n3)
                 errG_reg = ops.l1_mean(self.c_rand, target_cenc, 1.0)
                 errG_idt_reg = ops.l1_mean(info[1], idt_cenc_rand, 1.0)
                 errG_ex = ops.lincomb([(errG_reg, L["reg"]), (errG_idt_reg, L["idt_reg"] * (L["idt"] / L["cycle"]))])
@@ -598,7 +618,6 @@ class SRGAN_training():
         """k discriminator updates then one G/E update (util_notebook.py:696-728).  The reference then
         "restores" D from ``paramD = self.D.state_dict()``, which aliases the live tensors -- a no-op that
         is not replayed here.  Returns [errorG, errorD(first iteration), errorE]."""
-        errorD = None
         src, k = self.source_image, self.k
         nb = src.shape[0]
         # G does not change during the k discriminator updates, so all k translations are computed up front, with the
@@ -612,10 +631,8 @@ class SRGAN_training():
             # under the previous update's all-reduce; the last update's all-reduce runs under the encoder / generator forward
             # passes of phase 1 (update_GandE calls _finish_D() right before it needs the updated discriminator).
             def translate(i):
-                if i < k - 1:
-                    with torch.no_grad():
-                        return self.G(src, torch.cat([oh, noises[i]], 1)), noises[i]
-                return self.G(src, torch.cat([oh, noises[i]], 1)), noises[i]       # the graph that phases 1 and 2 back-propagate
+                with torch.set_grad_enabled(i == k - 1):       # the last one's graph is what phases 1 and 2 back-propagate
+                    return self.G(src, torch.cat([oh, noises[i]], 1)), noises[i]
 
             fake = translate(0)
             for i in range(k):
@@ -624,41 +641,36 @@ class SRGAN_training():
                 errD, fake = out if nxt is not None else (out, None)
                 if i == 0:
                     errorD = errD.detach()
-            errorG, errorE = self.update_GandE()
-            self._ema_update()
-            return [errorG, errorD, errorE]
-        fakes = []
-        if k > 1 and isinstance(dp.unwrap(self.G), SingleGenerator) and self._g_per_sample:   # per-sample network: batching is exact
-            # the kernels address an activation with 32-bit byte offsets (< 4 GiB per tensor): translations are batched in
-            # groups whose widest activation (the first conv's nch planes at full resolution) stays under that, e.g.
-            # 256x256, B=64, k=5 runs as two groups of 2*B images instead of one of 4*B
-            Gm = dp.unwrap(self.G)
-            widest = max(int(Gm.down_convs[0].weight.shape[0]), 3) * src.shape[2] * src.shape[3] * 4
-            per_group = max(1, min(k - 1, (((1 << 32) - (1 << 26)) // widest) // nb))
-            with torch.no_grad():
-                for lo in range(0, k - 1, per_group):
-                    zs = noises[lo:min(lo + per_group, k - 1)]
-                    c_all = torch.cat([torch.cat([oh, z], 1) for z in zs], 0)
-                    imgs = self.G(ops.cat_batch([src] * len(zs)) if len(zs) > 1 else src, c_all)
-                    fakes += [(imgs[i * nb:(i + 1) * nb], z) for i, z in enumerate(zs)]
-        elif k > 1:
-            with torch.no_grad():
-                fakes = [(self.G(src, torch.cat([oh, z], 1)), z) for z in noises[:-1]]
-        fakes.append((self.G(src, torch.cat([oh, noises[-1]], 1)), noises[-1]))
-        for i in range(k):
-            errD = self.update_D(_fake=fakes[i], _index=i)
-            fakes[i] = None
-            if i == 0:
-                errorD = errD.detach()
+        else:
+            fakes = []
+            if k > 1 and isinstance(dp.unwrap(self.G), SingleGenerator) and self._g_per_sample:   # per-sample network: batching is exact
+                # the kernels address an activation with 32-bit byte offsets (< 4 GiB per tensor): translations are batched in
+                # groups whose widest activation (the first conv's nch planes at full resolution) stays under that, e.g.
+                # 256x256, B=64, k=5 runs as two groups of 2*B images instead of one of 4*B
+                Gm = dp.unwrap(self.G)
+                widest = max(int(Gm.down_convs[0].weight.shape[0]), 3) * src.shape[2] * src.shape[3] * 4
+                per_group = max(1, min(k - 1, (((1 << 32) - (1 << 26)) // widest) // nb))
+                with torch.no_grad():
+                    for lo in range(0, k - 1, per_group):
+                        zs = noises[lo:min(lo + per_group, k - 1)]
+                        c_all = torch.cat([torch.cat([oh, z], 1) for z in zs], 0)
+                        imgs = self.G(ops.cat_batch([src] * len(zs)) if len(zs) > 1 else src, c_all)
+                        fakes += [(imgs[i * nb:(i + 1) * nb], z) for i, z in enumerate(zs)]
+            elif k > 1:
+                with torch.no_grad():
+                    fakes = [(self.G(src, torch.cat([oh, z], 1)), z) for z in noises[:-1]]
+            fakes.append((self.G(src, torch.cat([oh, noises[-1]], 1)), noises[-1]))
+            for i in range(k):
+                errD = self.update_D(_fake=fakes[i], _index=i)
+                fakes[i] = None
+                if i == 0:
+                    errorD = errD.detach()
         errorG, errorE = self.update_GandE()
-        self._ema_update()
-        return [errorG, errorD, errorE]
-
-    def _ema_update(self):
-        """One EMA update per ``train()`` (one iteration of the reference's loop), after phase 2's ``optG.step()``: on the
-        step's stream, inside its ``ops.pack_cache()`` scope and inside its recording.  Two launches, none with the EMA off."""
         if self._ema is not None:
+            # one EMA update per train() (one iteration of the reference's loop), after phase 2's optG.step(): on the step's
+            # stream, inside its ops.pack_cache() scope and inside its recording.  Two launches, none with the EMA off.
             self._ema.update()
+        return [errorG, errorD, errorE]
 
     def train(self, source_image, label):
         if self._ema_scope:
@@ -690,13 +702,11 @@ class SRGAN_training():
         re-create), the second captures and replays, later ones only stage the step's inputs (image batch, labels, the
         CPU-generator noise drawn in the reference's order) into static device buffers and launch the graph.  Inputs of
         another shape (an epoch's last partial batch) run eagerly.  Results are bit-identical to eager execution.
-        Under a process group the recording is cut where a collective starts and where its result is needed (2k + 6 graph
-        segments; between them the all-reduces are enqueued on the communication stream and run UNDER the following segment --
-        the next translation, phase 1's forward passes, E's optimiser step: ``_Recording``, ``dp.launch_pending``); if any rank
-        fails to record, all ranks drop graph mode together and continue eagerly
-        (``SRGAN_DP_GRAPH=0`` refuses graph mode under a process group altogether).  Networks marked with
-        ``dp.sync_batch_stats`` exchange partials inside their backward, where a recording cannot be cut: their step is recorded
-        only in the single-graph form of the C-ABI transport and runs eagerly otherwise (``_StepGraph.SEGMENTED_SYNC``)."""
+        Under a process group the recording is cut where a collective starts and where its result is needed, so that the
+        all-reduces run UNDER the following segment (``step_graph._Recording``, ``dp.launch_pending``); if any rank fails to
+        record, all ranks drop graph mode together and continue eagerly (``SRGAN_DP_GRAPH=0`` refuses graph mode under a process
+        group altogether).  Networks marked with ``dp.sync_batch_stats`` are recorded only in the single-graph form of the C-ABI
+        transport and run eagerly otherwise (``step_graph._StepGraph.SEGMENTED_SYNC``)."""
         self._graph = _StepGraph(self)
         return self
 
@@ -886,8 +896,7 @@ class SRGAN_training():
             opt.set_max_norm(self._guard_value(max_norm, n, "set_grad_clip"))
 
     def disable_grad_guard(self):
-        for n in self._GUARD_NETS:
-            opt = getattr(self, "opt" + n)
+        for opt in self._opts():
             if isinstance(opt, Adam):
                 opt.disable_grad_guard()
         self._guard_changed()
@@ -896,11 +905,8 @@ class SRGAN_training():
         """{"G": {...}, "D": {...}, "E": {...}} of ``optim.Adam.grad_guard_stats()`` (``None`` for a net without a guard): norm,
         scale and skip of each optimiser's last step and its cumulative steps / skipped / clipped counts.  Reads the device
         records: SYNCHRONISES the stream."""
-        out = {}
-        for n in self._GUARD_NETS:
-            opt = getattr(self, "opt" + n)
-            out[n] = opt.grad_guard_stats() if isinstance(opt, Adam) and opt._guard is not None else None
-        return out
+        return {n: opt.grad_guard_stats() if isinstance(opt, Adam) and opt._guard is not None else None
+                for n, opt in zip(self._GUARD_NETS, self._opts())}
 
     @contextlib.contextmanager
     def ema_weights(self):
@@ -918,495 +924,6 @@ class SRGAN_training():
         finally:
             self.G, self.E = live
             self._ema_scope = False
-
-
-class _StepGraph:
-    """Static inputs, capture and replay of one ``SRGAN_training`` step (see ``SRGAN_training.enable_graph``)."""
-
-    def __init__(self, sg):
-        self.sg = sg
-        reason = self.unsupported_reason()
-        if reason and reason is not self.SEGMENTED_SYNC:      # (that one is not a refusal: such steps run eagerly, _local_mode)
-            raise NotImplementedError("SRGAN_training.enable_graph: " + reason)
-        self.key = None          # input signature the eager warm-up ran with
-        self.graph = None
-        self.x = self.noise = self.out = None
-        self.aug = None          # staged DiffAugment tables [2k + 1, B, 8] (None with the feature off)
-        self._aug_i = 0
-        self.lab = {}
-        self._onehot = {}
-        self._noise_i = 0
-        self._versions = None
-        self.table = None
-        self._epoch = -1
-        self._keep = None
-        self._baked = None       # fingerprint of everything the recording holds by value or by pointer (see _fingerprint)
-        self._steps = None       # host-side optimiser step counts the device records stand at after the last replay
-        self._graph_ran = False  # the previous step ran on the capture stream (recorded or replayed)
-        self._force_segmented = False   # a single-graph recording failed on some rank: record segments from here on
-        self._last_single = False       # the recording being made / made last captured its collectives (one graph)
-
-    fault_hook = None            # tests: callable(stage) with stage in {"before", "inside"}; raising makes the recording fail
-
-    # A synced norm's backward exchanges partials from autograd's thread; cutting the recording there would end, in that thread, a
-    # capture begun in this one, which the HIP runtime refuses (hipErrorStreamCaptureWrongThread).  Such a step runs eagerly on
-    # every rank, or as ONE graph with the captured C-ABI collectives (SRGAN_DP_COMM=abi: no cut).
-    SEGMENTED_SYNC = ("synced batch norms in the segmented form: their backward exchange cannot cut a recording from autograd's "
-                      "thread; the step runs eagerly (or as one graph with SRGAN_DP_COMM=abi)")
-
-    def unsupported_reason(self):
-        sg = self.sg
-        if not sg._fused_paths():
-            return ("needs this package's own G / D / E modules, a one-hot ref_label and criteria with a fused kernel (nn.MSELoss, "
-                    "nn.BCEWithLogitsLoss / nn.BCELoss)")
-        for name in ("optG", "optD", "optE"):
-            if not isinstance(getattr(sg, name), Adam):
-                return f"{name} is not srgan_amd.optim.Adam (call opt_sche_initialization(), or pass that class)"
-        if dp.is_distributed() and os.environ.get("SRGAN_DP_GRAPH") == "0":
-            return "SRGAN_DP_GRAPH=0: data-parallel steps run eagerly (hook-driven all-reduce under the backward)"
-        if dp.is_distributed() and self._synced_norms() and not self._single_graph():
-            return self.SEGMENTED_SYNC
-        return None
-
-    def _synced_norms(self):
-        sg = self.sg
-        return any(_is_synced(m) and m.training for net in (sg.G, sg.E) for m in net.modules() if _is_batch_stat(m))
-
-    def _single_graph(self):
-        """Would a recording made now capture its collectives (one graph, no cut)?  The condition of _Recording.single."""
-        return (not getattr(self, "_force_segmented", False) and dp.transport() == "abi"
-                and os.environ.get("SRGAN_DP_SINGLE_GRAPH") != "0")
-
-    @staticmethod
-    def _key(source_image, label):
-        def dev(t):
-            return t.device.type if torch.is_tensor(t) else "host"
-        return (tuple(source_image.shape), dev(label["source"]), dev(label["target"]))
-
-    def _fingerprint(self):
-        """Everything a recording bakes in besides the input shape and the buffers ``ops.structure_epoch()`` watches: the
-        optimiser objects, their hyper-parameters and moment tensors (``load_state_dict`` replaces them), which parameters
-        take gradients (``freeze_melt`` / ``requires_grad_``), k, the loss weights, the criteria, the style-code source, the
-        label table.  A replay with any of these changed would silently keep training the OLD configuration."""
-        sg = self.sg
-        fp = [sg.k, sg.n_batch, sg.ndim, sg.encoded_feature, tuple(sorted((k, float(v)) for k, v in sg.lbd.items())),
-              type(sg.criterion), type(sg.criterion_class), np.asarray(sg.ref_label, dtype=np.float64).tobytes()]
-        # the kernel kinds follow from the types, but a criterion edited in place (reduction, weight) can lose its kind
-        fp.append((has_fused_kind(sg.criterion, "gan"), has_fused_kind(sg.criterion_class, "class")))
-        for opt in (sg.optG, sg.optD, sg.optE):
-            fp.append(id(opt))
-            for g in getattr(opt, "param_groups", ()):
-                fp.append((tuple(g["betas"]), float(g["eps"])))
-                for p in g["params"]:
-                    st = opt.state.get(p) or {}
-                    m, v = st.get("exp_avg"), st.get("exp_avg_sq")
-                    fp.append((id(p), m.data_ptr() if m is not None else 0, v.data_ptr() if v is not None else 0))
-        fp.append(tuple((id(p), p.data_ptr(), p.requires_grad) for p in self._all_params()))
-        # batch norms: train / eval mode, momentum and eps are baked into the recorded launches (the running buffers themselves are
-        # device state the step updates in place)
-        # so is the mark of dp.sync_batch_stats (another autograd function, with exchanges)
-        fp.append(tuple((id(m), m.training, m.momentum, m.eps, m.track_running_stats, _is_synced(m)) for net in (sg.G, sg.E)
-                        for m in net.modules() if _is_batch_stat(m)))
-        # the EMA's two launches, its record and its table (enable_ema / disable_ema between steps); the decay is device state
-        cur = getattr(sg, "_ema", None)
-        fp.append(cur.fingerprint() if cur is not None else None)
-        # the gradient guards: their reduce launches, the guarded update and the records (enable / disable between steps); the
-        # clipping threshold is device state
-        fp.append(tuple(opt.grad_guard_fingerprint() if isinstance(opt, Adam) else None for opt in (sg.optG, sg.optD, sg.optE)))
-        # spectral normalisation of D: the projection and the refresh, their table, workspace and buffers (applied or removed
-        # between steps); u, v, sigma and the normalised weights are device state
-        sn = sg._sn() if hasattr(sg, "_sn") else None
-        fp.append(sn.fingerprint() if sn is not None else None)
-        # DiffAugment of D's inputs: its launches (the groups of the policy, the cutout window), the static table buffer and the
-        # number of tables a step consumes (enabled, disabled or edited between steps); the tables themselves are staged
-        aug = getattr(sg, "augment", None)
-        fp.append(aug.fingerprint() if aug is not None else None)
-        # the R1 penalty: its schedule (every) and launches, the record, the constant seeds and the workspace; gamma is device state
-        r1 = getattr(sg, "_r1", None)
-        fp.append(r1.fingerprint() if r1 is not None else None)
-        return tuple(fp)
-
-    def _opt_steps(self):
-        sg = self.sg
-        return [[int(opt.state[p]["step"]) if len(opt.state.get(p) or {}) else -1 for g in opt.param_groups for p in g["params"]]
-                for opt in (sg.optG, sg.optD, sg.optE)]
-
-    def _drop(self):
-        self.graph, self.key, self._keep, self._baked, self._steps = None, None, None, None, None
-        self.x = self.noise = self.out = self.aug = None
-
-    def _local_mode(self, source_image, label):
-        """2: replay the recording, 1: record (the eager warm-up of this input shape has run), 0: eager."""
-        if dp.is_distributed() and self.unsupported_reason() is self.SEGMENTED_SYNC:
-            # the same answer on every rank (the marks, the transport and a failed single-graph recording are agreed state)
-            if self.graph is not None:
-                self._drop()
-            return 0
-        if self.graph is not None:
-            stale = self._epoch != ops.structure_epoch()
-            # a buffer the recording points at was replaced (compute-mode switch, invalidate_packed, optimiser re-seeded), or
-            # something it baked in changed (optimiser state loaded, requires_grad toggled, lbd / k edited), or the host-side
-            # step counts are not where the last replay left them (load_state_dict): forget the graph; this step runs eagerly
-            # with the new state (which also re-seeds the device-side Adam records), the next one records again
-            if not stale and (self._baked != self._fingerprint() or self._steps != self._opt_steps()):
-                stale = True
-                reason = self.unsupported_reason()
-                if reason:
-                    raise NotImplementedError("SRGAN_training graph mode: " + reason)
-            if stale:
-                self._drop()
-        if self.key is None or self._key(source_image, label) != self.key or not source_image.is_cuda:
-            return 0
-        return 2 if self.graph is not None else 1
-
-    def accepts(self, source_image, label):
-        """Replay / record this step (True) or run it eagerly (False).  Under a process group the decision is COLLECTIVE (one
-        MIN all-reduce of the local answer on the host-side control group): a rank replaying index-ordered flat buckets beside
-        a rank running the hook-ordered eager step -- or recording, with its extra agreement all-reduce -- would issue different
-        collectives.  If any rank has to record, every rank records again; if any rank runs eagerly, all do."""
-        failure = None
-        try:
-            mode = self._local_mode(source_image, label)
-        except NotImplementedError as e:
-            # A rank that can no longer take graph mode must still join the agreement below -- raising before the collective would
-            # leave the other ranks blocked in it.  It votes -1, a value no healthy rank uses (ADVICE r4: a vote of 0 read as
-            # "eager" on the peers, which then entered the eager step and blocked in its first gradient all-reduce until the dead
-            # rank's connection timed out); on a negative minimum EVERY rank raises, at the same point of its program.
-            failure, mode = e, -1
-            if not dp.is_distributed():
-                raise
-        if dp.is_distributed() and mode == 2 and failure is None and getattr(self.graph, "single", False):
-            # Single-graph data-parallel step (round 6): the collectives are INSIDE the recording, so a replay is one launch with
-            # no host-side exchange at all -- graph-or-eager was decided collectively when the step was recorded, and every
-            # condition that drops a recording (_local_mode) is a program-state change an SPMD program makes on every rank at the
-            # same step.  A rank that has to re-record alone votes below while its peers replay: it blocks there until the control
-            # group's timeout and raises (dp.control_group); the segmented mode keeps the per-step vote.
-            return True
-        if dp.is_distributed():
-            agreed = dp.all_min(mode)
-            if failure is not None:
-                raise failure
-            if agreed < 0:
-                raise RuntimeError("SRGAN_training graph mode: another rank cannot take this step (see its own error); no rank "
-                                   "runs it")
-            if agreed < 2 and self.graph is not None:
-                if agreed == 1:
-                    key = self.key
-                    self._drop()           # another rank re-records: record again with it (same segment structure)
-                    self.key = key
-            mode = agreed
-        return mode >= 1
-
-    def before_eager_step(self):
-        """An eager step follows a recorded / replayed one: the autograd graph the step keeps on purpose (``target_image`` is
-        back-propagated twice) pins AccumulateGrad nodes made on the CAPTURE stream; re-used by an eager backward they would
-        synchronise across streams on every gradient (PyTorch warns about the mismatch).  Drop those graphs first."""
-        if not self._graph_ran:
-            return
-        self._graph_ran = False
-        sg = self.sg
-        sg.target_image = sg.recon_image = sg.c_rand = sg.enc_info = sg.target_cenc = None
-        sg.loss_terms = {}
-        for opt in (sg.optG, sg.optD, sg.optE):
-            opt._keep_alive = None
-        gc.collect()
-
-    def note_eager_step(self, source_image, label):
-        if self.key is None and source_image.is_cuda:
-            self.key = self._key(source_image, label)
-        # the eager step left every packed operand fresh: writes from here on (load_state_dict, copy_) must be noticed
-        self._versions = sum(p._version for p in self._all_params())
-        if self.graph is not None:      # an eager step of this trainer (another batch shape) moved the optimisers legitimately
-            self._steps = self._opt_steps()
-
-    # -- what the captured body reads -----------------------------------------------------------------------------
-    def onehot(self, which):
-        hit = self._onehot.get(which)
-        if hit is None:              # once per step (inside the graph): rows of the device copy of ref_label
-            hit = self._onehot[which] = self.table.index_select(0, self.lab[which])
-        return hit
-
-    def next_noise(self):
-        t = self.noise[self._noise_i]
-        self._noise_i += 1
-        return t
-
-    def next_aug(self, count):
-        """the next ``count`` staged tables as one [count * B, 8] view of the static buffer"""
-        t = self.aug[self._aug_i:self._aug_i + count]
-        if t.shape[0] != count:
-            raise RuntimeError(f"the step asks for more DiffAugment tables than the {self.aug.shape[0]} staged")
-        self._aug_i += count
-        return t.reshape(-1, t.shape[-1])
-
-    # -- staging (outside the graph, stream-ordered before the replay) ---------------------------------------------
-    def _stage(self, source_image, label):
-        sg = self.sg
-        dev = source_image.device
-        nb = source_image.shape[0]
-        kinds = sg._noise_kinds()
-        draws = [sg.noise_fn(nb, sg.ndim) if kd == "randn" else torch.FloatTensor(nb, sg.ndim).normal_() for kd in kinds]
-        host_noise = torch.stack([d.to(torch.float32) for d in draws]).pin_memory()
-        x = ops.to_nhwc(source_image)
-        if self.x is None:
-            self.x = torch.empty_like(x)
-            self.noise = torch.empty(len(kinds), nb, sg.ndim, dtype=torch.float32, device=dev)
-            self.lab = {w: torch.empty(nb, dtype=torch.int64, device=dev) for w in ("source", "target")}
-            self.table = torch.tensor(np.asarray(sg.ref_label), dtype=torch.float32).to(dev)
-        n_aug = sg._aug_draws()
-        if n_aug:
-            # the step's 2k + 1 tables, drawn up front in the order the eager step draws them (SRGAN_training._aug_tables)
-            _, _, h, w = x.shape
-            host_aug = torch.stack([sg.augment.draw_fn(nb, h, w).to(torch.float32) for _ in range(n_aug)]).pin_memory()
-            if self.aug is None:
-                self.aug = torch.empty(n_aug, nb, ops.AUG_ROW, dtype=torch.float32, device=dev)
-            self.aug.copy_(host_aug, non_blocking=True)
-        self.x.copy_(x)
-        self.noise.copy_(host_noise, non_blocking=True)
-        for w in ("source", "target"):
-            lab = torch.as_tensor(label[w]).detach().to(dtype=torch.int64)
-            if not lab.is_cuda:
-                lab = lab.pin_memory()
-            self.lab[w].copy_(lab.view(-1), non_blocking=True)
-
-    def _all_params(self):
-        sg = self.sg
-        return [p for net in (sg.G, sg.D, sg.E) for p in net.parameters()]
-
-    def _guard_packed(self):
-        """Weights written behind the graph's back (load_state_dict, copy_: they bump the autograd version, the raw-pointer
-        Adam does not) would leave the captured step multiplying stale packed operands: re-pack before replaying."""
-        v = sum(p._version for p in self._all_params())
-        if self._versions is not None and v != self._versions:
-            ops.refresh_packed(self._all_params(), force=True)
-        self._versions = v
-
-    def _capture(self):
-        sg = self.sg
-        lib_prof_off()
-        # Every autograd graph of the eager warm-up must be gone before recording: a parameter's AccumulateGrad node lives as
-        # long as any graph that points at it, and remembers the stream it was created on.  The step keeps its last graph
-        # alive on purpose (target_image is back-propagated twice), so the nodes of the eager step -- made on the caller's
-        # stream -- would be re-used by the recorded step and pull that stream into the capture as an unjoined fork.
-        sg.target_image = sg.recon_image = sg.c_rand = None
-        sg.loss_terms = {}
-        sg.__dict__.get("_label_cache", {}).clear()
-        for opt in (sg.optG, sg.optD, sg.optE):
-            opt._keep_alive = None
-        gc.collect()
-        hook = type(self).fault_hook
-        if hook is not None:
-            hook("before")
-        ops.mark_singles_stale()          # their pack launches belong to the recording (ops.refresh_packed)
-        g = _Recording(self.x.device, single=not self._force_segmented)
-        self._last_single = g.single
-        epoch0 = ops.structure_epoch()    # ADVICE r5: a buffer replaced DURING the recording (the weight-gradient arena grown
-        sg._g_active = True               # between two segments) would leave earlier segments pointing at freed memory
-        self._noise_i, self._aug_i, self._onehot = 0, 0, {}
-        sg.source_image = self.x
-        try:
-            with g:
-                with ops.pack_cache(refresh_on_entry=False):
-                    err = sg.UnrolledUpdate()
-                if hook is not None:
-                    hook("inside")
-                self.out = torch.stack([e.detach().reshape(()) for e in err])
-        finally:
-            sg._g_active = False
-        if self._noise_i != self.noise.shape[0]:
-            raise RuntimeError(f"captured step consumed {self._noise_i} noise draws, staged {self.noise.shape[0]}")
-        if self._aug_i != sg._aug_draws():
-            raise RuntimeError(f"captured step consumed {self._aug_i} DiffAugment tables, staged {sg._aug_draws()}")
-        if ops.structure_epoch() != epoch0:
-            raise RuntimeError("a workspace the step points at was replaced while the step was being recorded "
-                               "(ops.structure_epoch moved): the recording is dropped")
-        self.graph = g
-        self.terms = dict(sg.loss_terms)
-        self._epoch = ops.structure_epoch()
-        self._keep = ops.graph_keepalive() + [t for opt in (sg.optG, sg.optD, sg.optE) for t in opt.graph_keepalive()]
-        if sg._ema is not None:
-            self._keep += sg._ema.graph_keepalive()
-        if sg._sn() is not None:
-            self._keep += sg._sn().graph_keepalive()
-        if getattr(sg, "_r1", None) is not None:
-            self._keep += sg._r1.graph_keepalive()
-        self._baked = self._fingerprint()
-
-    def _abandon(self, err, snap, keep_graph_mode=False):
-        """Some rank could not record the step: every rank drops graph mode together.  THIS step still runs -- eagerly, from the
-        inputs already staged for the recording (same image batch, labels and pre-drawn noise, so the CPU generator is where an
-        eager run would have left it) -- and later steps take the ordinary eager path."""
-        import warnings
-        sg = self.sg
-        for opt, c in zip((sg.optG, sg.optD, sg.optE), snap):
-            opt.restore_host_counters(c)          # the recording advanced them without running anything
-        if sg._ema is not None:
-            sg._ema.updates = self._ema_snap
-        warnings.warn("SRGAN_training: the step could not be recorded as " + ("ONE hipGraph with captured collectives" if keep_graph_mode
-                                                                              else "hipGraph segments") + " on every rank"
-                      + (f" (this rank: {type(err).__name__}: {err})" if err is not None else "")
-                      + ("; this step runs eagerly, the next one is recorded as segments" if keep_graph_mode else "; running eagerly from here on"))
-        self.graph = self._keep = self._baked = self._steps = None
-        self._noise_i, self._aug_i, self._onehot = 0, 0, {}     # (the staged noise and DiffAugment tables are used again)
-        sg.target_image = sg.recon_image = sg.c_rand = None
-        sg.loss_terms = {}
-        sg.__dict__.get("_label_cache", {}).clear()
-        # host-side caches may describe device buffers whose filling launch was only RECORDED (a packed operand or a repack table
-        # first made while recording): forget them all, the eager step re-packs from the weights
-        ops.invalidate_packed()
-        sg.source_image = self.x
-        sg._g_active = True
-        try:
-            with ops.pack_cache():
-                out = sg.UnrolledUpdate()
-        finally:
-            sg._g_active = False
-            if not keep_graph_mode:
-                sg._graph = None
-        return out
-
-    def run(self, source_image, label):
-        sg = self.sg
-        self._stage(source_image, label)
-        self._guard_packed()
-        for opt in (sg.optG, sg.optD, sg.optE):
-            opt.sync_device()
-        if self.graph is None:
-            err = None
-            snap = [opt.host_counters() for opt in (sg.optG, sg.optD, sg.optE)]
-            self._ema_snap = sg._ema.updates if sg._ema is not None else 0
-            try:
-                self._capture()      # records; the host-side optimiser counters advanced while recording
-            except Exception as e:   # noqa: BLE001 -- under a process group the ranks first agree on what happened
-                if not dp.is_distributed():
-                    # leave nothing half-advanced behind for a caller that catches this: the counters moved without anything
-                    # having run, caches may describe operands whose fill was only recorded, and graph mode stays off
-                    for opt, c in zip((sg.optG, sg.optD, sg.optE), snap):
-                        opt.restore_host_counters(c)
-                    if sg._ema is not None:
-                        sg._ema.updates = self._ema_snap
-                    ops.invalidate_packed()
-                    self._drop()
-                    sg._graph = None
-                    sg.target_image = sg.recon_image = sg.c_rand = None
-                    sg.loss_terms = {}
-                    raise
-                err = e
-            if dp.is_distributed() and not dp.all_agree(err is None):
-                # some rank could not record the step: EVERY rank gives the recording up together (a rank replaying segments
-                # beside a rank running eagerly would issue the same collectives in another order) and runs eagerly.  If the
-                # attempt was the single-graph form (collectives captured), the segmented form is tried at the next step before
-                # graph mode is given up: this step runs eagerly, the next one records segments.
-                retry = self._last_single and not self._force_segmented
-                self._force_segmented = self._force_segmented or self._last_single
-                return self._abandon(err, snap, keep_graph_mode=retry)
-            self._deltas = [opt.counters_since(c) for opt, c in zip((sg.optG, sg.optD, sg.optE), snap)]
-            self._ema_delta = sg._ema.updates - self._ema_snap if sg._ema is not None else 0
-            ema_moved = 0                # the recording advanced the host mirror already
-        else:
-            for opt, d in zip((sg.optG, sg.optD, sg.optE), self._deltas):
-                opt.advance_host(d)
-            ema_moved = self._ema_delta
-        self.graph.replay()
-        if sg._ema is not None:
-            sg._ema.after_replay(ema_moved)   # the replay wrote the copies through raw pointers
-        self._graph_ran = True
-        self._steps = self._opt_steps()
-        sg.source_image = self.x
-        sg.loss_terms = dict(self.terms)
-        out = self.out.clone()       # the static result vector is overwritten by the next replay
-        return [out[0], out[1], out[2]]
-
-
-class _Recording:
-    """One train step as a chain of hipGraph segments with host callables between them.
-
-    Single process: one segment -- the whole step is one graph launch.  Data parallel: ``srgan_amd.dp`` ends the segment being
-    recorded wherever the step starts a collective (``dp.launch_pending``: the bucket all-reduces after a backward; the mu
-    all-gather) and wherever it needs the result (``GradReducer.finish``), and hands over a host callable; ``replay()`` launches
-    segment, callable, segment, ... on the caller's stream.  A "start" callable enqueues the in-place all-reduces of the flat
-    buckets on the communication stream behind a ``ready`` event and returns; the segments launched next -- the work the trainer
-    placed between start and finish: the next translation during the discriminator loop, phase 1's encoder / generator forward
-    under the last discriminator all-reduce, E's optimiser step and phase 2's E(source) under G's -- run UNDER the collectives;
-    the "wait" callable makes the compute stream wait for the ``done`` events right before the optimiser-step segment.  Nothing
-    of RCCL is captured and no stream is forked inside a capture: the collectives stay ordinary eager calls on static buffers in
-    a fixed order.  2k + 6 segments per step (k x (start, wait), the all-gather, start(E) inside phase 1's backward, start(G) + wait(E), wait(G),
-    start(G) + wait(G): a wait that follows its start directly rides in the same callable).  All segments allocate from one private pool and are replayed in recording order, so a tensor made in one segment
-    is valid in the following ones."""
-
-    def __init__(self, device, single=True):
-        self.device = device
-        # Round 6 (VERDICT r5 item 4): with the C-ABI collectives (dp.set_transport("abi") / SRGAN_DP_COMM=abi) a collective is one
-        # RCCL enqueue on a stream -- capturable -- so the step is recorded as ONE graph: where the segmented form cuts, the host
-        # callable runs INSIDE the capture (the communication stream forks off the capture stream at the bucket's `ready` event
-        # and joins it again at `done`), and a replay is a single launch.  SRGAN_DP_SINGLE_GRAPH=0 keeps the segments.
-        self.single = bool(single and dp.is_distributed() and dp.transport() == "abi" and os.environ.get("SRGAN_DP_SINGLE_GRAPH") != "0")
-        self.inline = []           # single-graph form: kinds of the captured collectives, in enqueue order
-        self.segments = []         # [(CUDAGraph, callable or None)]
-        self.trace = None          # tests: a list -> the host-side order of the last replay: ("segment", i) / (comm kind, i)
-        self.pending = []          # flat gradient buckets laid out since the last cut (dp.GradReducer)
-        self._cur = None
-        self._pool = None
-        self._stream = None
-        self._stream_ctx = None
-        # other threads of a data-parallel process (the process group's watchdog) may touch HIP while this one records
-        self._mode = "thread_local" if dp.is_distributed() else "global"
-
-    def _begin(self):
-        self._cur = torch.cuda.CUDAGraph()
-        self._cur.capture_begin(pool=self._pool, capture_error_mode=self._mode)
-
-    def cut(self, comm):
-        if self.single:
-            comm()                 # enqueued into the capture (fork to / join from the communication stream)
-            self.inline.append(getattr(comm, "kind", "comm"))
-            return
-        self._cur.capture_end()
-        self.segments.append((self._cur, comm))
-        self._begin()
-
-    def __enter__(self):
-        torch.cuda.synchronize(self.device)
-        gc.collect()
-        torch.cuda.empty_cache()
-        self._pool = torch.cuda.graph_pool_handle()
-        self._stream = torch.cuda.Stream(self.device)
-        self._stream.wait_stream(torch.cuda.current_stream(self.device))
-        self._stream_ctx = torch.cuda.stream(self._stream)
-        self._stream_ctx.__enter__()
-        dp.set_recorder(self if dp.is_distributed() else None)
-        self._begin()
-        return self
-
-    def __exit__(self, *exc):
-        dp.set_recorder(None)
-        try:
-            self._cur.capture_end()
-            self.segments.append((self._cur, None))
-        finally:
-            self._cur = None
-            self._stream_ctx.__exit__(*exc)
-        if exc[0] is None and self.pending:
-            raise RuntimeError("recorded step left gradient buckets without their all-reduce (GradReducer.finish() not called)")
-        return False
-
-    def replay(self):
-        trace = self.trace
-        if trace is not None:
-            trace.clear()
-        with torch.no_grad():          # the collectives write buffers (views made inside autograd functions) in place
-            for i, (graph, comm) in enumerate(self.segments):
-                graph.replay()
-                if trace is not None:
-                    trace.append(("segment", i))
-                if comm is not None:
-                    comm()
-                    if trace is not None:
-                        trace.append((getattr(comm, "kind", "comm"), i))
-
-
-def lib_prof_off():
-    _lib.load().srgan_prof_enable(0)     # HIP-event brackets cannot be recorded into a capture
 
 
 def _select_rows(x, mask):

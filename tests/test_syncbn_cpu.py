@@ -106,6 +106,12 @@ def test_fingerprint_and_fallback_follow_the_mark():
     class SG:
         k, n_batch, ndim, encoded_feature, lbd, criterion, criterion_class, ref_label = 2, 4, 8, "mu", {}, None, None, [[1.0]]
         optG = optD = optE = Opt()
+
+        def _opts(self):
+            return (self.optG, self.optD, self.optE)
+
+        def _extensions(self):
+            return []
     sg = SG()
     sg.G, sg.D, sg.E = _tier_t()
     g = trainer._StepGraph.__new__(trainer._StepGraph)

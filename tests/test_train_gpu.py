@@ -336,6 +336,35 @@ def test_latent_mode_and_generic_encoder_path():
     np.testing.assert_allclose(out, ref, rtol=1e-3)
 
 
+@pytest.fixture(scope="module")
+def parent_bits(golden_dir):
+    return np.load(os.path.join(golden_dir, "train_step_parent_bits.npz"))
+
+
+@pytest.mark.parametrize("case", ["plain", "all_on", "batch_norm", "generic", "latent"])
+def test_train_step_keeps_the_parent_bits(parent_bits, case):
+    """The step computes, bit for bit, what the recorded commit computed (tests/golden/make_step_parent_bits.py; the fixture
+    names that commit): every returned loss and loss term of every step, every tensor of the networks, the Adam moments, the EMA
+    twins and the spectral state by digest, the R1 and gradient-guard records, and the launch count per kernel of the last step
+    (the deterministic stand-in for "as fast as before").  Eagerly for the five configurations -- between them they reach every
+    branch of the step body -- and replayed from a hipGraph for ``plain`` and ``all_on`` (no launch counts there: the launch
+    timer is off under a capture)."""
+    import json
+    from tests.step_bits_common import WITH_LAUNCH_COUNTS, run_case
+    assert len(str(parent_bits["parent_commit"])) == 40
+    want_losses, want = parent_bits[case + "/losses"], json.loads(parent_bits[case + "/meta"].tobytes())
+    for graph in (False, True) if case in WITH_LAUNCH_COUNTS else (False,):
+        losses, meta = run_case(case, graph=graph)
+        assert losses.dtype == np.float32 and want_losses.dtype == np.float32
+        np.testing.assert_array_equal(losses, want_losses)
+        assert meta["digests"] == want["digests"], sorted(k for k in want["digests"] if meta["digests"].get(k) != want["digests"][k])
+        assert meta["r1_stats"] == want["r1_stats"]
+        assert meta["grad_guard_stats"] == want["grad_guard_stats"]
+        if not graph:
+            assert meta["launches"] == want["launches"]
+            assert (want["launches"] is not None) == (case in WITH_LAUNCH_COUNTS)
+
+
 # ---- config 1: conventional SingleGAN (BASELINE configs[0]) on the HIP path --------------------------------
 SG_BASE = dict(**{"class": 0.0}, cycle=5.0, idt=5.0, reg=0.5, idt_reg=0.0, KL=0.1, batch_KL=0.0, corr_enc=0.0, hist=0.0)
 
