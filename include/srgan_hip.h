@@ -506,10 +506,14 @@ int srgan_ema_multi_dev(const void* table, int n_records, long long total_chunks
  * skip = S is not finite, scale = skip ? 0 : min(1, max_norm / (norm + 1e-6f)) in fp32, steps += 1, skipped / clipped += 1.
  * No atomics: the result does not depend on the grid.  srgan_adam_multi_dev_guard = srgan_adam_multi_dev behind the record: the
  * tick runs as always (t += 1 even for a skipped step), the update stores nothing when skip is set and otherwise runs the same
- * arithmetic on g * scale (one fp32 multiply; the gradients are not written; scale = 1 leaves every result bit-identical). */
+ * arithmetic on g * scale (one fp32 multiply; the gradients are not written; scale = 1 leaves every result bit-identical).
+ * srgan_grad_guard_state_set_counters (extension, no counterpart in the reference; resuming from a checkpoint): one one-thread
+ * launch that writes the three cumulative counters between steps and nothing else -- max_norm keeps its own setter, norm / scale /
+ * skip stay those of the last step; a negative count is refused (-1 with srgan_last_error(), no launch). */
 size_t srgan_grad_guard_state_bytes(void);
 int srgan_grad_guard_state_init(void* state, float max_norm, void* stream);
 int srgan_grad_guard_state_set_max_norm(void* state, float max_norm, void* stream);
+int srgan_grad_guard_state_set_counters(void* state, int steps, int skipped, int clipped, void* stream);
 size_t srgan_grad_guard_workspace(long long total_chunks);
 int srgan_grad_guard_reduce(const void* table, int n_records, long long total_chunks, void* ws, size_t ws_bytes, void* state,
                             void* stream);
@@ -577,10 +581,14 @@ int srgan_diffaugment_bwd(const float* gy, const float* table, float* gx, int n,
  * owner and order per element (same bits).  srgan_r1_finalize: one workgroup sums the partials in double in a fixed order and
  * writes mean_sq_norm = S / n, penalty = gamma * every / 2 * S / n, updates += 1.  No atomics: a sample's u0 and partials depend
  * neither on n nor on its position.  -1 with srgan_last_error() before any launch: c != 3, a NULL pointer, n / h / w <= 0,
- * gamma < 0 or not finite, every < 1, a workspace too small, u0 aliasing h1 or h2. */
+ * gamma < 0 or not finite, every < 1, a workspace too small, u0 aliasing h1 or h2.
+ * srgan_r1_state_set_updates (extension, no counterpart in the reference; resuming from a checkpoint): one one-thread launch that
+ * writes the count of penalised updates between steps and nothing else -- gamma, every, c and n keep srgan_r1_state_set, penalty and
+ * mean_sq_norm stay those of the last finalize; a negative count is refused (-1 with srgan_last_error(), no launch). */
 size_t srgan_r1_state_bytes(void);
 int srgan_r1_state_init(void* state, float gamma, int every, int n, void* stream);
 int srgan_r1_state_set(void* state, float gamma, int every, int n, void* stream);
+int srgan_r1_state_set_updates(void* state, int updates, void* stream);
 size_t srgan_r1_workspace(int n, int h, int w);
 int srgan_r1_seed(const float* h1, const float* h2, const void* state, float* u0, int n, int c, int h, int w, void* ws,
                   size_t ws_bytes, void* stream);

@@ -420,6 +420,10 @@ __global__ void guard_state_init_kernel(GuardState* s, float max_norm) {
   s->max_norm = max_norm; s->norm = 0.f; s->scale = 1.f; s->skip = 0; s->steps = 0; s->skipped = 0; s->clipped = 0; s->pad = 0;
 }
 __global__ void guard_state_max_norm_kernel(GuardState* s, float max_norm) { s->max_norm = max_norm; }
+// resume: the cumulative counters of a checkpoint; the threshold and the last step's decision stay
+__global__ void guard_state_counters_kernel(GuardState* s, int steps, int skipped, int clipped) {
+  s->steps = steps; s->skipped = skipped; s->clipped = clipped;
+}
 
 // Sum of squares of every gradient, one fp32 partial per 4096-element chunk.  `table`: n_records records of three 64-bit words
 // {g, numel, chunk0}; the work is the flat chunk list of ema_multi_dev_kernel (chunk0 = prefix sum of ceil(numel / 4096)), so 300
@@ -822,6 +826,14 @@ extern "C" int srgan_grad_guard_state_set_max_norm(void* state, float max_norm, 
   hipLaunchKernelGGL(srgan::guard_state_max_norm_kernel, dim3(1), dim3(1), 0, as_stream(stream),
                      static_cast<srgan::GuardState*>(state), max_norm);
   return check_launch("guard_state_max_norm_kernel");
+}
+
+extern "C" int srgan_grad_guard_state_set_counters(void* state, int steps, int skipped, int clipped, void* stream) {
+  SRGAN_REQUIRE(state && steps >= 0 && skipped >= 0 && clipped >= 0,
+                "grad_guard_state_set_counters: bad argument (steps, skipped, clipped >= 0)");
+  hipLaunchKernelGGL(srgan::guard_state_counters_kernel, dim3(1), dim3(1), 0, as_stream(stream),
+                     static_cast<srgan::GuardState*>(state), steps, skipped, clipped);
+  return check_launch("guard_state_counters_kernel");
 }
 
 extern "C" size_t srgan_grad_guard_workspace(long long total_chunks) {

@@ -41,6 +41,8 @@ __global__ void r1_state_init_kernel(R1State* s, float gamma, int every, int n) 
 __global__ void r1_state_set_kernel(R1State* s, float gamma, int every, int n) {
   s->gamma = gamma; s->every_scale = every; s->c = gamma * (float)every / (float)n; s->n = n;
 }
+// resume: a checkpoint's count of penalised updates; everything else stays
+__global__ void r1_state_updates_kernel(R1State* s, int updates) { s->updates = updates; }
 
 // rows (or columns) of the image the pooled coordinate k averages: those of 2k - 1 .. 2k + 1 inside [0, len)
 __device__ __forceinline__ int r1_span(int k, int len) { return min(2 * k + 1, len - 1) - max(2 * k - 1, 0) + 1; }
@@ -154,6 +156,13 @@ extern "C" int srgan_r1_state_set(void* state, float gamma, int every, int n, vo
   hipLaunchKernelGGL(srgan::r1_state_set_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::R1State*>(state), gamma,
                      every, n);
   return check_launch("r1_state_set_kernel");
+}
+
+extern "C" int srgan_r1_state_set_updates(void* state, int updates, void* stream) {
+  SRGAN_REQUIRE(state && updates >= 0, "r1_state_set_updates: bad argument (updates >= 0)");
+  hipLaunchKernelGGL(srgan::r1_state_updates_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::R1State*>(state),
+                     updates);
+  return check_launch("r1_state_updates_kernel");
 }
 
 extern "C" size_t srgan_r1_workspace(int n, int h, int w) {

@@ -182,6 +182,7 @@ SIGNATURES = {
     "srgan_grad_guard_state_bytes": (c_size_t, []),
     "srgan_grad_guard_state_init": (c_int, [P, c_float, P]),
     "srgan_grad_guard_state_set_max_norm": (c_int, [P, c_float, P]),
+    "srgan_grad_guard_state_set_counters": (c_int, [P, c_int, c_int, c_int, P]),
     "srgan_grad_guard_workspace": (c_size_t, [c_longlong]),
     "srgan_grad_guard_reduce": (c_int, [P, c_int, c_longlong, P, c_size_t, P, P]),
     "srgan_adam_multi_dev_guard": (c_int, [P, c_int, c_longlong, P, P, P]),
@@ -197,6 +198,7 @@ SIGNATURES = {
     "srgan_r1_state_bytes": (c_size_t, []),
     "srgan_r1_state_init": (c_int, [P, c_float, c_int, c_int, P]),
     "srgan_r1_state_set": (c_int, [P, c_float, c_int, c_int, P]),
+    "srgan_r1_state_set_updates": (c_int, [P, c_int, P]),
     "srgan_r1_workspace": (c_size_t, [c_int, c_int, c_int]),
     "srgan_r1_seed": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     "srgan_r1_finalize": (c_int, [P, c_size_t, c_int, c_int, c_int, P, P]),

@@ -157,3 +157,4 @@ class WeightEMA:
         for k, t in self.twins.items():
             t.load_state_dict(sd[k])          # in place: the table keeps pointing at the same storage
         self.reseed(sd["decay"], sd["ramp"], sd["updates"])
+        ops.mark_stale(self._params)          # the copies' cached packed operands describe the weights before the load

@@ -2425,6 +2425,12 @@ def grad_guard_state_set_max_norm(state, max_norm):
                "grad_guard_state_set_max_norm")
 
 
+def grad_guard_state_set_counters(state, steps, skipped, clipped):
+    """Write the cumulative counters between steps (resume from a checkpoint); the threshold and the last step's decision stay."""
+    _lib.check(_lib.load().srgan_grad_guard_state_set_counters(_ptr(state), int(steps), int(skipped), int(clipped), _stream()),
+               "grad_guard_state_set_counters")
+
+
 def grad_guard_state_read(state):
     """The record as a dict; synchronises the current stream (the only host read of the guard)."""
     torch.cuda.current_stream(state.device).synchronize()
@@ -2642,6 +2648,11 @@ def r1_state_new(device, gamma, every, n):
 def r1_state_set(state, gamma, every, n):
     """Rewrite gamma, every, n and c between steps; the counters stay (a recorded step reads the record)."""
     _lib.check(_lib.load().srgan_r1_state_set(_ptr(state), *_r1_args(gamma, every, n), _stream()), "r1_state_set")
+
+
+def r1_state_set_updates(state, updates):
+    """Write the count of penalised updates between steps (resume from a checkpoint); everything else stays."""
+    _lib.check(_lib.load().srgan_r1_state_set_updates(_ptr(state), int(updates), _stream()), "r1_state_set_updates")
 
 
 def r1_state_read(state):

@@ -164,6 +164,36 @@ class Adam(torch.optim.Optimizer):
             self._update(gi, group, batches, guard)
         return loss
 
+    # -- resume -----------------------------------------------------------------------------------------------------------
+    def load_state_dict(self, state_dict):
+        """``torch.optim.Optimizer.load_state_dict`` plus what the raw-pointer step needs of the result: ``state[p]["step"]`` is
+        an ``int`` again (a file may hand back a 0-dim tensor), the moments are contiguous float32 on their parameter's device
+        (torch casts them to the parameter's dtype and keeps the strides it was given), ``betas`` a tuple.  The cohorts are
+        forgotten, so the next ``step()`` seeds fresh device records at the loaded counts with the loaded hyper-parameters (a
+        recording that points at the old ones is dropped by its owner: ``ops.bump_structure_epoch``).  Between steps only.  A
+        parameter without saved state stays without state; the gradient guard is not part of the dict and stays as it is."""
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("srgan_amd.optim.Adam: load_state_dict inside a hipGraph capture")
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:
+            group["betas"] = tuple(float(b) for b in group["betas"])
+            for p in group["params"]:
+                st = self.state.get(p)
+                if not st:
+                    continue
+                st["step"] = int(st["step"])
+                for key in ("exp_avg", "exp_avg_sq"):
+                    m = st[key]
+                    if m.shape != p.shape:
+                        raise ValueError(f"srgan_amd.optim.Adam.load_state_dict: {key} of shape {tuple(m.shape)} for a parameter of "
+                                         f"shape {tuple(p.shape)}")
+                    if m.device != p.device or m.dtype != torch.float32 or not m.is_contiguous():
+                        st[key] = m.to(device=p.device, dtype=torch.float32).contiguous()
+        if self._cohorts:
+            ops.bump_structure_epoch()           # a captured step points at the records being dropped
+            self._cohorts = {}
+        self._keep_alive = None
+
     # -- gradient guard -------------------------------------------------------------------------------------------------
     def enable_grad_guard(self, max_norm=None):
         """Skip steps whose gradients are not finite and, with ``max_norm``, clip by the global 2-norm -- on the device, see the
@@ -200,6 +230,14 @@ class Adam(torch.optim.Optimizer):
             raise RuntimeError("srgan_amd.optim.Adam: max_norm changed inside a hipGraph capture")
         ops.grad_guard_state_set_max_norm(guard.state, max_norm)
         guard.max_norm = max_norm
+
+    def set_grad_guard_counters(self, steps, skipped, clipped):
+        """Resume: write a checkpoint's cumulative counters into the device record, between steps; the threshold and the last
+        step's decision stay."""
+        guard = self._need_guard("set_grad_guard_counters")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("srgan_amd.optim.Adam: guard counters written inside a hipGraph capture")
+        ops.grad_guard_state_set_counters(guard.state, steps, skipped, clipped)
 
     def grad_guard_stats(self):
         """{"max_norm", "norm", "scale", "skip", "steps", "skipped", "clipped"} read from the device record: norm / scale / skip

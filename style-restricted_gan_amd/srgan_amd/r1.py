@@ -97,6 +97,23 @@ class R1Penalty:
                 raise RuntimeError("set_r1_gamma inside a hipGraph capture")
             ops.r1_state_set(self.state, self.gamma, self.every, self._n)
 
+    def set_updates(self, updates, device=None, n=None):
+        """Resume: write a checkpoint's count of penalised updates into the device record, between steps.  A penalty that has not
+        run yet has no record; it is made here for batch size ``n`` on ``device`` (the step re-derives ``c`` should its batch
+        differ).  Without a record and without ``n`` only a count of 0 can be taken: that is what a fresh record starts at."""
+        if _capturing():
+            raise RuntimeError("R1Penalty: updates written inside a hipGraph capture")
+        updates = int(updates)
+        if updates < 0:
+            raise ValueError(f"R1Penalty: updates must be >= 0, got {updates}")
+        if self.state is None:
+            if n is None or device is None:
+                if updates:
+                    raise ValueError("R1Penalty: a count of updates without the batch size of its record (n)")
+                return
+            self._ensure(device, int(n))
+        ops.r1_state_set_updates(self.state, updates)
+
     @property
     def gamma_eff(self):
         return self.gamma * self.every

@@ -13,7 +13,9 @@ Same constructor / method signatures and return values as the reference class
   all-reduce (``srgan_amd.dp``) and the batch-statistics losses see the all-gathered mu.
 
 This module chooses the launches (the step body, ``_step``, the ``enable_*`` switches, ``SingleGAN_training``); how a fixed launch
-sequence is recorded into a hipGraph and replayed (``_StepGraph``, ``_Recording``) lives in ``srgan_amd.step_graph``.
+sequence is recorded into a hipGraph and replayed (``_StepGraph``, ``_Recording``) lives in ``srgan_amd.step_graph``; saving and
+resuming the whole trainer (``state_dict``, ``load_state_dict``, ``save_checkpoint``, ``load_checkpoint``) in
+``srgan_amd.checkpoint``.
 
 Semantics kept on purpose: stale ``target_image`` graph re-used after
 ``optG.step()`` with weights read at backward time; the no-op "unrolled" restore of D; corr/hist
@@ -30,6 +32,7 @@ import torch.optim as optim
 
 from . import dp, ema, ops, spectral
 from .augment import DiffAugment
+from .checkpoint import Checkpointing
 from . import r1 as _r1mod
 from .losses import class_encode, criterion_kind, get_domainloss_D, get_loss_D, has_fused_kind, histogram_imitation
 from .model import SingleGenerator, batch_stats_synced, host_to_device, per_sample
@@ -52,7 +55,7 @@ def _frozen(params):
             p.requires_grad_(f)
 
 
-class SRGAN_training():
+class SRGAN_training(Checkpointing):
     """
     net            : [G, D, E] nn.Modules          opt : [optG, optD, optE] (None -> fused HIP Adam)
     criterion      : [criterion, criterion_class]   (nn.MSELoss in every reference notebook; nn.BCEWithLogitsLoss / nn.BCELoss
@@ -932,7 +935,7 @@ def _select_rows(x, mask):
     return x.permute(0, 2, 3, 1)[mask].permute(0, 3, 1, 2)
 
 
-class SingleGAN_training():
+class SingleGAN_training(Checkpointing):
     """Conventional SingleGAN trainer on the HIP path -- BASELINE.json configs[0] (notebook 01).
 
     Same constructor / method signatures as the reference class (pyfiles/util_notebook.py:76-417):
