@@ -570,7 +570,12 @@ F43_CASES = [(32, 64, 32, 32, 128, True), (3, 64, 8, 12, 96, True), (5, 128, 16,
              (2, 256, 32, 32, 256, False)]
 SKIP_CASES = [(32, 64, 32, 32, 64), (3, 64, 8, 12, 64), (2, 16, 9, 7, 16), (2, 256, 32, 32, 256)]     # n, i, h, w, o
 SKIP_BF16_CASES = [(3, 64, 8, 32, 64), (2, 256, 32, 32, 256), (1, 128, 12, 64, 128)]
-NORM_ACT_CONV_CASES = [(32, 256, 256, True), (4, 64, 64, True), (3, 64, 96, False)]                  # n, c, o, affine (32 x 32 maps)
+# n, c, o, affine (32 x 32 maps); (3, 96, 64): c % 64 != 0, so no V image is kept (srgan_conv2d_wgrad_v_bytes == 0) and the backward of
+# ops._NormActConvFn recomputes the normalised input for srgan_conv2d_wgrad
+NORM_ACT_CONV_CASES = [(32, 256, 256, True), (4, 64, 64, True), (3, 64, 96, False), (3, 96, 64, True)]
+# n, i, o of tests/test_trunk_kernels_gpu.py (32 x 32 maps; tests/trunk_common.py names what each is there for)
+TRUNK_CASES = [(1, 32, 32), (3, 96, 64), (8, 64, 32), (16, 128, 96), (5, 256, 256), (1, 64, 32), (2, 64, 128), (2, 128, 64), (8, 64, 64),
+               (11, 128, 128), (2, 32, 32), (2, 64, 32)]
 RESBLOCK_CASES = [(32, 256), (4, 64), (3, 128)]                                                      # n, c (32 x 32 maps)
 RESBLOCK_BF16_CASES = [(32, 256, 32), (64, 64, 32), (32, 128, 32), (8, 256, 64)]                     # n, c, hw
 STRIDE2_IO_SHAPE = (2, 64, 128, 16, 64)                                                              # n, ci, co, h, w
@@ -706,10 +711,13 @@ COVERAGE = [
      ("m1",), ("default",), ("pack0", "fwd_packed", "pack1", "dgrad_packed_add")),
     # the fused nodes: V / Z images written by the norm kernels of conv_wino43.hip, multiply + weight gradient from them
     ("test_ops_gpu::test_instance_norm_act_conv_equals_the_unfused_chain", [full(n, c, 32, 32, o, 3, 1, 1) for n, c, o, _ in NORM_ACT_CONV_CASES],
-     ("m0",), ("forced",), ("pack0", "instnorm_fwd_v", "fwd_from_v", "pack1", "dgrad_packed", "wgrad_v")),
+     ("m0",), ("forced",), ("pack0", "instnorm_fwd_v", "fwd_from_v", "pack1", "dgrad_packed", "wgrad*")),
     ("test_ops_gpu::test_residual_block_fused_node_vs_chain_and_cpu", [full(n, c, 32, 32, c, 3, 1, 1) for n, c in RESBLOCK_CASES],
      ("m0",), ("forced",), ("pack0", "fwd_packed", "instnorm_fwd_v", "fwd_from_v", "pack1", "instnorm_bwd_vz", "dgrad_from_v",
                             "wgrad_vz", "dgrad_packed_add", "wgrad_v")),
+    # the same entries called one by one through ctypes, each composition against float64
+    ("test_trunk_kernels_gpu", [full(n, i, 32, 32, o, 3, 1, 1) for n, i, o in TRUNK_CASES], ("m0",), ("forced",),
+     ("pack0", "fwd_packed", "instnorm_fwd_v", "fwd_from_v", "pack1", "instnorm_bwd_vz", "dgrad_from_v", "wgrad_vz")),
     ("test_ops_gpu::test_residual_block_bf16_storage", [full(n, c, hw, hw, c, 3, 1, 1) for n, c, hw in RESBLOCK_BF16_CASES],
      ("m1",), ("default",), ("pack0", "pack1", "halo16_conv:kind0:in16=0:out16=1", "halo16_conv:kind0:in16=1:out16=1",      # ops._ResBlockBf16Fn's
                              "halo16_conv:kind1:in16=1:out16=1", "halo16_conv_res:in16=1",                                  # own calls, no others

@@ -263,6 +263,53 @@ def test_residual_block_fused_node_vs_chain_and_cpu(ops, n, c):
         close_grad(a, b.grad, 3e-4, what=name)
 
 
+def _residual_block_run(ops, n, c, needs):
+    """[out, gradients of (x, s1, h1, s2, h2, w1, w2)] of ops.residual_block; ``needs`` flags the inputs that take a gradient."""
+    import os
+    g = torch.Generator().manual_seed(41)
+    x = rnd(n, c, 32, 32, seed=41)
+    w1, w2 = rnd(c, c, 3, 3, seed=42) / np.sqrt(c * 9), rnd(c, c, 3, 3, seed=43) / np.sqrt(c * 9)
+    s1, s2 = torch.rand(n, c, generator=g) + 0.5, torch.rand(n, c, generator=g) + 0.5
+    h1, h2 = rnd(n, c, seed=44) * 0.3, rnd(n, c, seed=45) * 0.3
+    gy = rnd(n, c, 32, 32, seed=46)
+    os.environ["SRGAN_WINOGRAD_THRESHOLD_SCALE"] = "0"
+    try:
+        t = [v.cuda().requires_grad_(need) for v, need in zip((x, s1, h1, s2, h2, w1, w2), needs)]
+        ops.invalidate_packed()
+        with ops.pack_cache():
+            assert ops.res_block_fusable(t[0], t[5], t[6], t[1], t[3])
+            y = ops.residual_block(*t)
+            y.backward(gy.cuda())
+        torch.cuda.synchronize()
+    finally:
+        os.environ.pop("SRGAN_WINOGRAD_THRESHOLD_SCALE", None)
+        ops.invalidate_packed()
+    return [y.detach()] + [v.grad for v in t]
+
+
+def test_residual_block_without_weight_gradients_keeps_no_image(ops):
+    """w1, w2 detached: the node keeps no V image (both live in the shared workspace, one after the other) and launches no
+    weight gradient; the output and the gradients of x and of the affine parameters are those of the all-gradients run, bit for
+    bit."""
+    n, c = cc.RESBLOCK_CASES[1]
+    full = _residual_block_run(ops, n, c, (True,) * 7)
+    part = _residual_block_run(ops, n, c, (True,) * 5 + (False, False))
+    assert part[6] is None and part[7] is None and all(v is not None for v in full)
+    for name, a, b in zip(("out", "dx", "ds1", "dh1", "ds2", "dh2"), part, full):
+        assert torch.equal(a, b), name
+
+
+def test_residual_block_without_an_input_gradient(ops):
+    """x detached: no input gradient of c1 is launched; the weight and affine gradients are those of the all-gradients run,
+    bit for bit."""
+    n, c = cc.RESBLOCK_CASES[1]
+    full = _residual_block_run(ops, n, c, (True,) * 7)
+    part = _residual_block_run(ops, n, c, (False,) + (True,) * 6)
+    assert part[1] is None
+    for name, a, b in zip(("out", "ds1", "dh1", "ds2", "dh2", "dw1", "dw2"), part[:1] + part[2:], full[:1] + full[2:]):
+        assert torch.equal(a, b), name
+
+
 @pytest.mark.parametrize("n,c,hw", cc.RESBLOCK_BF16_CASES)
 def test_residual_block_bf16_storage(ops, n, c, hw):
     """bf16 mode: the residual block as one node with bf16 INTERMEDIATES in HBM (ops._ResBlockBf16Fn: conv outputs, normalised
