@@ -566,6 +566,46 @@ int srgan_diffaugment_fwd(const float* x0, int n0, const float* x1, int n1, cons
 /* table: the n rows of 8 floats [b, s, a, ty, tx, cy, cx, 0] the forward of these samples read */
 int srgan_diffaugment_bwd(const float* gy, const float* table, float* gx, int n, int c, int h, int w, int flags, int cut_h,
                           int cut_w, void* ws, size_t ws_bytes, void* stream);
+/* Gated forms (adaptive augmentation, below): the same arguments, and slot 7 of a table row is a skip mask -- an exact float in
+ * 0..7 with the bits of flags (whatever the float holds, it is clamped as the table's integers are and masked with 7: 8.0 and
+ * 1e30 read 0, -1.0 reads 7, a NaN reads 0).  A group whose bit is set is not applied to that sample: sample n with mask m comes
+ * out, forward and backward and on both access paths, bit for bit as the ungated entry point gives it with flags & ~m; all
+ * launched groups skipped: y is a bit copy of x, gx of gy.  The partial sums of a sample whose colour bit is skipped are neither
+ * written nor read.  The ungated entry points never read slot 7. */
+int srgan_diffaugment_fwd_gated(const float* x0, int n0, const float* x1, int n1, const float* table, float* y, int c, int h,
+                                int w, int flags, int cut_h, int cut_w, void* ws, size_t ws_bytes, void* stream);
+int srgan_diffaugment_bwd_gated(const float* gy, const float* table, float* gx, int n, int c, int h, int w, int flags, int cut_h,
+                                int cut_w, void* ws, size_t ws_bytes, void* stream);
+
+/* Adaptive discriminator augmentation (Karras et al., 2020, "Training Generative Adversarial Networks with Limited Data"): the
+ * probability p with which each DiffAugment group is applied to a sample, moved on the device by the overfitting heuristic
+ * r = E[sign(D(real) - thr)].  Extension, no counterpart in the reference.  Record (srgan_ada_state_bytes() = 56 bytes, device
+ * memory, 8-byte aligned):
+ *   offset  0 float p          4 float target     8 float step      12 float p_max    16 int interval    20 int seen
+ *          24 int64 n_pos     32 int64 n_neg     40 int64 n_total   48 int adjustments 52 float last_r
+ * srgan_ada_state_init writes p and the settings and zeroes the counters; srgan_ada_state_set rewrites target, step, p_max,
+ * interval and (set_p != 0) p and keeps the counters; srgan_ada_state_set_counters writes seen, the three counts, adjustments and
+ * last_r and nothing else (resuming from a checkpoint).  One one-thread launch each, stream-ordered.
+ * srgan_ada_gate: rows = n rows of 16 floats [b, s, a, ty, tx, cy, cx, -, u_colour, u_translation, u_cutout, -, -, -, -, -] (the
+ * uniforms in [0, 1)); one launch, one thread per sample, reads p from the record and writes the n rows of 8 floats the gated
+ * entry points above read: slots 0..6 copied bit for bit, slot 7 = the float of the mask whose bit g is set iff !(u_g < p)
+ * (p = 0 skips every group, p = 1 none, a NaN uniform skips).  rows and table 16-byte aligned, not aliased.
+ * srgan_ada_observe: maps[s] = fp32 map of scale s (n_scales <= 4), per_sample[s] its elements per row (both host arrays, read
+ * before the call returns), rows_first = B the real rows at the front of each map.  One launch of one workgroup: over rows [0, B)
+ * of every scale n_pos += #(v > thr), n_neg += #(v < thr), n_total += #elements (a NaN counts in n_total only), seen += 1, and
+ * once seen reaches interval: r = float(n_pos - n_neg) / float(n_total), p = min(max(p + sign(r - target) * step, 0), p_max) (sign
+ * 0 at equality; one fp32 add, then the clamp), last_r = r, adjustments += 1, the three counts and seen back to 0.  thr: 0.5 for
+ * nn.MSELoss against the targets 1 / 0, 0 for nn.BCEWithLogitsLoss.  Integer counts: exact in any order; plain stores, no atomics.
+ * -1 with srgan_last_error() before any launch: a NULL pointer, n <= 0, n_scales outside 1..4, B <= 0, a row count <= 0, a
+ * setting out of range (target or thr not finite, step < 0, not 0 <= p <= p_max <= 1, interval < 1, a negative count). */
+size_t srgan_ada_state_bytes(void);
+int srgan_ada_state_init(void* state, float p, float target, float step, float p_max, int interval, void* stream);
+int srgan_ada_state_set(void* state, float target, float step, float p_max, int interval, int set_p, float p, void* stream);
+int srgan_ada_state_set_counters(void* state, int seen, long long n_pos, long long n_neg, long long n_total, int adjustments,
+                                 float last_r, void* stream);
+int srgan_ada_gate(const float* rows, const void* state, float* table, int n, void* stream);
+int srgan_ada_observe(const float* const* maps, const long long* per_sample, int n_scales, int rows_first, float thr, void* state,
+                      void* stream);
 
 /* R1 gradient penalty on real samples (Mescheder et al., 2018), gamma / 2 * E_x |grad_x D(x)|^2, for the two-scale discriminator.
  * Extension, no counterpart in the reference.  The convolution passes are the ordinary entry points above (srgan_amd/r1.py drives

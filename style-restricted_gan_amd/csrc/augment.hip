@@ -16,6 +16,12 @@
 //                       pixel t + 256 k); the gather reads the same 48 bytes at a 4-byte aligned address when all four pixels exist.
 // No atomics, every sum has one owner and a fixed order that depends on H and W only: a sample's result does not depend on N, on
 // its position in the batch or on the grid.  fp contraction is off: both paths of a kernel round alike.
+//
+// Gated form (srgan_diffaugment_fwd_gated / _bwd_gated; adaptive augmentation, csrc/ada.hip writes the tables): slot 7 of a row is
+// a skip mask, an exact float in 0..7 with the bits of flags.  A group whose bit is set is not applied to that sample -- no colour
+// arithmetic, shift (0, 0), empty window -- so the sample comes out as the ungated kernels give it with flags & ~mask, bit for bit;
+// all launched groups skipped: a bit copy.  An item belongs to one sample: the branch is uniform per workgroup iteration.  The
+// partial sums of a sample whose colour bit is skipped are neither written nor read.  The ungated kernels never read slot 7.
 #include "common.h"
 #include <algorithm>
 #include <cstdint>
@@ -28,7 +34,7 @@ constexpr int kAugChunk = 4096;        // floats per partial sum
 constexpr int kAugItemPixels = 2048;   // pixels per item of the apply pass
 constexpr int kAugGridCap = 2048;      // 256 CUs x 8 workgroups; the rest by grid stride
 constexpr int kAugRow = 8;             // floats per table row
-enum { AUG_B, AUG_S, AUG_A, AUG_TY, AUG_TX, AUG_CY, AUG_CX };
+enum { AUG_B, AUG_S, AUG_A, AUG_TY, AUG_TX, AUG_CY, AUG_CX, AUG_SKIP };
 
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));     // a 16-byte access at a 4-byte aligned address
 
@@ -41,15 +47,23 @@ struct AugGeom {
 // a table integer; whatever the float holds, the index arithmetic below stays inside int (|value| <= 2^29, a NaN reads -2^29)
 __device__ __forceinline__ int aug_int(float v) { return (int)fminf(fmaxf(v, -536870912.f), 536870912.f); }
 
-template <int FLAGS, bool BWD>
-__device__ __forceinline__ AugGeom aug_geom(const float* __restrict__ row, int H, int W, int ch, int cw) {
+// the groups that run for the sample of `row`: the launch's, less (gated form) those of the row's skip mask.  Whatever slot 7
+// holds, the mask is in 0..7 (8.0 and 1e30 read 0, -1.0 reads 7, a NaN reads 0).
+template <int FLAGS, bool GATED>
+__device__ __forceinline__ int aug_flags(const float* __restrict__ row) {
+  return GATED ? (FLAGS & ~(aug_int(row[AUG_SKIP]) & 7)) : FLAGS;
+}
+
+// `flags`: aug_flags() of the sample, a compile-time constant in the ungated kernels
+template <bool BWD>
+__device__ __forceinline__ AugGeom aug_geom(const float* __restrict__ row, int H, int W, int ch, int cw, int flags) {
   AugGeom g = {H, W, 0, 0, 0, 0, 0, 0};
-  if (FLAGS & 2) {                        // a shift of the whole size already moves everything out
+  if (flags & 2) {                        // a shift of the whole size already moves everything out
     g.dy = min(max(aug_int(row[AUG_TY]), -H), H);
     g.dx = min(max(aug_int(row[AUG_TX]), -W), W);
     if (BWD) { g.dy = -g.dy; g.dx = -g.dx; }
   }
-  if (FLAGS & 4) {
+  if (flags & 4) {
     g.r0 = aug_int(row[AUG_CY]) - ch / 2;
     g.c0 = aug_int(row[AUG_CX]) - cw / 2;
     g.r1 = g.r0 + ch;
@@ -110,7 +124,7 @@ __device__ __forceinline__ const float* aug_sample(const float* __restrict__ x0,
   return n < n0 ? x0 + (size_t)n * E : x1 + (size_t)(n - n0) * E;
 }
 
-template <int FLAGS, bool BWD>
+template <int FLAGS, bool BWD, bool GATED>
 __global__ __launch_bounds__(256) void aug_sum_partials_kernel(const float* __restrict__ x0, int n0, const float* __restrict__ x1,
                                                                const float* __restrict__ table, float* __restrict__ part, int H, int W,
                                                                int ch, int cw, int nchunk, long long items, int vec) {
@@ -119,7 +133,9 @@ __global__ __launch_bounds__(256) void aug_sum_partials_kernel(const float* __re
   for (long long it = blockIdx.x; it < items; it += gridDim.x) {
     const int n = (int)(it / nchunk), chunk = (int)(it - (long long)n * nchunk);
     const float* src = aug_sample(x0, n0, x1, n, (size_t)E);
-    const AugGeom g = aug_geom<FLAGS, false>(table + (size_t)n * kAugRow, H, W, ch, cw);    // gy is indexed by the OUTPUT pixel
+    const int F = aug_flags<FLAGS, GATED>(table + (size_t)n * kAugRow);
+    if (GATED && !(F & 1)) continue;                                 // colour skipped for this sample: nobody reads its partials
+    const AugGeom g = aug_geom<false>(table + (size_t)n * kAugRow, H, W, ch, cw, F);        // gy is indexed by the OUTPUT pixel
     float acc = 0.f;
 #pragma unroll
     for (int jv = 0; jv < 4; ++jv) {
@@ -133,7 +149,7 @@ __global__ __launch_bounds__(256) void aug_sum_partials_kernel(const float* __re
         for (int q = 0; q < 4; ++q)
           if (e0 + q < E) v[q] = src[e0 + q];
       }
-      if (BWD && (FLAGS & 6)) {                                      // the gradient of a pixel no output reads does not count
+      if (BWD && (F & 6)) {                                          // the gradient of a pixel no output reads does not count
         int p = e0 / 3, c = e0 - 3 * p;
         int i = p / W, j = p - i * W;
         bool keep = aug_reads<false>(g, i, j);                       // the forward's test: not cut, and its source pixel exists
@@ -157,9 +173,10 @@ __global__ __launch_bounds__(256) void aug_sum_partials_kernel(const float* __re
 }
 
 // four consecutive pixels starting at pixel p0 (p0 % 4 == 0, all four exist)
+// FLAGS: the launch's (may the read address be off 16-byte alignment?); F: the sample's
 template <int FLAGS, bool BWD>
 __device__ __forceinline__ void aug_quad(const float* __restrict__ src, float* __restrict__ dst, const AugGeom& g, const AugColour& k,
-                                         int p0) {
+                                         int p0, int F) {
   int i = p0 / g.W, j = p0 - i * g.W;
   bool rd[4];
   bool all = true;
@@ -187,7 +204,7 @@ __device__ __forceinline__ void aug_quad(const float* __restrict__ src, float* _
       for (int c = 0; c < 3; ++c) v[3 * q + c] = rd[q] ? s[3 * q + c] : 0.f;
     }
   }
-  if (FLAGS & 1) {
+  if (F & 1) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       if (BWD || rd[q]) aug_pixel<BWD>(k, v[3 * q], v[3 * q + 1], v[3 * q + 2]);      // forward: a zero pixel stays zero
@@ -201,19 +218,19 @@ __device__ __forceinline__ void aug_quad(const float* __restrict__ src, float* _
   }
 }
 
-template <int FLAGS, bool BWD>
+template <bool BWD>
 __device__ __forceinline__ void aug_one(const float* __restrict__ src, float* __restrict__ dst, const AugGeom& g, const AugColour& k,
-                                        int p) {
+                                        int p, int F) {
   const int i = p / g.W, j = p - i * g.W;
   const bool rd = aug_reads<BWD>(g, i, j);
   const float* s = src + ((long long)p + (long long)g.dy * g.W + g.dx) * 3;
   float v0 = rd ? s[0] : 0.f, v1 = rd ? s[1] : 0.f, v2 = rd ? s[2] : 0.f;
-  if ((FLAGS & 1) && (BWD || rd)) aug_pixel<BWD>(k, v0, v1, v2);
+  if ((F & 1) && (BWD || rd)) aug_pixel<BWD>(k, v0, v1, v2);
   float* d = dst + (size_t)p * 3;
   d[0] = v0; d[1] = v1; d[2] = v2;
 }
 
-template <int FLAGS, bool BWD>
+template <int FLAGS, bool BWD, bool GATED>
 __global__ __launch_bounds__(256) void aug_apply_kernel(const float* __restrict__ x0, int n0, const float* __restrict__ x1,
                                                         const float* __restrict__ table, const float* __restrict__ part,
                                                         float* __restrict__ y, int H, int W, int ch, int cw, int nchunk, int nitem,
@@ -226,9 +243,10 @@ __global__ __launch_bounds__(256) void aug_apply_kernel(const float* __restrict_
     const float* src = aug_sample(x0, n0, x1, n, E);
     float* dst = y + (size_t)n * E;
     const float* row = table + (size_t)n * kAugRow;
-    const AugGeom g = aug_geom<FLAGS, BWD>(row, H, W, ch, cw);
+    const int F = aug_flags<FLAGS, GATED>(row);
+    const AugGeom g = aug_geom<BWD>(row, H, W, ch, cw, F);
     AugColour k = {0.f, 0.f, 0.f, 0.f};
-    if (FLAGS & 1) {
+    if (F & 1) {
       float sum = 0.f;
       for (int c = threadIdx.x; c < nchunk; c += 256) sum += part[(size_t)n * nchunk + c];
       sum = aug_block_sum(sum, red);
@@ -239,13 +257,13 @@ __global__ __launch_bounds__(256) void aug_apply_kernel(const float* __restrict_
 #pragma unroll
       for (int u = 0; u < kAugItemPixels / 1024; ++u) {
         const int p0 = base + (u * 256 + (int)threadIdx.x) * 4;
-        if (p0 < P) aug_quad<FLAGS, BWD>(src, dst, g, k, p0);
+        if (p0 < P) aug_quad<FLAGS, BWD>(src, dst, g, k, p0, F);
       }
     } else {
 #pragma unroll 2
       for (int u = 0; u < kAugItemPixels / 256; ++u) {
         const int p = base + u * 256 + (int)threadIdx.x;
-        if (p < P) aug_one<FLAGS, BWD>(src, dst, g, k, p);
+        if (p < P) aug_one<BWD>(src, dst, g, k, p, F);
       }
     }
   }
@@ -265,17 +283,17 @@ static bool aug_plan(int n, int h, int w, AugPlan* p) {
 
 static unsigned aug_grid(long long items) { return (unsigned)std::min<long long>(items, kAugGridCap); }
 
-template <int FLAGS, bool BWD>
+template <int FLAGS, bool BWD, bool GATED>
 static void aug_launch(const float* x0, int n0, const float* x1, const float* table, float* y, int h, int w, int ch, int cw,
                        const AugPlan& p, float* ws, int vec, hipStream_t st) {
   if constexpr ((FLAGS & 1) != 0)
-    hipLaunchKernelGGL((aug_sum_partials_kernel<FLAGS, BWD>), dim3(aug_grid(p.sum_items)), dim3(256), 0, st, x0, n0, x1, table, ws, h, w,
-                       ch, cw, p.nchunk, p.sum_items, vec);
-  hipLaunchKernelGGL((aug_apply_kernel<FLAGS, BWD>), dim3(aug_grid(p.apply_items)), dim3(256), 0, st, x0, n0, x1, table,
+    hipLaunchKernelGGL((aug_sum_partials_kernel<FLAGS, BWD, GATED>), dim3(aug_grid(p.sum_items)), dim3(256), 0, st, x0, n0, x1,
+                       table, ws, h, w, ch, cw, p.nchunk, p.sum_items, vec);
+  hipLaunchKernelGGL((aug_apply_kernel<FLAGS, BWD, GATED>), dim3(aug_grid(p.apply_items)), dim3(256), 0, st, x0, n0, x1, table,
                      static_cast<const float*>(ws), y, h, w, ch, cw, p.nchunk, p.nitem, p.apply_items, vec);
 }
 
-template <bool BWD>
+template <bool BWD, bool GATED>
 static int aug_run(const char* what, const float* x0, int n0, const float* x1, int n1, const float* table, float* y, int c, int h,
                    int w, int flags, int ch, int cw, void* ws, size_t ws_bytes, void* stream) {
   SRGAN_REQUIRE(c == 3, "%s: C = %d (three-channel images only)", what, c);
@@ -297,7 +315,7 @@ static int aug_run(const char* what, const float* x0, int n0, const float* x1, i
   hipStream_t st = as_stream(stream);
   float* wsf = static_cast<float*>(ws);
   switch (flags) {
-#define AUG_CASE(F) case F: aug_launch<F, BWD>(x0, n0, x1, table, y, h, w, ch, cw, p, wsf, vec, st); break;
+#define AUG_CASE(F) case F: aug_launch<F, BWD, GATED>(x0, n0, x1, table, y, h, w, ch, cw, p, wsf, vec, st); break;
     AUG_CASE(0) AUG_CASE(1) AUG_CASE(2) AUG_CASE(3) AUG_CASE(4) AUG_CASE(5) AUG_CASE(6) AUG_CASE(7)
 #undef AUG_CASE
   }
@@ -319,10 +337,20 @@ extern "C" size_t srgan_diffaugment_workspace(int n, int h, int w) {
 
 extern "C" int srgan_diffaugment_fwd(const float* x0, int n0, const float* x1, int n1, const float* table, float* y, int c, int h,
                                      int w, int flags, int cut_h, int cut_w, void* ws, size_t ws_bytes, void* stream) {
-  return aug_run<false>("diffaugment_fwd", x0, n0, x1, n1, table, y, c, h, w, flags, cut_h, cut_w, ws, ws_bytes, stream);
+  return aug_run<false, false>("diffaugment_fwd", x0, n0, x1, n1, table, y, c, h, w, flags, cut_h, cut_w, ws, ws_bytes, stream);
 }
 
 extern "C" int srgan_diffaugment_bwd(const float* gy, const float* table, float* gx, int n, int c, int h, int w, int flags,
                                      int cut_h, int cut_w, void* ws, size_t ws_bytes, void* stream) {
-  return aug_run<true>("diffaugment_bwd", gy, n, nullptr, 0, table, gx, c, h, w, flags, cut_h, cut_w, ws, ws_bytes, stream);
+  return aug_run<true, false>("diffaugment_bwd", gy, n, nullptr, 0, table, gx, c, h, w, flags, cut_h, cut_w, ws, ws_bytes, stream);
+}
+
+extern "C" int srgan_diffaugment_fwd_gated(const float* x0, int n0, const float* x1, int n1, const float* table, float* y, int c, int h,
+                                           int w, int flags, int cut_h, int cut_w, void* ws, size_t ws_bytes, void* stream) {
+  return aug_run<false, true>("diffaugment_fwd_gated", x0, n0, x1, n1, table, y, c, h, w, flags, cut_h, cut_w, ws, ws_bytes, stream);
+}
+
+extern "C" int srgan_diffaugment_bwd_gated(const float* gy, const float* table, float* gx, int n, int c, int h, int w, int flags,
+                                           int cut_h, int cut_w, void* ws, size_t ws_bytes, void* stream) {
+  return aug_run<true, true>("diffaugment_bwd_gated", gy, n, nullptr, 0, table, gx, c, h, w, flags, cut_h, cut_w, ws, ws_bytes, stream);
 }

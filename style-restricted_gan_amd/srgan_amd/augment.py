@@ -52,6 +52,7 @@ class DiffAugment:
         else:
             self.generator.manual_seed(int(seed))
         self.draw_fn = self.draw               # tests may inject callable(n, h, w) -> CPU float32 [n, 8]
+        self.gate_fn = self.draw_gate          # ... and callable(n) -> CPU float32 [n, 3] (adaptive augmentation only)
 
     @property
     def flags(self):
@@ -81,12 +82,18 @@ class DiffAugment:
             t[:, 6] = torch.randint(0, w + (1 - cw % 2), (n,), generator=g).to(torch.float32)
         return t
 
-    def apply(self, x, table):
-        """``table``: device float32 [n, 8]"""
+    def draw_gate(self, n):
+        """One CPU float32 [n, 3] of uniforms in [0, 1) for n images: colour, translation, cutout.  Adaptive augmentation
+        (``srgan_amd.ada``) applies group g to a sample iff ``u_g < p``; drawn after the sample's table, from the same generator,
+        and only with that feature on."""
+        return torch.rand(n, 3, generator=self.generator, dtype=torch.float32)
+
+    def apply(self, x, table, gated=False):
+        """``table``: device float32 [n, 8]; ``gated``: its slot 7 holds the per-sample skip mask (``ops.ada_gate``)"""
         flags = self.flags
         if flags == 0:
             return x
-        return ops.diffaugment(x, table, flags, self.cut(x.shape[2], x.shape[3]))
+        return ops.diffaugment(x, table, flags, self.cut(x.shape[2], x.shape[3]), gated)
 
     def __call__(self, x):
         """Draw, copy to the device, apply: for a training loop of one's own (differentiable in x)."""
@@ -98,7 +105,8 @@ class DiffAugment:
 
     def fingerprint(self):
         """what a recorded step bakes in: the groups launched, the window ratios, the draw source"""
-        return (id(self), self.flags, self.translation, self.cutout, id(getattr(self.draw_fn, "__func__", self.draw_fn)))
+        return (id(self), self.flags, self.translation, self.cutout, id(getattr(self.draw_fn, "__func__", self.draw_fn)),
+                id(getattr(self.gate_fn, "__func__", self.gate_fn)))
 
     def graph_keepalive(self):
         """device buffers a recorded step points at: none (the tables are staged by the recording's owner)"""

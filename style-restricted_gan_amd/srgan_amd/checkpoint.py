@@ -10,9 +10,10 @@ dict`` -- a file written from it loads with ``torch.load(path, weights_only=True
     G, D, E                  ``state_dict()`` of the unwrapped networks, the reference's keys (D: a list for per-domain discriminators)
     optG/D/E, scheG/D/E      ``state_dict()`` of the optimisers and schedulers (lists where the trainer keeps lists)
     hist_target              the histogram-imitation target the constructor drew (``lbd["hist"] > 0``)
-    ema, augment, r1,        the step's extensions that are on: the averaged copies and their update count, DiffAugment's settings
-    grad_guard               and generator, R1's gamma / every / updates (and the record's batch size n), per guarded net max_norm
-                             and the cumulative steps / skipped / clipped
+    ema, augment, ada, r1,   the step's extensions that are on: the averaged copies and their update count, DiffAugment's settings
+    grad_guard               and generator, the adaptive probability's settings and whole record (p, seen, the three counts,
+                             adjustments, last_r, the record's batch size n), R1's gamma / every / updates (and the record's batch
+                             size n), per guarded net max_norm and the cumulative steps / skipped / clipped
     rng                      the CPU default generator (style and reparametrisation noise) and numpy's global one (``get_target``)
 
 Not saved: the last step's images, ``loss_terms``, the label cache, workspaces, packed operands, the guard's decision and R1's
@@ -41,7 +42,7 @@ LoadReport.__doc__ = """Sections the trainer has but the checkpoint lacks (they 
 use for (skipped)."""
 
 _NETS = ("G", "D", "E")
-_EXTENSIONS = ("ema", "augment", "r1", "grad_guard")
+_EXTENSIONS = ("ema", "augment", "ada", "r1", "grad_guard")
 
 
 def _plain(obj, where="state_dict"):
@@ -132,7 +133,7 @@ class Checkpointing:
         out += [n for n in ("optG", "optD", "optE", "scheG", "scheD", "scheE") if getattr(self, n, None) is not None]
         if getattr(self, "hi", None) is not None:
             out.append("hist_target")
-        for name, attr in (("ema", "_ema"), ("augment", "augment"), ("r1", "_r1")):
+        for name, attr in (("ema", "_ema"), ("augment", "augment"), ("ada", "_ada"), ("r1", "_r1")):
             if getattr(self, attr, None) is not None:
                 out.append(name)
         out += [f"grad_guard.{n}" for n in self._ckpt_guards()]
@@ -159,7 +160,7 @@ class Checkpointing:
     # ---- save ---------------------------------------------------------------------------------------------------------------------
     def state_dict(self, rng=True):
         """A snapshot of everything the next ``train()`` depends on (module docstring): CPU clones and plain values.  Between steps
-        only; reads the R1 and gradient-guard records, so it SYNCHRONISES the stream.  ``rng=False`` leaves the two host
+        only; reads the adaptive-probability, R1 and gradient-guard records, so it SYNCHRONISES the stream.  ``rng=False`` leaves the two host
         generators out.  Per process: no collective."""
         self._ckpt_between_steps("state_dict")
         sd = {"version": VERSION, "config": self._ckpt_config()}
@@ -175,6 +176,8 @@ class Checkpointing:
             sd["ema"] = _plain(self._ema.state_dict(), "ema")
         if getattr(self, "augment", None) is not None:
             sd["augment"] = _plain(self.augment.state_dict(), "augment")
+        if getattr(self, "_ada", None) is not None:
+            sd["ada"] = _plain(self._ada.state_dict(), "ada")
         r1 = getattr(self, "_r1", None)
         if r1 is not None:
             st = r1.stats()
@@ -296,6 +299,11 @@ class Checkpointing:
             if self.augment is None:
                 self.enable_diffaugment(a["policy"], a["translation"], a["cutout"])
             self.augment.load_state_dict(a)
+        if use("ada"):
+            a = sd["ada"]
+            if self._ada is None or self._ada.interval != int(a["interval"]):
+                self.enable_ada(a["target"], int(a["interval"]), a["kimg"], a["p"], a["p_max"])
+            self._ada.load_state_dict(a, next(dp.unwrap(self.D).parameters()).device)
         if use("r1"):
             r = sd["r1"]
             if self._r1 is None or self._r1.every != int(r["every"]):

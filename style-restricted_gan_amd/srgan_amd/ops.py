@@ -2577,47 +2577,51 @@ def _aug_workspace(lib, flags, n, h, w, device):
     return workspace(device, nb), nb
 
 
-def _aug_fwd(xs, table, flags, cut, geom):
+def _aug_fwd(xs, table, flags, cut, geom, gated=False):
     n, h, w = geom
     lib = _lib.load()
     y = nhwc_empty(n, 3, h, w, xs[0].device)
     ws, nb = _aug_workspace(lib, flags, n, h, w, y.device)
     x1 = xs[1] if len(xs) > 1 else None
-    _lib.check(lib.srgan_diffaugment_fwd(_ptr(xs[0]), xs[0].shape[0], _ptr(x1), x1.shape[0] if x1 is not None else 0, _ptr(table),
-                                         _ptr(y), 3, h, w, flags, cut[0], cut[1], _ptr(ws), nb, _stream()), "diffaugment_fwd")
+    fwd = lib.srgan_diffaugment_fwd_gated if gated else lib.srgan_diffaugment_fwd
+    _lib.check(fwd(_ptr(xs[0]), xs[0].shape[0], _ptr(x1), x1.shape[0] if x1 is not None else 0, _ptr(table), _ptr(y), 3, h, w, flags, cut[0],
+                   cut[1], _ptr(ws), nb, _stream()), "diffaugment_fwd_gated" if gated else "diffaugment_fwd")
     return y
 
 
 class _DiffAugmentFn(Function):
     @staticmethod
-    def forward(ctx, x, table, flags, cut):
+    def forward(ctx, x, table, flags, cut, gated=False):
         xs, table, flags, cut, geom = _aug_args("diffaugment", [x], table, flags, cut)
         ctx.save_for_backward(table)
-        ctx.aug = (flags, cut, geom)
-        return _aug_fwd(xs, table, flags, cut, geom)
+        ctx.aug = (flags, cut, geom, bool(gated))
+        return _aug_fwd(xs, table, flags, cut, geom, bool(gated))
 
     @staticmethod
     def backward(ctx, gy):
         (table,) = ctx.saved_tensors
-        flags, cut, (n, h, w) = ctx.aug
+        flags, cut, (n, h, w), gated = ctx.aug
         gy = to_nhwc(gy)
         lib = _lib.load()
         gx = nhwc_empty(n, 3, h, w, gy.device)
         ws, nb = _aug_workspace(lib, flags, n, h, w, gy.device)
-        _lib.check(lib.srgan_diffaugment_bwd(_ptr(gy), _ptr(table), _ptr(gx), n, 3, h, w, flags, cut[0], cut[1], _ptr(ws), nb,
-                                             _stream()), "diffaugment_bwd")
-        return gx, None, None, None
+        bwd = lib.srgan_diffaugment_bwd_gated if gated else lib.srgan_diffaugment_bwd
+        _lib.check(bwd(_ptr(gy), _ptr(table), _ptr(gx), n, 3, h, w, flags, cut[0], cut[1], _ptr(ws), nb, _stream()),
+                   "diffaugment_bwd_gated" if gated else "diffaugment_bwd")
+        return gx, None, None, None, None
 
 
-def diffaugment(x, table, flags, cut):
+def diffaugment(x, table, flags, cut, gated=False):
     """DiffAugment of a batch ``x[N, 3, H, W]``: colour, then translation, then cutout, whichever of them ``flags`` names
     (AUG_COLOR | AUG_TRANSLATION | AUG_CUTOUT), from one device row ``[b, s, a, ty, tx, cy, cx, 0]`` of ``table[N, 8]`` per sample
     and the cutout window ``cut = (ch, cw)``.  Differentiable in ``x`` only.  Two launches each way with colour on, one without;
-    hipGraph-capturable."""
-    return _DiffAugmentFn.apply(x, table, flags, cut)
+    hipGraph-capturable.  ``gated``: slot 7 of a row is a skip mask (an exact float in 0..7, the bits of ``flags``; ``ada_gate``
+    writes it) and a group whose bit is set is not applied to that sample, forward and backward: the sample comes out bit for bit
+    as the ungated pass gives it with ``flags & ~mask``."""
+    return _DiffAugmentFn.apply(x, table, flags, cut, gated)
 
 
-def diffaugment_cat(xs, table, flags, cut):
+def diffaugment_cat(xs, table, flags, cut, gated=False):
     """``diffaugment`` of the batch ``cat_batch(xs)`` (one or two sources) written in the same pass -- the discriminator update's
     real and fake halves.  Forward only: an input that requires grad is refused."""
     if not 1 <= len(xs) <= 2:
@@ -2626,7 +2630,75 @@ def diffaugment_cat(xs, table, flags, cut):
         raise _lib.SrganHipError("diffaugment_cat: an input requires grad; this form has no backward (detach it, or use diffaugment)")
     with torch.no_grad():
         xs, table, flags, cut, geom = _aug_args("diffaugment_cat", list(xs), table, flags, cut)
-        return _aug_fwd(xs, table, flags, cut, geom)
+        return _aug_fwd(xs, table, flags, cut, geom, bool(gated))
+
+
+# ---- adaptive discriminator augmentation: p on the device (srgan_amd.ada; extension, no counterpart in the reference) -----------
+ADA_ROW = 16                   # floats per row the gate reads: [b, s, a, ty, tx, cy, cx, -, u_colour, u_translation, u_cutout, 5 x -]
+ADA_MAX_SCALES = 4
+_ADA_FMT = "ffffiiqqqif"       # the record (include/srgan_hip.h): 56 bytes
+_ADA_FIELDS = ("p", "target", "step", "p_max", "interval", "seen", "n_pos", "n_neg", "n_total", "adjustments", "last_r")
+
+
+def ada_state_new(device, p, target, step, p_max, interval):
+    """Device-resident record {p, target, step, p_max, interval, seen, n_pos, n_neg, n_total, adjustments, last_r}, counters 0."""
+    lib = _lib.load()
+    st = torch.empty(lib.srgan_ada_state_bytes(), dtype=torch.uint8, device=device)
+    _lib.check(lib.srgan_ada_state_init(_ptr(st), float(p), float(target), float(step), float(p_max), int(interval), _stream()),
+               "ada_state_init")
+    return st
+
+
+def ada_state_set(state, target, step, p_max, interval, p=None):
+    """Rewrite target, step, p_max, interval and (``p`` given) p between steps; the counters stay (a recorded step reads the
+    record)."""
+    _lib.check(_lib.load().srgan_ada_state_set(_ptr(state), float(target), float(step), float(p_max), int(interval),
+                                               0 if p is None else 1, 0.0 if p is None else float(p), _stream()), "ada_state_set")
+
+
+def ada_state_set_counters(state, seen, n_pos, n_neg, n_total, adjustments, last_r):
+    """Write the heuristic's counters between steps (resume from a checkpoint); p and the settings stay."""
+    _lib.check(_lib.load().srgan_ada_state_set_counters(_ptr(state), int(seen), int(n_pos), int(n_neg), int(n_total),
+                                                        int(adjustments), float(last_r), _stream()), "ada_state_set_counters")
+
+
+def ada_state_read(state):
+    """The record as a dict; synchronises the current stream."""
+    torch.cuda.current_stream(state.device).synchronize()
+    return dict(zip(_ADA_FIELDS, struct.unpack(_ADA_FMT, state.cpu().numpy().tobytes()[:struct.calcsize(_ADA_FMT)])))
+
+
+def ada_gate(rows, state):
+    """One launch: device rows ``[n, 16]`` (a DiffAugment row in slots 0..6, the uniforms of the three groups in slots 8..10) and
+    the record's p -> the table ``[n, 8]`` of the gated ``diffaugment``: slots 0..6 copied, slot 7 the skip mask whose bit g is set
+    iff ``not u_g < p``.  hipGraph-capturable."""
+    _require_gpu(rows, "ada_gate rows")
+    if rows.dim() != 2 or rows.shape[1] != ADA_ROW or not rows.is_contiguous() or rows.shape[0] == 0:
+        raise _lib.SrganHipError(f"ada_gate: rows of shape {tuple(rows.shape)}, a contiguous [n, {ADA_ROW}] expected")
+    table = torch.empty(rows.shape[0], AUG_ROW, dtype=torch.float32, device=rows.device)
+    _lib.check(_lib.load().srgan_ada_gate(_ptr(rows), _ptr(state), _ptr(table), rows.shape[0], _stream()), "ada_gate")
+    return table
+
+
+def ada_observe_(outs, rows_first, thr, state):
+    """One launch of one workgroup: counts ``v > thr`` / ``v < thr`` / all over the first ``rows_first`` rows of the
+    discriminator's maps ``outs`` (fp32, what ``d_losses`` reads in both compute modes) into the record and, every ``interval``-th
+    call, moves p.  hipGraph-capturable; nothing comes back to the host."""
+    S = len(outs)
+    if not 1 <= S <= ADA_MAX_SCALES:
+        raise _lib.SrganHipError(f"ada_observe: {S} scales (1 to {ADA_MAX_SCALES})")
+    o = []
+    for t in outs:
+        t = t.detach()
+        _require_gpu(t, "ada_observe")
+        if t.dim() == 4 and t.shape[1] != 1:
+            raise _lib.SrganHipError("ada_observe: the maps must have one channel")
+        if t.shape[0] < rows_first:
+            raise _lib.SrganHipError(f"ada_observe: a map of {t.shape[0]} rows, {rows_first} real rows asked for")
+        o.append(t if (t.is_contiguous() or is_nhwc_dense(t)) else t.contiguous())
+    per = (ctypes.c_longlong * S)(*[t.numel() // t.shape[0] for t in o])
+    _lib.check(_lib.load().srgan_ada_observe((ctypes.c_void_p * S)(*[t.data_ptr() for t in o]), per, S, int(rows_first), float(thr),
+                                             _ptr(state), _stream()), "ada_observe")
 
 
 # ---- R1 gradient penalty on real samples (srgan_amd.r1; extension, no counterpart in the reference) ----------------------------

@@ -59,7 +59,7 @@ class _StepGraph:
         self.graph = None
         self.x = self.out = None
         self.staged_noise = _Staged("noise draws")            # [len(sg._noise_kinds()), B, ndim]
-        self.staged_aug = _Staged("DiffAugment tables")       # [2k + 1, B, 8] (no buffer with the feature off)
+        self.staged_aug = _Staged("DiffAugment tables")       # [2k + 1, B, row width] (no buffer with the feature off)
         self.lab = {}
         self._onehot = {}
         self._versions = None
@@ -259,9 +259,10 @@ class _StepGraph:
             self.table = torch.tensor(np.asarray(sg.ref_label), dtype=torch.float32).to(dev)
         n_aug = sg._aug_draws()
         if n_aug:
-            # the step's 2k + 1 tables, drawn up front in the order the eager step draws them (SRGAN_training._aug_tables)
+            # the step's 2k + 1 rows, drawn up front in the order the eager step draws them (SRGAN_training._aug_tables); what a row
+            # holds and how wide it is, is the trainer's business
             _, _, h, w = x.shape
-            self.staged_aug.stage([sg.augment.draw_fn(nb, h, w) for _ in range(n_aug)], dev)
+            self.staged_aug.stage([sg._aug_row_draw(nb, h, w) for _ in range(n_aug)], dev)
         self.x.copy_(x)
         self.staged_noise.stage(draws, dev)
         for w in ("source", "target"):

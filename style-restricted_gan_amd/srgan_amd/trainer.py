@@ -31,6 +31,7 @@ import torch.nn as nn
 import torch.optim as optim
 
 from . import dp, ema, ops, spectral
+from . import ada as _adamod
 from .augment import DiffAugment
 from .checkpoint import Checkpointing
 from . import r1 as _r1mod
@@ -98,6 +99,7 @@ class SRGAN_training(Checkpointing):
         self.G_ema = self.E_ema = None
         self._ema_scope = False        # inside ema_weights(): self.G / self.E are the copies
         self.augment = None            # DiffAugment of the discriminator's inputs (enable_diffaugment)
+        self._ada = None               # adaptive augmentation probability on the device (enable_ada)
         self._r1 = None                # R1 gradient penalty on the real rows (enable_r1)
         self._label_cache = {}         # (kind, which) -> (label tensor, its device form): _cached
         self._d_pending = None         # an update_D left its all-reduce / optimiser step to _finish_D: the reducer, or True
@@ -167,15 +169,29 @@ class SRGAN_training(Checkpointing):
         """Does the step augment what D reads?  (an empty policy is the plain step: no draw, no launch)"""
         return self.augment is not None and self.augment.flags != 0
 
+    def _aug_row_draw(self, nb, h, w):
+        """One host draw of the step: the CPU table [nb, 8] of ``draw_fn``; with adaptive augmentation on, followed by the three
+        uniforms per sample of ``gate_fn`` and joined into the [nb, 16] rows ``ops.ada_gate`` reads."""
+        table = self.augment.draw_fn(nb, h, w).to(torch.float32)
+        if self._ada is None:
+            return table
+        return _adamod.join_rows(table, self.augment.gate_fn(nb))
+
     def _aug_tables(self, count, nb, h, w):
         """The next ``count`` parameter tables of the step as ONE device tensor [count * nb, 8].  Draw order of a step
         (``_aug_draws``): per discriminator update the real rows' table, then the fake rows'; after the k updates phase 1's.  They
         come from the augmentation's own generator, never the default one.  Graph mode: drawn up front in the same order and
-        staged; this hands out the next slice of the static buffer."""
+        staged; this hands out the next slice of the static buffer.  Adaptive augmentation: the rows are [count * nb, 16] and go
+        through ONE ``ada_gate`` launch, which reads p and writes the tables with their skip masks."""
         if self._g_active:
-            return self._graph.staged_aug.next(count)
-        tabs = [self.augment.draw_fn(nb, h, w).to(torch.float32) for _ in range(count)]
-        return host_to_device(tabs[0] if count == 1 else torch.cat(tabs, 0), self.device)
+            rows = self._graph.staged_aug.next(count)
+        else:
+            tabs = [self._aug_row_draw(nb, h, w) for _ in range(count)]
+            rows = host_to_device(tabs[0] if count == 1 else torch.cat(tabs, 0), self.device)
+        if self._ada is None:
+            return rows
+        self._ada._ensure(rows.device, nb)
+        return self._ada.gate(rows)
 
     def _aug_draws(self):
         """tables a step consumes: 2 per discriminator update, 1 for phase 1"""
@@ -186,7 +202,7 @@ class SRGAN_training(Checkpointing):
         if not self._aug_on():
             return image
         n, _, h, w = image.shape
-        return self.augment.apply(image, self._aug_tables(1, n, h, w))
+        return self.augment.apply(image, self._aug_tables(1, n, h, w), gated=self._ada is not None)
 
     def _noise_kinds(self):
         """The step's noise draws in order (fused execution paths)."""
@@ -204,7 +220,7 @@ class SRGAN_training(Checkpointing):
         return (self.optG, self.optD, self.optE)
 
     def _extensions(self):
-        return [x for x in (self._ema, self._sn(), self.augment, self._r1) if x is not None]
+        return [x for x in (self._ema, self._sn(), self.augment, self._ada, self._r1) if x is not None]
 
     def _mirrors(self):
         """who mirrors, on the host, a device-side count that the step advances: Adam's step counts, the EMA's update count"""
@@ -390,19 +406,27 @@ class SRGAN_training(Checkpointing):
         else:
             self.target_image, self.c_rand = _fake
 
+        if self._ada is not None:
+            self._ada_check()
         if self._fused_paths():
             # real and fake halves through D as ONE batch (per-sample network: exact; 2x the rows per GEMM launch)
             B = self.source_image.shape[0]
             if self._aug_on():
                 # both halves augmented and concatenated in ONE pass (no gradient needed: real rows have none, fake rows are detached)
+                # adaptive augmentation: the two tables went through one gate launch of 2B rows (_aug_tables)
                 _, _, h, w = self.source_image.shape
                 d_in = ops.diffaugment_cat([self.source_image.detach(), self.target_image.detach()], self._aug_tables(2, B, h, w),
-                                           self.augment.flags, self.augment.cut(h, w))
+                                           self.augment.flags, self.augment.cut(h, w), gated=self._ada is not None)
                 d_real = d_in[:B]                          # what D read as the real rows (the R1 penalty is taken there)
             else:
                 d_in = ops.cat_batch([self.source_image, self.target_image.detach()])
                 d_real = self.source_image
             outs, logits = dp.unwrap(self.D).forward_logits(d_in)
+            if self._ada is not None:
+                # the overfitting heuristic on what D says about the real rows; every interval-th call moves p, so the p that
+                # gated THIS update's input is the one from before this observation
+                self._ada.observe(outs, B, _adamod.threshold(self._kinds()[0]))
+                self.loss_terms["ada_p"] = self._ada.p_tensor()
             # criterion(real, 1) + class loss * lbd + criterion(fake, 0) over both scales, values and gradients: one launch
             errD, parts = ops.d_losses(outs, logits, self._label_dev("source"), B, 1., 0., self.lbd["class"], *self._kinds())
             errD_real, errD_class, errD_fake = parts[0], parts[1], parts[2]
@@ -789,8 +813,70 @@ class SRGAN_training(Checkpointing):
         return self
 
     def disable_diffaugment(self):
+        """Also turns the adaptive probability off (``enable_ada``): there is nothing left to gate."""
         self.augment = None
+        self._ada = None
         self._guard_changed()
+
+    # ------------------------------------------------------------------------------------------
+    # adaptive augmentation probability (extension, no counterpart in the reference; srgan_amd.ada)
+    def _ada_check(self):
+        if not self._aug_on():
+            raise NotImplementedError("SRGAN_training: the adaptive probability gates DiffAugment's groups and "
+                                      + ("DiffAugment is off" if self.augment is None else "its policy is empty")
+                                      + " (enable_diffaugment(policy=...) first, or disable_ada())")
+        if dp.is_distributed():
+            raise NotImplementedError("SRGAN_training: the adaptive probability is on under a process group of several ranks; p "
+                                      "and the heuristic's counters would have to be agreed across the ranks (run one process, or "
+                                      "disable_ada())")
+        if not self._fused_paths():
+            raise NotImplementedError("SRGAN_training: the adaptive probability is wired into the fused discriminator pass only "
+                                      "(this package's own G / D / E modules with forward_logits, a one-hot ref_label, criteria "
+                                      "with a fused kernel); use those, or disable_ada()")
+
+    def enable_ada(self, target=0.6, interval=4, kimg=500.0, p=0.0, p_max=0.8):
+        """Adaptive discriminator augmentation (Karras et al., 2020) on top of ``enable_diffaugment``: from now on each group of the
+        policy is applied to a sample with probability p instead of always, and p follows the overfitting heuristic
+        ``r = E[sign(D(real) - thr)]`` over the real rows of both scales (thr: 0.5 for nn.MSELoss, 0 for nn.BCEWithLogitsLoss):
+        every ``interval`` discriminator updates p moves by ``step = B * interval / (kimg * 1000)`` up if ``r > target``, down if
+        ``r < target``, inside [0, ``p_max``].  p, the counters and the per-sample decisions are device state (``srgan_amd.ada``,
+        ``csrc/ada.hip``): captured with the step in graph mode (a recording made before is dropped), saved in a checkpoint.  Each
+        table is followed by three uniforms per sample from the augmentation's own generator; k observe + (k + 1) gate launches
+        per step (and k copies of p: ``loss_terms["ada_p"]``, a device scalar, is p after the step's last update).  The p that
+        gated an update's input is the one from before that update's observation.  R1 on top penalises at what D read.  Off:
+        draws, rows and launches are exactly DiffAugment's.  Refused: DiffAugment off or an empty policy, more than one rank,
+        the generic (non-fused) discriminator path."""
+        state = _adamod.AdaptiveP(target, interval, kimg, p, p_max)
+        self._ada = state
+        try:
+            self._ada_check()
+        except NotImplementedError:
+            self._ada = None
+            raise
+        self._guard_changed()
+        return self
+
+    def disable_ada(self):
+        self._ada = None
+        self._guard_changed()
+
+    def _need_ada(self, what):
+        if self._ada is None:
+            raise RuntimeError(f"{what}: the adaptive probability is off (enable_ada)")
+        return self._ada
+
+    def set_ada_p(self, p):
+        """Write a new p into the device record, between steps; a recorded step reads it from there and stays valid."""
+        self._need_ada("set_ada_p").set_p(p)
+
+    def set_ada_target(self, target):
+        """Write a new target into the device record, between steps; a recorded step reads it from there and stays valid."""
+        self._need_ada("set_ada_target").set_target(target)
+
+    def ada_stats(self):
+        """The controller's device record as a dict (``p``, ``target``, ``step``, ``p_max``, ``interval``, ``seen``, ``n_pos``,
+        ``n_neg``, ``n_total``, ``adjustments``, ``last_r``), or None with the feature off.  SYNCHRONISES the stream."""
+        return self._ada.stats() if self._ada is not None else None
 
     # ------------------------------------------------------------------------------------------
     # R1 gradient penalty on the real rows (extension, no counterpart in the reference; srgan_amd.r1)
@@ -985,6 +1071,11 @@ class SingleGAN_training(Checkpointing):
     def enable_diffaugment(self, *args, **kwargs):
         raise NotImplementedError("SingleGAN_training: DiffAugment is not wired into this trainer's discriminator passes (per-domain "
                                   "sub-batches); use SRGAN_training.enable_diffaugment, or augment.DiffAugment in a loop of your own")
+
+    def enable_ada(self, *args, **kwargs):
+        raise NotImplementedError("SingleGAN_training: the adaptive augmentation probability is not wired into this trainer's "
+                                  "discriminator passes (per-domain sub-batches); use SRGAN_training.enable_ada, or ada.AdaptiveP "
+                                  "in a loop of your own")
 
     def enable_r1(self, *args, **kwargs):
         raise NotImplementedError("SingleGAN_training: the R1 penalty is not wired into this trainer's discriminator passes (per-domain "
