@@ -604,8 +604,33 @@ int srgan_ada_state_set(void* state, float target, float step, float p_max, int 
 int srgan_ada_state_set_counters(void* state, int seen, long long n_pos, long long n_neg, long long n_total, int adjustments,
                                  float last_r, void* stream);
 int srgan_ada_gate(const float* rows, const void* state, float* table, int n, void* stream);
+/* The gate for the rows of the geometric stage (below): rows = n rows of 16 floats [fx, k, zoom, cos, sin, -, -, -, u_flip, u_rot90,
+ * u_scale, u_rotate, -, -, -, -]; writes the n rows of 8 floats the gated geometric entry points read: slots 0..6 copied bit for
+ * bit, slot 7 = the float of the mask (0..15) whose bit g is set iff !(u_g < p).  Same rules and checks as srgan_ada_gate. */
+int srgan_ada_gate_geom(const float* rows, const void* state, float* table, int n, void* stream);
 int srgan_ada_observe(const float* const* maps, const long long* per_sample, int n_scales, int rows_first, float thr, void* state,
                       void* stream);
+
+/* Geometric augmentation of the images D reads (the pixel-blitting and geometric groups of Karras et al., 2020): x-flip, 90-degree
+ * turns, isotropic scale and arbitrary rotation as one bilinear affine warp per sample; a second stage after DiffAugment.  fp32,
+ * NHWC-dense, C == 3.  table: n rows of 8 floats [fx, k, zoom, cos, sin, 0, 0, mask]; flags: flip 1, rot90 2, scale 4, rotate 8 (a
+ * group that is off takes its identity value 0, 0, 1, (1, 0)).  With cen = ((h - 1) / 2, (w - 1) / 2) output pixel q reads the
+ * source at s(q) = cen + R(cos, sin) Q(k) F(fx) (q - cen) / zoom, offsets in (row, col) order, F = diag(1, 1 - 2 fx), Q the turn by
+ * k * 90 degrees, R = [[cos, -sin], [sin, cos]]; y[q] is the bilinear interpolation over the four neighbours, a neighbour outside the
+ * image reads 0.  srgan_geom_augment_bwd is the adjoint as a gather: gx[p] = sum_q hat(s_i(q) - p_i) hat(s_j(q) - p_j) gy[q],
+ * hat(t) = max(0, 1 - |t|), over the window of radius min(ceil(zoom (|cos| + |sin|)), 3) around round(cen + zoom (R Q F)^T (p - cen)),
+ * row-major: no atomics, a fixed order, a sample's result depends neither on n nor on its position.  gated != 0: slot 7 of a row
+ * is a skip mask, an exact float in 0..15 with the bits of flags (srgan_ada_gate_geom writes it); the sample comes out bit for bit
+ * as the ungated form gives it with flags & ~mask.  A sample without a group left is a bit copy; any other sample goes through the
+ * weighted sum, so a pure flip / rot90 row permutes VALUES (a -0.0 comes out +0.0; inf or NaN next to a read pixel, under a zero
+ * weight, makes that pixel a NaN).  Whatever a row holds: zoom is
+ * clamped into [0.5, 2] (non-finite reads 1), fx and k are truncated and masked into {0, 1} and {0..3} (non-finite reads 0), a
+ * non-finite cos or sin makes the rotation the identity, every coordinate is clamped before it becomes an integer and every index
+ * is bounds-tested: no access outside the image for any table.  One launch each.  -1 with srgan_last_error() before any launch:
+ * c != 3, a NULL pointer, n, h or w <= 0, h * w > 2^29, an unknown flag bit, y aliasing x. */
+int srgan_geom_augment_fwd(const float* x, const float* table, float* y, int n, int c, int h, int w, int flags, int gated, void* stream);
+int srgan_geom_augment_bwd(const float* gy, const float* table, float* gx, int n, int c, int h, int w, int flags, int gated,
+                           void* stream);
 
 /* R1 gradient penalty on real samples (Mescheder et al., 2018), gamma / 2 * E_x |grad_x D(x)|^2, for the two-scale discriminator.
  * Extension, no counterpart in the reference.  The convolution passes are the ordinary entry points above (srgan_amd/r1.py drives

@@ -9,6 +9,7 @@
 //                       (the uniforms in [0, 1) pre-drawn on the host) -> row of 8 floats for the gated kernels of augment.hip:
 //                       slots 0..6 copied, slot 7 = the float of the skip mask whose bit g is set iff !(u_g < p).  p = 0 skips
 //                       everything, p = 1 nothing, a NaN uniform skips.
+//   ada_gate_geom_kernel  the same for the rows of the geometric stage (four groups, mask 0..15)
 //   ada_observe_kernel  one workgroup of 256 threads: over the first B rows of up to 4 discriminator maps n_pos += #(v > thr),
 //                       n_neg += #(v < thr), n_total += #elements (a NaN counts in n_total only); integer counts, so the order of
 //                       the reduction does not matter: thread-strided, a butterfly inside each wave, four LDS slots.  Thread 0 then
@@ -72,6 +73,25 @@ __global__ __launch_bounds__(256) void ada_gate_kernel(const float* __restrict__
   int mask = 0;
 #pragma unroll
   for (int g = 0; g < 3; ++g) mask |= (u[g] < p) ? 0 : (1 << g);
+  *reinterpret_cast<f32x4*>(t) = a;
+  const f32x4 hi = {b[0], b[1], b[2], (float)mask};
+  *reinterpret_cast<f32x4*>(t + 4) = hi;
+}
+
+// the same gate for the rows of the geometric stage (csrc/augment_geom.hip): [fx, k, zoom, cos, sin, -, -, -, u_flip, u_rot90, u_scale,
+// u_rotate, ...] -> [fx, k, zoom, cos, sin, -, -, mask], the mask over four groups (0..15)
+__global__ __launch_bounds__(256) void ada_gate_geom_kernel(const float* __restrict__ rows, const AdaState* __restrict__ st,
+                                                            float* __restrict__ table, int n) {
+  const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (i >= n) return;
+  const float p = st->p;
+  const float* r = rows + (size_t)i * kAdaRowIn;
+  float* t = table + (size_t)i * kAdaRowOut;
+  const f32x4 a = *reinterpret_cast<const f32x4*>(r), b = *reinterpret_cast<const f32x4*>(r + 4);
+  const f32x4 u = *reinterpret_cast<const f32x4*>(r + 8);
+  int mask = 0;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) mask |= (u[g] < p) ? 0 : (1 << g);
   *reinterpret_cast<f32x4*>(t) = a;
   const f32x4 hi = {b[0], b[1], b[2], (float)mask};
   *reinterpret_cast<f32x4*>(t + 4) = hi;
@@ -168,6 +188,17 @@ extern "C" int srgan_ada_gate(const float* rows, const void* state, float* table
   hipLaunchKernelGGL(srgan::ada_gate_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, as_stream(stream), rows,
                      static_cast<const srgan::AdaState*>(state), table, n);
   return check_launch("ada_gate_kernel");
+}
+
+extern "C" int srgan_ada_gate_geom(const float* rows, const void* state, float* table, int n, void* stream) {
+  SRGAN_REQUIRE(rows && state && table, "ada_gate_geom: null pointer");
+  SRGAN_REQUIRE(n > 0, "ada_gate_geom: n = %d rows (n > 0)", n);
+  SRGAN_REQUIRE(((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(table)) & 15) == 0,
+                "ada_gate_geom: rows / table not 16-byte aligned");
+  SRGAN_REQUIRE(static_cast<const void*>(rows) != static_cast<const void*>(table), "ada_gate_geom: the table must not alias the rows");
+  hipLaunchKernelGGL(srgan::ada_gate_geom_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, as_stream(stream), rows,
+                     static_cast<const srgan::AdaState*>(state), table, n);
+  return check_launch("ada_gate_geom_kernel");
 }
 
 extern "C" int srgan_ada_observe(const float* const* maps, const long long* per_sample, int n_scales, int rows_first, float thr,

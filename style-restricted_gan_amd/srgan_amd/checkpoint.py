@@ -10,10 +10,11 @@ dict`` -- a file written from it loads with ``torch.load(path, weights_only=True
     G, D, E                  ``state_dict()`` of the unwrapped networks, the reference's keys (D: a list for per-domain discriminators)
     optG/D/E, scheG/D/E      ``state_dict()`` of the optimisers and schedulers (lists where the trainer keeps lists)
     hist_target              the histogram-imitation target the constructor drew (``lbd["hist"] > 0``)
-    ema, augment, ada, r1,   the step's extensions that are on: the averaged copies and their update count, DiffAugment's settings
-    grad_guard               and generator, the adaptive probability's settings and whole record (p, seen, the three counts,
-                             adjustments, last_r, the record's batch size n), R1's gamma / every / updates (and the record's batch
-                             size n), per guarded net max_norm and the cumulative steps / skipped / clipped
+    ema, augment, geometry,  the step's extensions that are on: the averaged copies and their update count, DiffAugment's settings
+    ada, r1, grad_guard      and generator, the geometric stage's settings and generator, the adaptive probability's settings and
+                             whole record (p, seen, the three counts, adjustments, last_r, the record's batch size n), R1's
+                             gamma / every / updates (and the record's batch size n), per guarded net max_norm and the cumulative
+                             steps / skipped / clipped
     rng                      the CPU default generator (style and reparametrisation noise) and numpy's global one (``get_target``)
 
 Not saved: the last step's images, ``loss_terms``, the label cache, workspaces, packed operands, the guard's decision and R1's
@@ -42,7 +43,7 @@ LoadReport.__doc__ = """Sections the trainer has but the checkpoint lacks (they 
 use for (skipped)."""
 
 _NETS = ("G", "D", "E")
-_EXTENSIONS = ("ema", "augment", "ada", "r1", "grad_guard")
+_EXTENSIONS = ("ema", "augment", "geometry", "ada", "r1", "grad_guard")
 
 
 def _plain(obj, where="state_dict"):
@@ -133,7 +134,7 @@ class Checkpointing:
         out += [n for n in ("optG", "optD", "optE", "scheG", "scheD", "scheE") if getattr(self, n, None) is not None]
         if getattr(self, "hi", None) is not None:
             out.append("hist_target")
-        for name, attr in (("ema", "_ema"), ("augment", "augment"), ("ada", "_ada"), ("r1", "_r1")):
+        for name, attr in (("ema", "_ema"), ("augment", "augment"), ("geometry", "geometry"), ("ada", "_ada"), ("r1", "_r1")):
             if getattr(self, attr, None) is not None:
                 out.append(name)
         out += [f"grad_guard.{n}" for n in self._ckpt_guards()]
@@ -176,6 +177,8 @@ class Checkpointing:
             sd["ema"] = _plain(self._ema.state_dict(), "ema")
         if getattr(self, "augment", None) is not None:
             sd["augment"] = _plain(self.augment.state_dict(), "augment")
+        if getattr(self, "geometry", None) is not None:
+            sd["geometry"] = _plain(self.geometry.state_dict(), "geometry")
         if getattr(self, "_ada", None) is not None:
             sd["ada"] = _plain(self._ada.state_dict(), "ada")
         r1 = getattr(self, "_r1", None)
@@ -299,6 +302,11 @@ class Checkpointing:
             if self.augment is None:
                 self.enable_diffaugment(a["policy"], a["translation"], a["cutout"])
             self.augment.load_state_dict(a)
+        if use("geometry"):
+            a = sd["geometry"]
+            if self.geometry is None:
+                self.enable_geometric_augment(a["policy"], a["scale_std"], a["rotate_max"])
+            self.geometry.load_state_dict(a)
         if use("ada"):
             a = sd["ada"]
             if self._ada is None or self._ada.interval != int(a["interval"]):

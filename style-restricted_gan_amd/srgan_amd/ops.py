@@ -2701,6 +2701,72 @@ def ada_observe_(outs, rows_first, thr, state):
                                              _ptr(state), _stream()), "ada_observe")
 
 
+# ---- geometric augmentation of the discriminator's inputs (srgan_amd.augment.GeometricAugment; extension) ------------------------
+GEOM_FLIP, GEOM_ROT90, GEOM_SCALE, GEOM_ROTATE = 1, 2, 4, 8
+GEOM_ROW = 8                   # floats per table row: [fx, k, zoom, cos, sin, 0, 0, mask]
+
+
+def _geom_args(what, x, table, flags):
+    x = to_nhwc(x)
+    _require_gpu(x, what)
+    if x.shape[1] != 3:
+        raise _lib.SrganHipError(f"{what}: images of shape {tuple(x.shape)} (three channels)")
+    _require_gpu(table, what + " table")
+    if tuple(table.shape) != (x.shape[0], GEOM_ROW) or not table.is_contiguous():
+        raise _lib.SrganHipError(f"{what}: table of shape {tuple(table.shape)}, a contiguous [{x.shape[0]}, {GEOM_ROW}] expected")
+    flags = int(flags)
+    if flags & ~15:
+        raise _lib.SrganHipError(f"{what}: flags = {flags} (flip 1, rot90 2, scale 4, rotate 8)")
+    return x, flags
+
+
+class _GeomAugmentFn(Function):
+    @staticmethod
+    def forward(ctx, x, table, flags, gated=False):
+        x, flags = _geom_args("geom_augment", x, table, flags)
+        n, _, h, w = x.shape
+        ctx.save_for_backward(table)
+        ctx.geom = (flags, (n, h, w), bool(gated))
+        y = nhwc_empty(n, 3, h, w, x.device)
+        _lib.check(_lib.load().srgan_geom_augment_fwd(_ptr(x), _ptr(table), _ptr(y), n, 3, h, w, flags, int(bool(gated)), _stream()),
+                   "geom_augment_fwd")
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (table,) = ctx.saved_tensors
+        flags, (n, h, w), gated = ctx.geom
+        gy = to_nhwc(gy)
+        gx = nhwc_empty(n, 3, h, w, gy.device)
+        _lib.check(_lib.load().srgan_geom_augment_bwd(_ptr(gy), _ptr(table), _ptr(gx), n, 3, h, w, flags, int(gated), _stream()),
+                   "geom_augment_bwd")
+        return gx, None, None, None
+
+
+def geom_augment(x, table, flags, gated=False):
+    """Geometric augmentation of a batch ``x[N, 3, H, W]``: x-flip, 90-degree turns, isotropic scale and rotation, whichever of them
+    ``flags`` names (GEOM_FLIP | GEOM_ROT90 | GEOM_SCALE | GEOM_ROTATE), as one bilinear affine warp per sample from one device row
+    ``[fx, k, zoom, cos, sin, 0, 0, mask]`` of ``table[N, 8]``; pixels outside the image read 0.  Differentiable in ``x`` only (the
+    adjoint is a gather: no atomics, a fixed order).  One launch each way; hipGraph-capturable.  ``flags == 0`` returns ``x``.
+    ``gated``: slot 7 of a row is a skip mask (an exact float in 0..15, the bits of ``flags``; ``ada_gate_geom`` writes it) and the
+    sample comes out bit for bit as the ungated pass gives it with ``flags & ~mask``."""
+    if int(flags) == 0:
+        return x
+    return _GeomAugmentFn.apply(x, table, flags, gated)
+
+
+def ada_gate_geom(rows, state):
+    """One launch: device rows ``[n, 16]`` (a geometry row in slots 0..6, the uniforms of the four groups in slots 8..11) and the
+    record's p -> the table ``[n, 8]`` of the gated ``geom_augment``: slots 0..6 copied, slot 7 the skip mask whose bit g is set iff
+    ``not u_g < p``.  hipGraph-capturable."""
+    _require_gpu(rows, "ada_gate_geom rows")
+    if rows.dim() != 2 or rows.shape[1] != ADA_ROW or not rows.is_contiguous() or rows.shape[0] == 0:
+        raise _lib.SrganHipError(f"ada_gate_geom: rows of shape {tuple(rows.shape)}, a contiguous [n, {ADA_ROW}] expected")
+    table = torch.empty(rows.shape[0], GEOM_ROW, dtype=torch.float32, device=rows.device)
+    _lib.check(_lib.load().srgan_ada_gate_geom(_ptr(rows), _ptr(state), _ptr(table), rows.shape[0], _stream()), "ada_gate_geom")
+    return table
+
+
 # ---- R1 gradient penalty on real samples (srgan_amd.r1; extension, no counterpart in the reference) ----------------------------
 R1_CHUNK = 4096                # floats of a sample per partial sum of |g|^2
 

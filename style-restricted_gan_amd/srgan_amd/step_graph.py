@@ -2,7 +2,7 @@
 
 ``trainer.py`` chooses the launches; this module stages the step's inputs (``_StepGraph._stage``), records ``sg.UnrolledUpdate()``
 (``_capture``, ``_Recording``), replays it, and drops the recording when something it baked in has changed.  It names no optional
-feature beyond staging the DiffAugment tables: a feature joins ``_fingerprint()`` and the keep-alive list by being in
+feature beyond staging the DiffAugment and geometry tables: a feature joins ``_fingerprint()`` and the keep-alive list by being in
 ``sg._extensions()``, and the host-side counters a recording advances are those of ``sg._mirrors()``.
 """
 import gc
@@ -60,6 +60,7 @@ class _StepGraph:
         self.x = self.out = None
         self.staged_noise = _Staged("noise draws")            # [len(sg._noise_kinds()), B, ndim]
         self.staged_aug = _Staged("DiffAugment tables")       # [2k + 1, B, row width] (no buffer with the feature off)
+        self.staged_geom = _Staged("geometry tables")         # [2k + 1, B, row width] (no buffer with the feature off)
         self.lab = {}
         self._onehot = {}
         self._versions = None
@@ -79,6 +80,10 @@ class _StepGraph:
     @property
     def aug(self):               # the staged DiffAugment tables (None with the feature off)
         return self.staged_aug.buf
+
+    @property
+    def geom(self):              # the staged geometry tables (None with the feature off)
+        return self.staged_geom.buf
 
     fault_hook = None            # tests: callable(stage) with stage in {"before", "inside"}; raising makes the recording fail
 
@@ -154,7 +159,7 @@ class _StepGraph:
 
     def _drop(self):
         self.graph = self.key = self._keep = self._baked = self._steps = self._deltas = None
-        self.x = self.out = self.staged_noise.buf = self.staged_aug.buf = None
+        self.x = self.out = self.staged_noise.buf = self.staged_aug.buf = self.staged_geom.buf = None
 
     def _local_mode(self, source_image, label):
         """2: replay the recording, 1: record (the eager warm-up of this input shape has run), 0: eager."""
@@ -243,6 +248,7 @@ class _StepGraph:
     def _rewind(self):           # the body about to run reads the staged inputs from the start
         self.staged_noise.reset()
         self.staged_aug.reset()
+        self.staged_geom.reset()
         self._onehot = {}
 
     # -- staging (outside the graph, stream-ordered before the replay) ---------------------------------------------
@@ -263,6 +269,10 @@ class _StepGraph:
             # holds and how wide it is, is the trainer's business
             _, _, h, w = x.shape
             self.staged_aug.stage([sg._aug_row_draw(nb, h, w) for _ in range(n_aug)], dev)
+        n_geom = sg._geom_draws()
+        if n_geom:                       # the geometric stage's rows, from its own generator, staged the same way
+            _, _, h, w = x.shape
+            self.staged_geom.stage([sg._geom_row_draw(nb, h, w) for _ in range(n_geom)], dev)
         self.x.copy_(x)
         self.staged_noise.stage(draws, dev)
         for w in ("source", "target"):
@@ -310,6 +320,7 @@ class _StepGraph:
             sg._g_active = False
         self.staged_noise.check_consumed()
         self.staged_aug.check_consumed()
+        self.staged_geom.check_consumed()
         if ops.structure_epoch() != epoch0:
             raise RuntimeError("a workspace the step points at was replaced while the step was being recorded "
                                "(ops.structure_epoch moved): the recording is dropped")
@@ -340,7 +351,7 @@ class _StepGraph:
                       + ("; this step runs eagerly, the next one is recorded as segments" if keep_graph_mode else "; running eagerly from here on"))
         self.graph = self._keep = self._baked = self._steps = None
         self._undo_recording(snap)
-        self._rewind()                            # (the staged noise and DiffAugment tables are used again)
+        self._rewind()                            # (the staged noise, DiffAugment and geometry tables are used again)
         sg.source_image = self.x
         sg._g_active = True
         try:

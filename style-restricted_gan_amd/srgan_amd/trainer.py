@@ -32,7 +32,7 @@ import torch.optim as optim
 
 from . import dp, ema, ops, spectral
 from . import ada as _adamod
-from .augment import DiffAugment
+from .augment import DiffAugment, GeometricAugment, join_geom_rows
 from .checkpoint import Checkpointing
 from . import r1 as _r1mod
 from .losses import class_encode, criterion_kind, get_domainloss_D, get_loss_D, has_fused_kind, histogram_imitation
@@ -99,6 +99,7 @@ class SRGAN_training(Checkpointing):
         self.G_ema = self.E_ema = None
         self._ema_scope = False        # inside ema_weights(): self.G / self.E are the copies
         self.augment = None            # DiffAugment of the discriminator's inputs (enable_diffaugment)
+        self.geometry = None           # geometric augmentation of the discriminator's inputs, after DiffAugment (enable_geometric_augment)
         self._ada = None               # adaptive augmentation probability on the device (enable_ada)
         self._r1 = None                # R1 gradient penalty on the real rows (enable_r1)
         self._label_cache = {}         # (kind, which) -> (label tensor, its device form): _cached
@@ -198,11 +199,50 @@ class SRGAN_training(Checkpointing):
         return 2 * self.k + 1 if self._aug_on() else 0
 
     def _aug(self, image):
-        """DiffAugment of one batch D is about to read (differentiable); the image itself with the feature off."""
-        if not self._aug_on():
+        """DiffAugment, then the geometric stage, of one batch D is about to read (differentiable); the image itself with both
+        features off."""
+        if self._aug_on():
+            n, _, h, w = image.shape
+            image = self.augment.apply(image, self._aug_tables(1, n, h, w), gated=self._ada is not None)
+        return self._geom(image, 1)
+
+    def _geom_on(self):
+        """Does the step run the geometric stage?  (an empty policy is the plain step: no draw, no launch)"""
+        return self.geometry is not None and self.geometry.flags != 0
+
+    def _geom_row_draw(self, nb, h, w):
+        """One host draw of the geometric stage: the CPU table [nb, 8] of its ``draw_fn``; with adaptive augmentation on, followed by
+        the four uniforms per sample of its ``gate_fn`` and joined into the [nb, 16] rows ``ops.ada_gate_geom`` reads."""
+        table = self.geometry.draw_fn(nb, h, w).to(torch.float32)
+        if self._ada is None:
+            return table
+        return join_geom_rows(table, self.geometry.gate_fn(nb))
+
+    def _geom_tables(self, count, nb, h, w):
+        """The next ``count`` geometry tables of the step as ONE device tensor [count * nb, 8]: the order of ``_aug_tables``, from
+        the geometric stage's own generator; staged in graph mode; ONE ``ada_gate_geom`` launch with adaptive augmentation on (the
+        same p as DiffAugment's gate: the record is moved by the update's observation, after both)."""
+        if self._g_active:
+            rows = self._graph.staged_geom.next(count)
+        else:
+            tabs = [self._geom_row_draw(nb, h, w) for _ in range(count)]
+            rows = host_to_device(tabs[0] if count == 1 else torch.cat(tabs, 0), self.device)
+        if self._ada is None:
+            return rows
+        self._ada._ensure(rows.device, nb)
+        return ops.ada_gate_geom(rows, self._ada.state)
+
+    def _geom_draws(self):
+        """geometry tables a step consumes: 2 per discriminator update, 1 for phase 1"""
+        return 2 * self.k + 1 if self._geom_on() else 0
+
+    def _geom(self, image, count):
+        """The geometric stage on a batch of ``count`` tables' worth of rows (differentiable): ONE launch; the image itself with
+        the feature off."""
+        if not self._geom_on():
             return image
         n, _, h, w = image.shape
-        return self.augment.apply(image, self._aug_tables(1, n, h, w), gated=self._ada is not None)
+        return self.geometry.apply(image, self._geom_tables(count, n // count, h, w), gated=self._ada is not None)
 
     def _noise_kinds(self):
         """The step's noise draws in order (fused execution paths)."""
@@ -220,7 +260,7 @@ class SRGAN_training(Checkpointing):
         return (self.optG, self.optD, self.optE)
 
     def _extensions(self):
-        return [x for x in (self._ema, self._sn(), self.augment, self._ada, self._r1) if x is not None]
+        return [x for x in (self._ema, self._sn(), self.augment, self.geometry, self._ada, self._r1) if x is not None]
 
     def _mirrors(self):
         """who mirrors, on the host, a device-side count that the step advances: Adam's step counts, the EMA's update count"""
@@ -417,10 +457,12 @@ class SRGAN_training(Checkpointing):
                 _, _, h, w = self.source_image.shape
                 d_in = ops.diffaugment_cat([self.source_image.detach(), self.target_image.detach()], self._aug_tables(2, B, h, w),
                                            self.augment.flags, self.augment.cut(h, w), gated=self._ada is not None)
-                d_real = d_in[:B]                          # what D read as the real rows (the R1 penalty is taken there)
             else:
                 d_in = ops.cat_batch([self.source_image, self.target_image.detach()])
-                d_real = self.source_image
+            if self._geom_on():
+                d_in = self._geom(d_in, 2)                 # the geometric stage on the 2B rows: one launch, tables real then fake
+            # what D read as the real rows (the R1 penalty is taken there)
+            d_real = d_in[:B] if self._aug_on() or self._geom_on() else self.source_image
             outs, logits = dp.unwrap(self.D).forward_logits(d_in)
             if self._ada is not None:
                 # the overfitting heuristic on what D says about the real rows; every interval-th call moves p, so the p that
@@ -819,6 +861,31 @@ class SRGAN_training(Checkpointing):
         self._guard_changed()
 
     # ------------------------------------------------------------------------------------------
+    # geometric augmentation of what D reads (extension, no counterpart in the reference; srgan_amd.augment.GeometricAugment)
+    def enable_geometric_augment(self, policy="flip,rot90,scale,rotate", scale_std=0.2, rotate_max=1.0, seed=None):
+        """From now on every batch the discriminator reads goes, AFTER DiffAugment's pass (or as it is, with DiffAugment off), through
+        one bilinear affine warp per sample: x-flip, 90-degree turns, isotropic scale (``zoom = 2 ** (N(0, 1) * scale_std)`` in
+        [0.5, 2]) and rotation by ``U(-pi, pi) * rotate_max`` (``policy``: any comma-separated subset, '' = none); pixels outside
+        the image read 0, and the generator's gradient flows back through the warp (a gather: no atomics, a fixed order).
+        ``self.geometry`` is the ``augment.GeometricAugment`` that draws the parameters: 2k + 1 tables of [B, 8] per step, in
+        DiffAugment's order, from its OWN generator (``seed``) -- DiffAugment's tables and the step's noise are what they are
+        without it.  k + 1 forward launches and 1 backward per step (the 2B rows of a discriminator update in one launch); captured
+        with the step in graph mode, where the tables are staged beside DiffAugment's (a recording made before is dropped); saved
+        in a checkpoint (section ``geometry``).  With ``enable_ada`` on the four groups are gated per sample by the same p as
+        DiffAugment's (k + 1 more gate launches, four uniforms per sample after each table); ``enable_ada`` itself still asks for a
+        non-empty DiffAugment policy.  ``rot90`` and ``rotate`` applied always (without ``enable_ada``) leak into the generated
+        images in the ADA paper's sense; ``flip`` is safe on flip-symmetric data.  R1 penalises at what D read.  Off, or an empty
+        policy: no draw, no launch, no allocation, the step is bit-identical to the one without.  Data parallel: per sample, every
+        rank draws its own tables."""
+        self.geometry = GeometricAugment(policy, scale_std, rotate_max, seed)
+        self._guard_changed()
+        return self
+
+    def disable_geometric_augment(self):
+        self.geometry = None
+        self._guard_changed()
+
+    # ------------------------------------------------------------------------------------------
     # adaptive augmentation probability (extension, no counterpart in the reference; srgan_amd.ada)
     def _ada_check(self):
         if not self._aug_on():
@@ -1071,6 +1138,11 @@ class SingleGAN_training(Checkpointing):
     def enable_diffaugment(self, *args, **kwargs):
         raise NotImplementedError("SingleGAN_training: DiffAugment is not wired into this trainer's discriminator passes (per-domain "
                                   "sub-batches); use SRGAN_training.enable_diffaugment, or augment.DiffAugment in a loop of your own")
+
+    def enable_geometric_augment(self, *args, **kwargs):
+        raise NotImplementedError("SingleGAN_training: the geometric augmentation is not wired into this trainer's discriminator "
+                                  "passes (per-domain sub-batches); use SRGAN_training.enable_geometric_augment, or "
+                                  "augment.GeometricAugment in a loop of your own")
 
     def enable_ada(self, *args, **kwargs):
         raise NotImplementedError("SingleGAN_training: the adaptive augmentation probability is not wired into this trainer's "
