@@ -586,28 +586,27 @@ int srgan_diffaugment_bwd_gated(const float* gy, const float* table, float* gx, 
  * srgan_ada_state_init writes p and the settings and zeroes the counters; srgan_ada_state_set rewrites target, step, p_max,
  * interval and (set_p != 0) p and keeps the counters; srgan_ada_state_set_counters writes seen, the three counts, adjustments and
  * last_r and nothing else (resuming from a checkpoint).  One one-thread launch each, stream-ordered.
- * srgan_ada_gate: rows = n rows of 16 floats [b, s, a, ty, tx, cy, cx, -, u_colour, u_translation, u_cutout, -, -, -, -, -] (the
- * uniforms in [0, 1)); one launch, one thread per sample, reads p from the record and writes the n rows of 8 floats the gated
- * entry points above read: slots 0..6 copied bit for bit, slot 7 = the float of the mask whose bit g is set iff !(u_g < p)
- * (p = 0 skips every group, p = 1 none, a NaN uniform skips).  rows and table 16-byte aligned, not aliased.
+ * srgan_ada_gate: the one gate of every augmentation stage.  rows = n rows of 16 floats: slots 0..6 the stage's table row, slots
+ * 8..8 + n_groups - 1 one uniform in [0, 1) per gated group, the other slots unread -- DiffAugment (n_groups = 3):
+ * [b, s, a, ty, tx, cy, cx, -, u_colour, u_translation, u_cutout, ...]; the geometric stage below (n_groups = 4):
+ * [fx, k, zoom, cos, sin, -, -, -, u_flip, u_rot90, u_scale, u_rotate, ...].  One launch, one thread per sample, reads p from the
+ * record and writes the n rows of 8 floats the stage's gated entry points read: slots 0..6 copied bit for bit, slot 7 = the float
+ * of the mask whose bit g < n_groups is set iff !(u_g < p) and whose other bits are clear (p = 0 skips every group, p = 1 none, a
+ * NaN uniform skips).  n_groups is 1 to 4; rows and table 16-byte aligned, not aliased.
  * srgan_ada_observe: maps[s] = fp32 map of scale s (n_scales <= 4), per_sample[s] its elements per row (both host arrays, read
  * before the call returns), rows_first = B the real rows at the front of each map.  One launch of one workgroup: over rows [0, B)
  * of every scale n_pos += #(v > thr), n_neg += #(v < thr), n_total += #elements (a NaN counts in n_total only), seen += 1, and
  * once seen reaches interval: r = float(n_pos - n_neg) / float(n_total), p = min(max(p + sign(r - target) * step, 0), p_max) (sign
  * 0 at equality; one fp32 add, then the clamp), last_r = r, adjustments += 1, the three counts and seen back to 0.  thr: 0.5 for
  * nn.MSELoss against the targets 1 / 0, 0 for nn.BCEWithLogitsLoss.  Integer counts: exact in any order; plain stores, no atomics.
- * -1 with srgan_last_error() before any launch: a NULL pointer, n <= 0, n_scales outside 1..4, B <= 0, a row count <= 0, a
+ * -1 with srgan_last_error() before any launch: a NULL pointer, n <= 0, n_groups or n_scales outside 1..4, B <= 0, a row count <= 0, a
  * setting out of range (target or thr not finite, step < 0, not 0 <= p <= p_max <= 1, interval < 1, a negative count). */
 size_t srgan_ada_state_bytes(void);
 int srgan_ada_state_init(void* state, float p, float target, float step, float p_max, int interval, void* stream);
 int srgan_ada_state_set(void* state, float target, float step, float p_max, int interval, int set_p, float p, void* stream);
 int srgan_ada_state_set_counters(void* state, int seen, long long n_pos, long long n_neg, long long n_total, int adjustments,
                                  float last_r, void* stream);
-int srgan_ada_gate(const float* rows, const void* state, float* table, int n, void* stream);
-/* The gate for the rows of the geometric stage (below): rows = n rows of 16 floats [fx, k, zoom, cos, sin, -, -, -, u_flip, u_rot90,
- * u_scale, u_rotate, -, -, -, -]; writes the n rows of 8 floats the gated geometric entry points read: slots 0..6 copied bit for
- * bit, slot 7 = the float of the mask (0..15) whose bit g is set iff !(u_g < p).  Same rules and checks as srgan_ada_gate. */
-int srgan_ada_gate_geom(const float* rows, const void* state, float* table, int n, void* stream);
+int srgan_ada_gate(const float* rows, const void* state, float* table, int n, int n_groups, void* stream);
 int srgan_ada_observe(const float* const* maps, const long long* per_sample, int n_scales, int rows_first, float thr, void* state,
                       void* stream);
 
@@ -620,7 +619,7 @@ int srgan_ada_observe(const float* const* maps, const long long* per_sample, int
  * image reads 0.  srgan_geom_augment_bwd is the adjoint as a gather: gx[p] = sum_q hat(s_i(q) - p_i) hat(s_j(q) - p_j) gy[q],
  * hat(t) = max(0, 1 - |t|), over the window of radius min(ceil(zoom (|cos| + |sin|)), 3) around round(cen + zoom (R Q F)^T (p - cen)),
  * row-major: no atomics, a fixed order, a sample's result depends neither on n nor on its position.  gated != 0: slot 7 of a row
- * is a skip mask, an exact float in 0..15 with the bits of flags (srgan_ada_gate_geom writes it); the sample comes out bit for bit
+ * is a skip mask, an exact float in 0..15 with the bits of flags (srgan_ada_gate with n_groups = 4 writes it); the sample comes out bit for bit
  * as the ungated form gives it with flags & ~mask.  A sample without a group left is a bit copy; any other sample goes through the
  * weighted sum, so a pure flip / rot90 row permutes VALUES (a -0.0 comes out +0.0; inf or NaN next to a read pixel, under a zero
  * weight, makes that pixel a NaN).  Whatever a row holds: zoom is

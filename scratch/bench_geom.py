@@ -84,7 +84,7 @@ def graph_time_us(fn):
 
 def kernel_times():
     from srgan_amd import _lib, ops
-    from srgan_amd.augment import GeometricAugment, join_geom_rows
+    from srgan_amd.augment import GeometricAugment
     dev = torch.device("cuda", 0)
     out = {}
     geo = GeometricAugment(seed=3)
@@ -92,8 +92,8 @@ def kernel_times():
     for n in (64, 32):
         x = ops.to_nhwc(torch.rand(n, 3, 128, 128, device=dev))
         table = geo.draw(n, 128, 128).to(dev)
-        rows = join_geom_rows(geo.draw(n, 128, 128), geo.draw_gate(n)).to(dev)
-        gated = ops.ada_gate_geom(rows, state)
+        rows = geo.join_rows(geo.draw(n, 128, 128), geo.draw_gate(n)).to(dev)
+        gated = ops.ada_gate(rows, state, 4)
         moved = 2 * x.numel() * 4
         lib_fwd = lambda t=table, g=False: ops.geom_augment(x, t, 15, g)          # noqa: E731
         gy, gx = torch.randn_like(x), torch.empty_like(x)
@@ -105,7 +105,7 @@ def kernel_times():
         entry = {}
         for name, fn in (("fwd", lib_fwd), ("fwd_gated", lambda: lib_fwd(gated, True)),
                          ("bwd", lib_bwd),
-                         ("gate", lambda: ops.ada_gate_geom(rows, state))):
+                         ("gate", lambda: ops.ada_gate(rows, state, 4))):
             us = graph_time_us(fn)
             entry[name] = {"us": round(us, 2)}
             if name != "gate":

@@ -5,11 +5,11 @@
 // A recorded step is replayed without the host, so p, the overfitting heuristic's counters and the per-sample decision "is this
 // group applied?" are device state:
 //
-//   ada_gate_kernel     one thread per sample: row of 16 floats [b, s, a, ty, tx, cy, cx, -, u_colour, u_translation, u_cutout, ...]
-//                       (the uniforms in [0, 1) pre-drawn on the host) -> row of 8 floats for the gated kernels of augment.hip:
-//                       slots 0..6 copied, slot 7 = the float of the skip mask whose bit g is set iff !(u_g < p).  p = 0 skips
-//                       everything, p = 1 nothing, a NaN uniform skips.
-//   ada_gate_geom_kernel  the same for the rows of the geometric stage (four groups, mask 0..15)
+//   ada_gate_kernel     one thread per sample: row of 16 floats [7 parameters of a stage's table row, -, u_0 .. u_{n_groups - 1}, ...]
+//                       (the uniforms in [0, 1) pre-drawn on the host; DiffAugment has 3 groups, the geometric stage 4) -> row of 8
+//                       floats for the gated kernels of augment.hip / augment_geom.hip: slots 0..6 copied, slot 7 = the float of
+//                       the skip mask whose bit g < n_groups is set iff !(u_g < p).  p = 0 skips everything, p = 1 nothing, a NaN
+//                       uniform skips.
 //   ada_observe_kernel  one workgroup of 256 threads: over the first B rows of up to 4 discriminator maps n_pos += #(v > thr),
 //                       n_neg += #(v < thr), n_total += #elements (a NaN counts in n_total only); integer counts, so the order of
 //                       the reduction does not matter: thread-strided, a butterfly inside each wave, four LDS slots.  Thread 0 then
@@ -30,7 +30,8 @@ namespace srgan {
 
 constexpr int kAdaMaxScales = 4;
 constexpr int kAdaRowIn = 16;       // floats per row the gate reads
-constexpr int kAdaRowOut = 8;       // floats per row it writes (augment.hip's table row)
+constexpr int kAdaRowOut = 8;       // floats per row it writes (the table row of augment.hip and augment_geom.hip)
+constexpr int kAdaMaxGroups = 4;    // uniforms per row it can read (slots 8..11)
 
 // p, seen, the three counts, adjustments and last_r are moved by ada_observe_kernel; the rest is written by the host between steps
 struct AdaState {
@@ -62,7 +63,7 @@ __global__ void ada_state_counters_kernel(AdaState* s, int seen, long long n_pos
 }
 
 __global__ __launch_bounds__(256) void ada_gate_kernel(const float* __restrict__ rows, const AdaState* __restrict__ st,
-                                                       float* __restrict__ table, int n) {
+                                                       float* __restrict__ table, int n, int n_groups) {
   const int i = (int)(blockIdx.x * 256u + threadIdx.x);
   if (i >= n) return;
   const float p = st->p;
@@ -72,26 +73,7 @@ __global__ __launch_bounds__(256) void ada_gate_kernel(const float* __restrict__
   const f32x4 u = *reinterpret_cast<const f32x4*>(r + 8);
   int mask = 0;
 #pragma unroll
-  for (int g = 0; g < 3; ++g) mask |= (u[g] < p) ? 0 : (1 << g);
-  *reinterpret_cast<f32x4*>(t) = a;
-  const f32x4 hi = {b[0], b[1], b[2], (float)mask};
-  *reinterpret_cast<f32x4*>(t + 4) = hi;
-}
-
-// the same gate for the rows of the geometric stage (csrc/augment_geom.hip): [fx, k, zoom, cos, sin, -, -, -, u_flip, u_rot90, u_scale,
-// u_rotate, ...] -> [fx, k, zoom, cos, sin, -, -, mask], the mask over four groups (0..15)
-__global__ __launch_bounds__(256) void ada_gate_geom_kernel(const float* __restrict__ rows, const AdaState* __restrict__ st,
-                                                            float* __restrict__ table, int n) {
-  const int i = (int)(blockIdx.x * 256u + threadIdx.x);
-  if (i >= n) return;
-  const float p = st->p;
-  const float* r = rows + (size_t)i * kAdaRowIn;
-  float* t = table + (size_t)i * kAdaRowOut;
-  const f32x4 a = *reinterpret_cast<const f32x4*>(r), b = *reinterpret_cast<const f32x4*>(r + 4);
-  const f32x4 u = *reinterpret_cast<const f32x4*>(r + 8);
-  int mask = 0;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) mask |= (u[g] < p) ? 0 : (1 << g);
+  for (int g = 0; g < kAdaMaxGroups; ++g) mask |= (g >= n_groups || u[g] < p) ? 0 : (1 << g);
   *reinterpret_cast<f32x4*>(t) = a;
   const f32x4 hi = {b[0], b[1], b[2], (float)mask};
   *reinterpret_cast<f32x4*>(t + 4) = hi;
@@ -179,26 +161,17 @@ extern "C" int srgan_ada_state_set_counters(void* state, int seen, long long n_p
   return check_launch("ada_state_counters_kernel");
 }
 
-extern "C" int srgan_ada_gate(const float* rows, const void* state, float* table, int n, void* stream) {
+extern "C" int srgan_ada_gate(const float* rows, const void* state, float* table, int n, int n_groups, void* stream) {
   SRGAN_REQUIRE(rows && state && table, "ada_gate: null pointer");
   SRGAN_REQUIRE(n > 0, "ada_gate: n = %d rows (n > 0)", n);
+  SRGAN_REQUIRE(n_groups >= 1 && n_groups <= srgan::kAdaMaxGroups, "ada_gate: n_groups = %d (1 to %d)", n_groups,
+                srgan::kAdaMaxGroups);
   SRGAN_REQUIRE(((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(table)) & 15) == 0,
                 "ada_gate: rows / table not 16-byte aligned");
   SRGAN_REQUIRE(static_cast<const void*>(rows) != static_cast<const void*>(table), "ada_gate: the table must not alias the rows");
   hipLaunchKernelGGL(srgan::ada_gate_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, as_stream(stream), rows,
-                     static_cast<const srgan::AdaState*>(state), table, n);
+                     static_cast<const srgan::AdaState*>(state), table, n, n_groups);
   return check_launch("ada_gate_kernel");
-}
-
-extern "C" int srgan_ada_gate_geom(const float* rows, const void* state, float* table, int n, void* stream) {
-  SRGAN_REQUIRE(rows && state && table, "ada_gate_geom: null pointer");
-  SRGAN_REQUIRE(n > 0, "ada_gate_geom: n = %d rows (n > 0)", n);
-  SRGAN_REQUIRE(((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(table)) & 15) == 0,
-                "ada_gate_geom: rows / table not 16-byte aligned");
-  SRGAN_REQUIRE(static_cast<const void*>(rows) != static_cast<const void*>(table), "ada_gate_geom: the table must not alias the rows");
-  hipLaunchKernelGGL(srgan::ada_gate_geom_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, as_stream(stream), rows,
-                     static_cast<const srgan::AdaState*>(state), table, n);
-  return check_launch("ada_gate_geom_kernel");
 }
 
 extern "C" int srgan_ada_observe(const float* const* maps, const long long* per_sample, int n_scales, int rows_first, float thr,

@@ -201,8 +201,7 @@ SIGNATURES = {
     "srgan_ada_state_init": (c_int, [P, c_float, c_float, c_float, c_float, c_int, P]),
     "srgan_ada_state_set": (c_int, [P, c_float, c_float, c_float, c_int, c_int, c_float, P]),
     "srgan_ada_state_set_counters": (c_int, [P, c_int, c_longlong, c_longlong, c_longlong, c_int, c_float, P]),
-    "srgan_ada_gate": (c_int, [P, P, P, c_int, P]),
-    "srgan_ada_gate_geom": (c_int, [P, P, P, c_int, P]),
+    "srgan_ada_gate": (c_int, [P, P, P, c_int, c_int, P]),
     "srgan_geom_augment_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "srgan_geom_augment_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "srgan_ada_observe": (c_int, [P, P, c_int, c_int, c_float, P, P]),

@@ -1,17 +1,20 @@
 """Adaptive discriminator augmentation (Karras et al., 2020, "Training Generative Adversarial Networks with Limited Data",
-sections 2.2 and 3) on top of ``augment.DiffAugment`` -- an extension, the reference augments nothing.
+sections 2.2 and 3) on top of the augmentation stages of ``srgan_amd.augment`` -- an extension, the reference augments nothing.
 
-Each DiffAugment group is applied to a sample with probability p instead of always; augmentations applied with p < 1 do not leak
+Each group of a stage is applied to a sample with probability p instead of always; augmentations applied with p < 1 do not leak
 into the generated images, and the right p follows the overfitting heuristic ``r = E[sign(D(real) - thr)]``: every ``interval``
 discriminator updates p moves by ``step`` towards keeping ``r`` at ``target``.  A recorded step is replayed without the host, so
-everything lives in a device record (``csrc/ada.hip``): p, the settings, the heuristic's counters.  Per discriminator read
+everything lives in a device record (``csrc/ada.hip``): p, the settings, the heuristic's counters.  Per discriminator read, for
+every stage that is on (DiffAugment, then the geometric stage)
 
-    host      table [n, 8] from ``DiffAugment.draw_fn``, then uniforms [n, 3] from ``DiffAugment.gate_fn`` (the augmentation's own
-              generator), joined into rows of 16 floats (``join_rows``)
+    host      table [n, 8] from the stage's ``draw_fn``, then uniforms [n, n_groups] from its ``gate_fn`` (the stage's own
+              generator), joined into rows of 16 floats (the stage's ``join_rows``)
     device    ``ops.ada_gate``      rows + the record's p -> table [n, 8] whose slot 7 is the per-sample skip mask
-              ``ops.diffaugment(..., gated=True)``
-              ``ops.ada_observe_``  (discriminator updates only) counts over the real rows of D's maps; every ``interval``-th call
-                                    moves p
+              the stage's ``apply(..., gated=True)``
+
+and then, in discriminator updates only
+
+              ``ops.ada_observe_``  counts over the real rows of D's maps; every ``interval``-th call moves p
 
 ``step = B * interval / (kimg * 1000)``: p can travel from 0 to 1 in ``kimg`` thousand real images.
 ``SRGAN_training.enable_ada`` wires it into the train step."""
@@ -21,6 +24,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .augment import DiffAugment
 
 __all__ = ["AdaptiveP", "join_rows", "threshold"]
 
@@ -66,15 +70,7 @@ def threshold(gan_kind):
     return 0.5 if gan_kind == ops.CRIT_MSE else 0.0
 
 
-def join_rows(table, uniforms):
-    """CPU ``[n, 8]`` table and ``[n, 3]`` uniforms -> the ``[n, 16]`` rows ``ops.ada_gate`` reads (slots 8..10 the uniforms)."""
-    n = table.shape[0]
-    if tuple(table.shape) != (n, ops.AUG_ROW) or tuple(uniforms.shape) != (n, 3):
-        raise ValueError(f"join_rows: table {tuple(table.shape)} and uniforms {tuple(uniforms.shape)}; [n, 8] and [n, 3] expected")
-    rows = torch.zeros(n, ops.ADA_ROW, dtype=torch.float32)
-    rows[:, :ops.AUG_ROW] = table.to(torch.float32)
-    rows[:, 8:11] = uniforms.to(torch.float32)
-    return rows
+join_rows = DiffAugment.join_rows     # DiffAugment's rows; every stage has its own ``join_rows(table, uniforms)``
 
 
 class AdaptiveP:
@@ -137,9 +133,9 @@ class AdaptiveP:
         """A new interval: part of the fingerprint, a recording made before is dropped.  The record follows at the next step."""
         self.interval = check_interval(interval, "AdaptiveP.set_interval")
 
-    def gate(self, rows):
-        """rows [n, 16] on the device -> the gated table [n, 8] (one launch)"""
-        return ops.ada_gate(rows, self.state)
+    def gate(self, rows, n_groups):
+        """rows [n, 16] of a stage with ``n_groups`` gated groups, on the device -> the gated table [n, 8] (one launch)"""
+        return ops.ada_gate(rows, self.state, n_groups)
 
     def observe(self, outs, rows_first, thr):
         ops.ada_observe_(outs, rows_first, thr, self.state)

@@ -1,19 +1,22 @@
-"""Differentiable augmentation of the discriminator's inputs (DiffAugment: Zhao et al., 2020) on the HIP path.
+"""Augmentation stages for the discriminator's inputs on the HIP path.  Extension, no counterpart in the reference.
 
-Extension, no counterpart in the reference.  Every batch the discriminator sees -- real and fake -- goes through the same random
-colour change, translation and cutout, and the generator's gradient flows back through it; the standard remedy when D memorises a
-small training set.  The random parameters are drawn on the host from a generator THIS object owns (never the default one: the
-step's style and reparametrisation noise is the same with the feature on or off), one float32 row per sample:
+Every batch the discriminator sees -- real and fake -- goes through each stage that is on, in order, and the generator's gradient
+flows back through it.  Two stages exist: ``DiffAugment`` (Zhao et al., 2020: random colour change, translation and cutout; the
+standard remedy when D memorises a small training set) and ``GeometricAugment`` (x-flip, 90-degree turns, isotropic scale,
+rotation as one bilinear warp per sample), which runs after it.
 
-    [b, s, a, ty, tx, cy, cx, 0]      b = r_b - 0.5, s = 2 r_s, a = r_c + 0.5 with r ~ U[0, 1)          (colour)
-                                      ty in [-Sy, Sy], tx in [-Sx, Sx], S = int(size * translation + 0.5)  (translation)
-                                      cy in [0, H + (1 - ch % 2)), cx likewise, ch = int(H * cutout + 0.5) (cutout)
+What a stage provides (``_Stage`` holds what all of them share; a new stage is a subclass):
 
-and applied by ``ops.diffaugment`` (csrc/augment.hip).  A group that is off gets identity values (0, 1, 1 / 0, 0 / 0, 0) and is
-not launched.  ``SRGAN_training.enable_diffaugment`` wires it into the train step.
+    groups          {policy entry: flag bit}; ``n_groups`` of them are gated per sample by adaptive augmentation (``srgan_amd.ada``)
+    section         its name in a checkpoint, which is also the ``SRGAN_training`` attribute it lives in
+    settings        the names of its numeric settings (saved, and part of a recording's fingerprint), ``_check_settings`` their check
+    draw(n, h, w)   one CPU float32 table [n, 8] of per-sample parameters, drawn from a generator the STAGE owns (never the default
+                    one: the step's style and reparametrisation noise is the same with the stage on or off); a group that is off
+                    draws nothing and gets its identity values
+    apply(x, table, gated)   the HIP kernels on a device table; ``gated``: slot 7 of a row is the skip mask ``ops.ada_gate`` wrote
 
-``GeometricAugment`` (below) is a second, independent stage -- x-flip, 90-degree turns, isotropic scale, rotation as one bilinear
-warp per sample -- with its own generator, table and kernels; ``SRGAN_training.enable_geometric_augment`` runs it after this one."""
+``SRGAN_training._stages()`` is the list the train step, graph staging and checkpoints iterate; ``enable_diffaugment`` and
+``enable_geometric_augment`` put a stage there."""
 import math
 
 import torch
@@ -23,45 +26,120 @@ from . import ops
 __all__ = ["DiffAugment", "GROUPS", "GeometricAugment", "GEOM_GROUPS"]
 
 GROUPS = {"color": ops.AUG_COLOR, "translation": ops.AUG_TRANSLATION, "cutout": ops.AUG_CUTOUT}
+GEOM_GROUPS = {"flip": ops.GEOM_FLIP, "rot90": ops.GEOM_ROT90, "scale": ops.GEOM_SCALE, "rotate": ops.GEOM_ROTATE}
 
 
-def parse_policy(policy):
-    """'color,translation,cutout' (any comma-separated subset; '' = identity) -> flag bits"""
-    if not isinstance(policy, str):
-        raise ValueError(f"DiffAugment: policy is a comma-separated string of {sorted(GROUPS)}, got {policy!r}")
-    flags = 0
-    for name in (p.strip() for p in policy.split(",")):
-        if name == "" and policy.strip() == "":
-            continue
-        if name not in GROUPS:
-            raise ValueError(f"DiffAugment: unknown policy entry {name!r} (a comma-separated subset of {sorted(GROUPS)})")
-        flags |= GROUPS[name]
-    return flags
+class _Stage:
+    """What the stages share: the policy, the private generator, the injectable draw sources, the rows of the adaptive gate, and the
+    extension interface of the train step (``fingerprint``, ``graph_keepalive``, ``state_dict`` / ``load_state_dict``)."""
 
+    groups, n_groups, section, settings = {}, 0, None, ()
 
-def _window(size, ratio):
-    return int(size * ratio + 0.5)
-
-
-class DiffAugment:
-    def __init__(self, policy="color,translation,cutout", translation=0.125, cutout=0.5, seed=None):
-        parse_policy(policy)                   # an unknown name raises here
+    def __init__(self, policy, seed, **settings):
+        self.parse_policy(policy)              # an unknown name raises here
         self.policy = policy
-        if not (translation >= 0 and cutout >= 0):
-            raise ValueError(f"DiffAugment: translation = {translation}, cutout = {cutout} (ratios >= 0)")
-        self.translation = float(translation)
-        self.cutout = float(cutout)
+        self._take(settings)
         self.generator = torch.Generator()
         if seed is None:
             self.generator.seed()
         else:
             self.generator.manual_seed(int(seed))
         self.draw_fn = self.draw               # tests may inject callable(n, h, w) -> CPU float32 [n, 8]
-        self.gate_fn = self.draw_gate          # ... and callable(n) -> CPU float32 [n, 3] (adaptive augmentation only)
+        self.gate_fn = self.draw_gate          # ... and callable(n) -> CPU float32 [n, n_groups] (adaptive augmentation only)
+
+    @classmethod
+    def parse_policy(cls, policy):
+        """a comma-separated subset of the stage's groups ('' = identity) -> flag bits"""
+        names = sorted(cls.groups)
+        if not isinstance(policy, str):
+            raise ValueError(f"{cls.__name__}: policy is a comma-separated string of {names}, got {policy!r}")
+        flags = 0
+        for name in (p.strip() for p in policy.split(",")):
+            if name == "" and policy.strip() == "":
+                continue
+            if name not in cls.groups:
+                raise ValueError(f"{cls.__name__}: unknown policy entry {name!r} (a comma-separated subset of {names})")
+            flags |= cls.groups[name]
+        return flags
+
+    def _take(self, sd):
+        for name, v in zip(self.settings, self._check_settings(*(sd[k] for k in self.settings))):
+            setattr(self, name, v)
 
     @property
     def flags(self):
-        return parse_policy(self.policy)
+        return self.parse_policy(self.policy)
+
+    def draw_gate(self, n):
+        """One CPU float32 [n, n_groups] of uniforms in [0, 1) for n images, one per group in the order of ``groups``.  Adaptive
+        augmentation (``srgan_amd.ada``) applies group g to a sample iff ``u_g < p``; drawn after the sample's table, from the same
+        generator, and only with that feature on."""
+        return torch.rand(n, self.n_groups, generator=self.generator, dtype=torch.float32)
+
+    @classmethod
+    def join_rows(cls, table, uniforms):
+        """CPU ``[n, 8]`` table and ``[n, n_groups]`` uniforms -> the ``[n, 16]`` rows ``ops.ada_gate`` reads: the table in slots
+        0..7, the uniforms from slot 8 on, zeros elsewhere."""
+        n, g = table.shape[0], cls.n_groups
+        if tuple(table.shape) != (n, ops.AUG_ROW) or tuple(uniforms.shape) != (n, g):
+            raise ValueError(f"{cls.__name__}.join_rows: table {tuple(table.shape)} and uniforms {tuple(uniforms.shape)}; [n, 8] and "
+                             f"[n, {g}] expected")
+        rows = torch.zeros(n, ops.ADA_ROW, dtype=torch.float32)
+        rows[:, :ops.AUG_ROW] = table.to(torch.float32)
+        rows[:, 8:8 + g] = uniforms.to(torch.float32)
+        return rows
+
+    def __call__(self, x):
+        """Draw, copy to the device, apply: for a training loop of one's own (differentiable in x)."""
+        if self.flags == 0:
+            return x
+        n, _, h, w = x.shape
+        table = self.draw_fn(n, h, w).to(dtype=torch.float32).pin_memory().to(x.device, non_blocking=True)
+        return self.apply(x, table)
+
+    def fingerprint(self):
+        """what a recorded step bakes in: the groups launched, the settings, the draw sources"""
+        return (id(self), self.flags, *(getattr(self, k) for k in self.settings), id(getattr(self.draw_fn, "__func__", self.draw_fn)),
+                id(getattr(self.gate_fn, "__func__", self.gate_fn)))
+
+    def graph_keepalive(self):
+        """device buffers a recorded step points at: none (the tables are staged by the recording's owner)"""
+        return []
+
+    def state_dict(self):
+        return {"policy": self.policy, **{k: getattr(self, k) for k in self.settings}, "generator": self.generator.get_state().clone()}
+
+    def load_state_dict(self, sd):
+        self.parse_policy(sd["policy"])
+        self._take(sd)
+        self.policy = sd["policy"]
+        self.generator.set_state(sd["generator"])
+
+
+def _window(size, ratio):
+    return int(size * ratio + 0.5)
+
+
+class DiffAugment(_Stage):
+    """DiffAugment (Zhao et al., 2020), applied by ``ops.diffaugment`` (csrc/augment.hip).  One float32 row per sample:
+
+        [b, s, a, ty, tx, cy, cx, 0]      b = r_b - 0.5, s = 2 r_s, a = r_c + 0.5 with r ~ U[0, 1)          (colour)
+                                          ty in [-Sy, Sy], tx in [-Sx, Sx], S = int(size * translation + 0.5)  (translation)
+                                          cy in [0, H + (1 - ch % 2)), cx likewise, ch = int(H * cutout + 0.5) (cutout)
+
+    A group that is off gets identity values (0, 1, 1 / 0, 0 / 0, 0) and is not launched.  ``SRGAN_training.enable_diffaugment``
+    wires it into the train step."""
+
+    groups, n_groups, section, settings = GROUPS, 3, "augment", ("translation", "cutout")
+
+    def __init__(self, policy="color,translation,cutout", translation=0.125, cutout=0.5, seed=None):
+        super().__init__(policy, seed, translation=translation, cutout=cutout)
+        if not (translation >= 0 and cutout >= 0):
+            raise ValueError(f"DiffAugment: translation = {translation}, cutout = {cutout} (ratios >= 0)")
+
+    @staticmethod
+    def _check_settings(translation, cutout):
+        return float(translation), float(cutout)
 
     def cut(self, h, w):
         """the cutout window (ch, cw) of an h x w image"""
@@ -87,63 +165,12 @@ class DiffAugment:
             t[:, 6] = torch.randint(0, w + (1 - cw % 2), (n,), generator=g).to(torch.float32)
         return t
 
-    def draw_gate(self, n):
-        """One CPU float32 [n, 3] of uniforms in [0, 1) for n images: colour, translation, cutout.  Adaptive augmentation
-        (``srgan_amd.ada``) applies group g to a sample iff ``u_g < p``; drawn after the sample's table, from the same generator,
-        and only with that feature on."""
-        return torch.rand(n, 3, generator=self.generator, dtype=torch.float32)
-
     def apply(self, x, table, gated=False):
         """``table``: device float32 [n, 8]; ``gated``: its slot 7 holds the per-sample skip mask (``ops.ada_gate``)"""
         flags = self.flags
         if flags == 0:
             return x
         return ops.diffaugment(x, table, flags, self.cut(x.shape[2], x.shape[3]), gated)
-
-    def __call__(self, x):
-        """Draw, copy to the device, apply: for a training loop of one's own (differentiable in x)."""
-        if self.flags == 0:
-            return x
-        n, _, h, w = x.shape
-        table = self.draw_fn(n, h, w).to(dtype=torch.float32).pin_memory().to(x.device, non_blocking=True)
-        return self.apply(x, table)
-
-    def fingerprint(self):
-        """what a recorded step bakes in: the groups launched, the window ratios, the draw source"""
-        return (id(self), self.flags, self.translation, self.cutout, id(getattr(self.draw_fn, "__func__", self.draw_fn)),
-                id(getattr(self.gate_fn, "__func__", self.gate_fn)))
-
-    def graph_keepalive(self):
-        """device buffers a recorded step points at: none (the tables are staged by the recording's owner)"""
-        return []
-
-    def state_dict(self):
-        return {"policy": self.policy, "translation": self.translation, "cutout": self.cutout,
-                "generator": self.generator.get_state().clone()}
-
-    def load_state_dict(self, sd):
-        parse_policy(sd["policy"])
-        self.policy = sd["policy"]
-        self.translation, self.cutout = float(sd["translation"]), float(sd["cutout"])
-        self.generator.set_state(sd["generator"])
-
-
-# ---- the geometric stage --------------------------------------------------------------------------------------------------------------
-GEOM_GROUPS = {"flip": ops.GEOM_FLIP, "rot90": ops.GEOM_ROT90, "scale": ops.GEOM_SCALE, "rotate": ops.GEOM_ROTATE}
-
-
-def parse_geom_policy(policy):
-    """'flip,rot90,scale,rotate' (any comma-separated subset; '' = identity) -> flag bits"""
-    if not isinstance(policy, str):
-        raise ValueError(f"GeometricAugment: policy is a comma-separated string of {sorted(GEOM_GROUPS)}, got {policy!r}")
-    flags = 0
-    for name in (p.strip() for p in policy.split(",")):
-        if name == "" and policy.strip() == "":
-            continue
-        if name not in GEOM_GROUPS:
-            raise ValueError(f"GeometricAugment: unknown policy entry {name!r} (a comma-separated subset of {sorted(GEOM_GROUPS)})")
-        flags |= GEOM_GROUPS[name]
-    return flags
 
 
 def _geom_settings(scale_std, rotate_max):
@@ -157,7 +184,7 @@ def _geom_settings(scale_std, rotate_max):
     return s, r
 
 
-class GeometricAugment:
+class GeometricAugment(_Stage):
     """The pixel-blitting and geometric groups of Karras et al. (2020) -- x-flip, 90-degree turns, isotropic scale, arbitrary rotation --
     as ONE bilinear affine warp per sample (``ops.geom_augment``, csrc/augment_geom.hip); a second stage, applied after
     ``DiffAugment``'s pass, with its own generator, table and kernels.  One float32 row per sample:
@@ -171,23 +198,14 @@ class GeometricAugment:
     Output pixel q reads the source at ``cen + R(theta) Q(k) F(fx) (q - cen) / zoom``; pixels outside the image read 0 and the image
     size is kept.  A group that is off draws nothing and gets its identity value (0, 0, 1, (1, 0)).  ``rot90`` and ``rotate`` applied
     always are LEAKING augmentations in the sense of that paper (the generator learns to produce turned images): they are meant to
-    run under the adaptive probability (``SRGAN_training.enable_ada``); ``flip`` is safe on flip-symmetric data."""
+    run under the adaptive probability (``SRGAN_training.enable_ada``); ``flip`` is safe on flip-symmetric data.
+    ``SRGAN_training.enable_geometric_augment`` wires it into the train step."""
+
+    groups, n_groups, section, settings = GEOM_GROUPS, 4, "geometry", ("scale_std", "rotate_max")
+    _check_settings = staticmethod(_geom_settings)
 
     def __init__(self, policy="flip,rot90,scale,rotate", scale_std=0.2, rotate_max=1.0, seed=None):
-        parse_geom_policy(policy)              # an unknown name raises here
-        self.policy = policy
-        self.scale_std, self.rotate_max = _geom_settings(scale_std, rotate_max)
-        self.generator = torch.Generator()
-        if seed is None:
-            self.generator.seed()
-        else:
-            self.generator.manual_seed(int(seed))
-        self.draw_fn = self.draw               # tests may inject callable(n, h, w) -> CPU float32 [n, 8]
-        self.gate_fn = self.draw_gate          # ... and callable(n) -> CPU float32 [n, 4] (adaptive augmentation only)
-
-    @property
-    def flags(self):
-        return parse_geom_policy(self.policy)
+        super().__init__(policy, seed, scale_std=scale_std, rotate_max=rotate_max)
 
     def draw(self, n, h, w):
         """One CPU float32 table [n, 8] for n images of h x w; groups that are off get identity values and draw nothing."""
@@ -208,50 +226,6 @@ class GeometricAugment:
             t[:, 4] = torch.sin(theta).to(torch.float32)
         return t
 
-    def draw_gate(self, n):
-        """One CPU float32 [n, 4] of uniforms in [0, 1) for n images: flip, rot90, scale, rotate.  Adaptive augmentation applies group
-        g to a sample iff ``u_g < p``; drawn after the sample's table, from the same generator, and only with that feature on."""
-        return torch.rand(n, 4, generator=self.generator, dtype=torch.float32)
-
     def apply(self, x, table, gated=False):
-        """``table``: device float32 [n, 8]; ``gated``: its slot 7 holds the per-sample skip mask (``ops.ada_gate_geom``)"""
+        """``table``: device float32 [n, 8]; ``gated``: its slot 7 holds the per-sample skip mask (``ops.ada_gate``)"""
         return ops.geom_augment(x, table, self.flags, gated)
-
-    def __call__(self, x):
-        """Draw, copy to the device, apply: for a training loop of one's own (differentiable in x)."""
-        if self.flags == 0:
-            return x
-        n, _, h, w = x.shape
-        table = self.draw_fn(n, h, w).to(dtype=torch.float32).pin_memory().to(x.device, non_blocking=True)
-        return self.apply(x, table)
-
-    def fingerprint(self):
-        """what a recorded step bakes in: the groups launched and the draw sources (the settings only shape the host draws)"""
-        return (id(self), self.flags, self.scale_std, self.rotate_max, id(getattr(self.draw_fn, "__func__", self.draw_fn)),
-                id(getattr(self.gate_fn, "__func__", self.gate_fn)))
-
-    def graph_keepalive(self):
-        """device buffers a recorded step points at: none (the tables are staged by the recording's owner)"""
-        return []
-
-    def state_dict(self):
-        return {"policy": self.policy, "scale_std": self.scale_std, "rotate_max": self.rotate_max,
-                "generator": self.generator.get_state().clone()}
-
-    def load_state_dict(self, sd):
-        parse_geom_policy(sd["policy"])
-        self.scale_std, self.rotate_max = _geom_settings(sd["scale_std"], sd["rotate_max"])
-        self.policy = sd["policy"]
-        self.generator.set_state(sd["generator"])
-
-
-def join_geom_rows(table, uniforms):
-    """CPU ``[n, 8]`` geometry table and ``[n, 4]`` uniforms -> the ``[n, 16]`` rows ``ops.ada_gate_geom`` reads (slots 8..11 the
-    uniforms)."""
-    n = table.shape[0]
-    if tuple(table.shape) != (n, ops.GEOM_ROW) or tuple(uniforms.shape) != (n, 4):
-        raise ValueError(f"join_geom_rows: table {tuple(table.shape)} and uniforms {tuple(uniforms.shape)}; [n, 8] and [n, 4] expected")
-    rows = torch.zeros(n, ops.ADA_ROW, dtype=torch.float32)
-    rows[:, :ops.GEOM_ROW] = table.to(torch.float32)
-    rows[:, 8:12] = uniforms.to(torch.float32)
-    return rows

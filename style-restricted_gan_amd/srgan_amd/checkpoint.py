@@ -44,6 +44,10 @@ use for (skipped)."""
 
 _NETS = ("G", "D", "E")
 _EXTENSIONS = ("ema", "augment", "geometry", "ada", "r1", "grad_guard")
+# the augmentation stages (srgan_amd.augment): (section, the trainer attribute the stage lives in, the switch that makes one, the keys
+# of a saved section the switch takes, in its order), in the order of application
+_STAGES = (("augment", "augment", "enable_diffaugment", ("policy", "translation", "cutout")),
+           ("geometry", "geometry", "enable_geometric_augment", ("policy", "scale_std", "rotate_max")))
 
 
 def _plain(obj, where="state_dict"):
@@ -134,7 +138,7 @@ class Checkpointing:
         out += [n for n in ("optG", "optD", "optE", "scheG", "scheD", "scheE") if getattr(self, n, None) is not None]
         if getattr(self, "hi", None) is not None:
             out.append("hist_target")
-        for name, attr in (("ema", "_ema"), ("augment", "augment"), ("geometry", "geometry"), ("ada", "_ada"), ("r1", "_r1")):
+        for name, attr in (("ema", "_ema"), *(s[:2] for s in _STAGES), ("ada", "_ada"), ("r1", "_r1")):
             if getattr(self, attr, None) is not None:
                 out.append(name)
         out += [f"grad_guard.{n}" for n in self._ckpt_guards()]
@@ -175,10 +179,9 @@ class Checkpointing:
             sd["hist_target"] = _plain(self.hi.target)
         if getattr(self, "_ema", None) is not None:
             sd["ema"] = _plain(self._ema.state_dict(), "ema")
-        if getattr(self, "augment", None) is not None:
-            sd["augment"] = _plain(self.augment.state_dict(), "augment")
-        if getattr(self, "geometry", None) is not None:
-            sd["geometry"] = _plain(self.geometry.state_dict(), "geometry")
+        for name, attr, _, _ in _STAGES:
+            if getattr(self, attr, None) is not None:
+                sd[name] = _plain(getattr(self, attr).state_dict(), name)
         if getattr(self, "_ada", None) is not None:
             sd["ada"] = _plain(self._ada.state_dict(), "ada")
         r1 = getattr(self, "_r1", None)
@@ -297,16 +300,11 @@ class Checkpointing:
                 self.hi.target.copy_(sd["hist_target"])
         if use("ema"):
             self.load_ema_state_dict(sd["ema"])          # (enables it for the saved nets if it is off; re-seeds the record in place)
-        if use("augment"):
-            a = sd["augment"]
-            if self.augment is None:
-                self.enable_diffaugment(a["policy"], a["translation"], a["cutout"])
-            self.augment.load_state_dict(a)
-        if use("geometry"):
-            a = sd["geometry"]
-            if self.geometry is None:
-                self.enable_geometric_augment(a["policy"], a["scale_std"], a["rotate_max"])
-            self.geometry.load_state_dict(a)
+        for name, attr, enable, keys in _STAGES:
+            if use(name):
+                if getattr(self, attr) is None:
+                    getattr(self, enable)(*(sd[name][k] for k in keys))
+                getattr(self, attr).load_state_dict(sd[name])
         if use("ada"):
             a = sd["ada"]
             if self._ada is None or self._ada.interval != int(a["interval"]):

@@ -2634,7 +2634,7 @@ def diffaugment_cat(xs, table, flags, cut, gated=False):
 
 
 # ---- adaptive discriminator augmentation: p on the device (srgan_amd.ada; extension, no counterpart in the reference) -----------
-ADA_ROW = 16                   # floats per row the gate reads: [b, s, a, ty, tx, cy, cx, -, u_colour, u_translation, u_cutout, 5 x -]
+ADA_ROW = 16                   # floats per row the gate reads: [a stage's table row (slots 0..6), -, one uniform per gated group, ...]
 ADA_MAX_SCALES = 4
 _ADA_FMT = "ffffiiqqqif"       # the record (include/srgan_hip.h): 56 bytes
 _ADA_FIELDS = ("p", "target", "step", "p_max", "interval", "seen", "n_pos", "n_neg", "n_total", "adjustments", "last_r")
@@ -2668,15 +2668,16 @@ def ada_state_read(state):
     return dict(zip(_ADA_FIELDS, struct.unpack(_ADA_FMT, state.cpu().numpy().tobytes()[:struct.calcsize(_ADA_FMT)])))
 
 
-def ada_gate(rows, state):
-    """One launch: device rows ``[n, 16]`` (a DiffAugment row in slots 0..6, the uniforms of the three groups in slots 8..10) and
-    the record's p -> the table ``[n, 8]`` of the gated ``diffaugment``: slots 0..6 copied, slot 7 the skip mask whose bit g is set
-    iff ``not u_g < p``.  hipGraph-capturable."""
+def ada_gate(rows, state, n_groups=3):
+    """One launch, for any augmentation stage: device rows ``[n, 16]`` (the stage's table row in slots 0..6, the uniforms of its
+    ``n_groups`` gated groups -- 3 for DiffAugment (the default), 4 for the geometric stage, 1 to 4 -- from slot 8 on) and the record's p -> the
+    table ``[n, 8]`` of the gated ``diffaugment`` / ``geom_augment``: slots 0..6 copied, slot 7 the skip mask whose bit
+    g < ``n_groups`` is set iff ``not u_g < p``.  hipGraph-capturable."""
     _require_gpu(rows, "ada_gate rows")
     if rows.dim() != 2 or rows.shape[1] != ADA_ROW or not rows.is_contiguous() or rows.shape[0] == 0:
         raise _lib.SrganHipError(f"ada_gate: rows of shape {tuple(rows.shape)}, a contiguous [n, {ADA_ROW}] expected")
     table = torch.empty(rows.shape[0], AUG_ROW, dtype=torch.float32, device=rows.device)
-    _lib.check(_lib.load().srgan_ada_gate(_ptr(rows), _ptr(state), _ptr(table), rows.shape[0], _stream()), "ada_gate")
+    _lib.check(_lib.load().srgan_ada_gate(_ptr(rows), _ptr(state), _ptr(table), rows.shape[0], int(n_groups), _stream()), "ada_gate")
     return table
 
 
@@ -2748,23 +2749,11 @@ def geom_augment(x, table, flags, gated=False):
     ``flags`` names (GEOM_FLIP | GEOM_ROT90 | GEOM_SCALE | GEOM_ROTATE), as one bilinear affine warp per sample from one device row
     ``[fx, k, zoom, cos, sin, 0, 0, mask]`` of ``table[N, 8]``; pixels outside the image read 0.  Differentiable in ``x`` only (the
     adjoint is a gather: no atomics, a fixed order).  One launch each way; hipGraph-capturable.  ``flags == 0`` returns ``x``.
-    ``gated``: slot 7 of a row is a skip mask (an exact float in 0..15, the bits of ``flags``; ``ada_gate_geom`` writes it) and the
+    ``gated``: slot 7 of a row is a skip mask (an exact float in 0..15, the bits of ``flags``; ``ada_gate`` writes it) and the
     sample comes out bit for bit as the ungated pass gives it with ``flags & ~mask``."""
     if int(flags) == 0:
         return x
     return _GeomAugmentFn.apply(x, table, flags, gated)
-
-
-def ada_gate_geom(rows, state):
-    """One launch: device rows ``[n, 16]`` (a geometry row in slots 0..6, the uniforms of the four groups in slots 8..11) and the
-    record's p -> the table ``[n, 8]`` of the gated ``geom_augment``: slots 0..6 copied, slot 7 the skip mask whose bit g is set iff
-    ``not u_g < p``.  hipGraph-capturable."""
-    _require_gpu(rows, "ada_gate_geom rows")
-    if rows.dim() != 2 or rows.shape[1] != ADA_ROW or not rows.is_contiguous() or rows.shape[0] == 0:
-        raise _lib.SrganHipError(f"ada_gate_geom: rows of shape {tuple(rows.shape)}, a contiguous [n, {ADA_ROW}] expected")
-    table = torch.empty(rows.shape[0], GEOM_ROW, dtype=torch.float32, device=rows.device)
-    _lib.check(_lib.load().srgan_ada_gate_geom(_ptr(rows), _ptr(state), _ptr(table), rows.shape[0], _stream()), "ada_gate_geom")
-    return table
 
 
 # ---- R1 gradient penalty on real samples (srgan_amd.r1; extension, no counterpart in the reference) ----------------------------

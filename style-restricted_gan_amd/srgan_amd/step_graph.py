@@ -2,8 +2,9 @@
 
 ``trainer.py`` chooses the launches; this module stages the step's inputs (``_StepGraph._stage``), records ``sg.UnrolledUpdate()``
 (``_capture``, ``_Recording``), replays it, and drops the recording when something it baked in has changed.  It names no optional
-feature beyond staging the DiffAugment and geometry tables: a feature joins ``_fingerprint()`` and the keep-alive list by being in
-``sg._extensions()``, and the host-side counters a recording advances are those of ``sg._mirrors()``.
+feature: a feature joins ``_fingerprint()`` and the keep-alive list by being in ``sg._extensions()``, the host-side counters a
+recording advances are those of ``sg._mirrors()``, and the augmentation stages whose host-drawn tables are staged beside the noise
+(one ``_Staged`` per stage, keyed by its ``section``) are those of ``sg._stages()``.
 """
 import gc
 import os
@@ -18,7 +19,7 @@ from .optim import Adam
 
 
 class _Staged:
-    """``what`` ("noise draws", "DiffAugment tables") the step draws on the host: staged into one static device buffer
+    """``what`` ("noise draws", "augment tables") the step draws on the host: staged into one static device buffer
     [n, B, row] and handed out slice by slice while the captured body runs."""
 
     def __init__(self, what):
@@ -59,8 +60,7 @@ class _StepGraph:
         self.graph = None
         self.x = self.out = None
         self.staged_noise = _Staged("noise draws")            # [len(sg._noise_kinds()), B, ndim]
-        self.staged_aug = _Staged("DiffAugment tables")       # [2k + 1, B, row width] (no buffer with the feature off)
-        self.staged_geom = _Staged("geometry tables")         # [2k + 1, B, row width] (no buffer with the feature off)
+        self.staged = {}         # a stage's section -> _Staged of [2k + 1, B, row width], for the stages of sg._stages() that draw
         self.lab = {}
         self._onehot = {}
         self._versions = None
@@ -77,13 +77,12 @@ class _StepGraph:
         if reason and reason is not self.SEGMENTED_SYNC:      # (that one is not a refusal: such steps run eagerly, _local_mode)
             raise NotImplementedError("SRGAN_training.enable_graph: " + reason)
 
-    @property
-    def aug(self):               # the staged DiffAugment tables (None with the feature off)
-        return self.staged_aug.buf
+    def tables(self, section):
+        """the staged tables of the stage ``section`` names (None with the stage off)"""
+        return self.staged[section].buf if section in self.staged else None
 
-    @property
-    def geom(self):              # the staged geometry tables (None with the feature off)
-        return self.staged_geom.buf
+    aug = property(lambda self: self.tables("augment"))         # shorthands of the two stages that exist today
+    geom = property(lambda self: self.tables("geometry"))
 
     fault_hook = None            # tests: callable(stage) with stage in {"before", "inside"}; raising makes the recording fail
 
@@ -159,7 +158,8 @@ class _StepGraph:
 
     def _drop(self):
         self.graph = self.key = self._keep = self._baked = self._steps = self._deltas = None
-        self.x = self.out = self.staged_noise.buf = self.staged_aug.buf = self.staged_geom.buf = None
+        self.x = self.out = self.staged_noise.buf = None
+        self.staged = {}
 
     def _local_mode(self, source_image, label):
         """2: replay the recording, 1: record (the eager warm-up of this input shape has run), 0: eager."""
@@ -246,9 +246,8 @@ class _StepGraph:
         return hit
 
     def _rewind(self):           # the body about to run reads the staged inputs from the start
-        self.staged_noise.reset()
-        self.staged_aug.reset()
-        self.staged_geom.reset()
+        for st in (self.staged_noise, *self.staged.values()):
+            st.reset()
         self._onehot = {}
 
     # -- staging (outside the graph, stream-ordered before the replay) ---------------------------------------------
@@ -263,16 +262,14 @@ class _StepGraph:
             self.x = torch.empty_like(x)
             self.lab = {w: torch.empty(nb, dtype=torch.int64, device=dev) for w in ("source", "target")}
             self.table = torch.tensor(np.asarray(sg.ref_label), dtype=torch.float32).to(dev)
-        n_aug = sg._aug_draws()
-        if n_aug:
-            # the step's 2k + 1 rows, drawn up front in the order the eager step draws them (SRGAN_training._aug_tables); what a row
-            # holds and how wide it is, is the trainer's business
-            _, _, h, w = x.shape
-            self.staged_aug.stage([sg._aug_row_draw(nb, h, w) for _ in range(n_aug)], dev)
-        n_geom = sg._geom_draws()
-        if n_geom:                       # the geometric stage's rows, from its own generator, staged the same way
-            _, _, h, w = x.shape
-            self.staged_geom.stage([sg._geom_row_draw(nb, h, w) for _ in range(n_geom)], dev)
+        _, _, h, w = x.shape
+        for stage in sg._stages():
+            # a stage's 2k + 1 rows, drawn up front in the order the eager step draws them (SRGAN_training._stage_tables), stage by
+            # stage: each draws from its own generator; what a row holds and how wide it is, is the trainer's business
+            n = sg._stage_draws(stage)
+            if n:
+                st = self.staged.setdefault(stage.section, _Staged(stage.section + " tables"))
+                st.stage([sg._stage_row_draw(stage, nb, h, w) for _ in range(n)], dev)
         self.x.copy_(x)
         self.staged_noise.stage(draws, dev)
         for w in ("source", "target"):
@@ -318,9 +315,8 @@ class _StepGraph:
                 self.out = torch.stack([e.detach().reshape(()) for e in err])
         finally:
             sg._g_active = False
-        self.staged_noise.check_consumed()
-        self.staged_aug.check_consumed()
-        self.staged_geom.check_consumed()
+        for st in (self.staged_noise, *self.staged.values()):
+            st.check_consumed()
         if ops.structure_epoch() != epoch0:
             raise RuntimeError("a workspace the step points at was replaced while the step was being recorded "
                                "(ops.structure_epoch moved): the recording is dropped")
@@ -351,7 +347,7 @@ class _StepGraph:
                       + ("; this step runs eagerly, the next one is recorded as segments" if keep_graph_mode else "; running eagerly from here on"))
         self.graph = self._keep = self._baked = self._steps = None
         self._undo_recording(snap)
-        self._rewind()                            # (the staged noise, DiffAugment and geometry tables are used again)
+        self._rewind()                            # (the staged noise and the stages' tables are used again)
         sg.source_image = self.x
         sg._g_active = True
         try:

@@ -32,7 +32,7 @@ import torch.optim as optim
 
 from . import dp, ema, ops, spectral
 from . import ada as _adamod
-from .augment import DiffAugment, GeometricAugment, join_geom_rows
+from .augment import DiffAugment, GeometricAugment
 from .checkpoint import Checkpointing
 from . import r1 as _r1mod
 from .losses import class_encode, criterion_kind, get_domainloss_D, get_loss_D, has_fused_kind, histogram_imitation
@@ -166,83 +166,53 @@ class SRGAN_training(Checkpointing):
         cpu = self.noise_fn(nb, self.ndim) if kind == "randn" else torch.FloatTensor(nb, self.ndim).normal_()
         return host_to_device(cpu, self.device)
 
-    def _aug_on(self):
-        """Does the step augment what D reads?  (an empty policy is the plain step: no draw, no launch)"""
-        return self.augment is not None and self.augment.flags != 0
+    def _stages(self):
+        """The augmentation stages (``srgan_amd.augment``) the trainer holds, in the order they are applied to what D reads.  The
+        step, graph staging (``step_graph``) and checkpoints go by this list; a stage lives in the attribute its ``section`` names."""
+        return [s for s in (self.augment, self.geometry) if s is not None]
 
-    def _aug_row_draw(self, nb, h, w):
-        """One host draw of the step: the CPU table [nb, 8] of ``draw_fn``; with adaptive augmentation on, followed by the three
-        uniforms per sample of ``gate_fn`` and joined into the [nb, 16] rows ``ops.ada_gate`` reads."""
-        table = self.augment.draw_fn(nb, h, w).to(torch.float32)
+    @staticmethod
+    def _stage_on(stage):
+        """Does the step run this stage?  (None, or an empty policy, is the plain step: no draw, no launch)"""
+        return stage is not None and stage.flags != 0
+
+    def _stage_draws(self, stage):
+        """tables of a stage a step consumes: 2 per discriminator update, 1 for phase 1"""
+        return 2 * self.k + 1 if self._stage_on(stage) else 0
+
+    def _stage_row_draw(self, stage, nb, h, w):
+        """One host draw of the step: the CPU table [nb, 8] of the stage's ``draw_fn``; with adaptive augmentation on, followed by
+        one uniform per group and sample of its ``gate_fn`` and joined into the [nb, 16] rows ``ops.ada_gate`` reads."""
+        table = stage.draw_fn(nb, h, w).to(torch.float32)
         if self._ada is None:
             return table
-        return _adamod.join_rows(table, self.augment.gate_fn(nb))
+        return stage.join_rows(table, stage.gate_fn(nb))
 
-    def _aug_tables(self, count, nb, h, w):
-        """The next ``count`` parameter tables of the step as ONE device tensor [count * nb, 8].  Draw order of a step
-        (``_aug_draws``): per discriminator update the real rows' table, then the fake rows'; after the k updates phase 1's.  They
-        come from the augmentation's own generator, never the default one.  Graph mode: drawn up front in the same order and
-        staged; this hands out the next slice of the static buffer.  Adaptive augmentation: the rows are [count * nb, 16] and go
-        through ONE ``ada_gate`` launch, which reads p and writes the tables with their skip masks."""
+    def _stage_tables(self, stage, count, nb, h, w):
+        """The next ``count`` parameter tables of a stage as ONE device tensor [count * nb, 8].  Draw order of a step
+        (``_stage_draws``): per discriminator update the real rows' table, then the fake rows'; after the k updates phase 1's.  They
+        come from the stage's own generator, never the default one.  Graph mode: drawn up front in the same order and staged; this
+        hands out the next slice of the stage's static buffer.  Adaptive augmentation: the rows are [count * nb, 16] and go through
+        ONE ``ada_gate`` launch, which reads p and writes the tables with their skip masks (every stage's gate of an update reads
+        the same p: the record is moved by the update's observation, after all of them)."""
         if self._g_active:
-            rows = self._graph.staged_aug.next(count)
+            rows = self._graph.staged[stage.section].next(count)
         else:
-            tabs = [self._aug_row_draw(nb, h, w) for _ in range(count)]
+            tabs = [self._stage_row_draw(stage, nb, h, w) for _ in range(count)]
             rows = host_to_device(tabs[0] if count == 1 else torch.cat(tabs, 0), self.device)
         if self._ada is None:
             return rows
         self._ada._ensure(rows.device, nb)
-        return self._ada.gate(rows)
+        return self._ada.gate(rows, stage.n_groups)
 
-    def _aug_draws(self):
-        """tables a step consumes: 2 per discriminator update, 1 for phase 1"""
-        return 2 * self.k + 1 if self._aug_on() else 0
-
-    def _aug(self, image):
-        """DiffAugment, then the geometric stage, of one batch D is about to read (differentiable); the image itself with both
-        features off."""
-        if self._aug_on():
-            n, _, h, w = image.shape
-            image = self.augment.apply(image, self._aug_tables(1, n, h, w), gated=self._ada is not None)
-        return self._geom(image, 1)
-
-    def _geom_on(self):
-        """Does the step run the geometric stage?  (an empty policy is the plain step: no draw, no launch)"""
-        return self.geometry is not None and self.geometry.flags != 0
-
-    def _geom_row_draw(self, nb, h, w):
-        """One host draw of the geometric stage: the CPU table [nb, 8] of its ``draw_fn``; with adaptive augmentation on, followed by
-        the four uniforms per sample of its ``gate_fn`` and joined into the [nb, 16] rows ``ops.ada_gate_geom`` reads."""
-        table = self.geometry.draw_fn(nb, h, w).to(torch.float32)
-        if self._ada is None:
-            return table
-        return join_geom_rows(table, self.geometry.gate_fn(nb))
-
-    def _geom_tables(self, count, nb, h, w):
-        """The next ``count`` geometry tables of the step as ONE device tensor [count * nb, 8]: the order of ``_aug_tables``, from
-        the geometric stage's own generator; staged in graph mode; ONE ``ada_gate_geom`` launch with adaptive augmentation on (the
-        same p as DiffAugment's gate: the record is moved by the update's observation, after both)."""
-        if self._g_active:
-            rows = self._graph.staged_geom.next(count)
-        else:
-            tabs = [self._geom_row_draw(nb, h, w) for _ in range(count)]
-            rows = host_to_device(tabs[0] if count == 1 else torch.cat(tabs, 0), self.device)
-        if self._ada is None:
-            return rows
-        self._ada._ensure(rows.device, nb)
-        return ops.ada_gate_geom(rows, self._ada.state)
-
-    def _geom_draws(self):
-        """geometry tables a step consumes: 2 per discriminator update, 1 for phase 1"""
-        return 2 * self.k + 1 if self._geom_on() else 0
-
-    def _geom(self, image, count):
-        """The geometric stage on a batch of ``count`` tables' worth of rows (differentiable): ONE launch; the image itself with
-        the feature off."""
-        if not self._geom_on():
-            return image
+    def _aug(self, image, count=1, stages=None):
+        """The stages that are on (all, or ``stages``), in order, on a batch of ``count`` tables' worth of rows D is about to read
+        (differentiable): ONE launch per stage; the image itself with all of them off."""
         n, _, h, w = image.shape
-        return self.geometry.apply(image, self._geom_tables(count, n // count, h, w), gated=self._ada is not None)
+        for stage in self._stages() if stages is None else stages:
+            if self._stage_on(stage):
+                image = stage.apply(image, self._stage_tables(stage, count, n // count, h, w), gated=self._ada is not None)
+        return image
 
     def _noise_kinds(self):
         """The step's noise draws in order (fused execution paths)."""
@@ -260,7 +230,7 @@ class SRGAN_training(Checkpointing):
         return (self.optG, self.optD, self.optE)
 
     def _extensions(self):
-        return [x for x in (self._ema, self._sn(), self.augment, self.geometry, self._ada, self._r1) if x is not None]
+        return [x for x in (self._ema, self._sn(), *self._stages(), self._ada, self._r1) if x is not None]
 
     def _mirrors(self):
         """who mirrors, on the host, a device-side count that the step advances: Adam's step counts, the EMA's update count"""
@@ -451,18 +421,19 @@ class SRGAN_training(Checkpointing):
         if self._fused_paths():
             # real and fake halves through D as ONE batch (per-sample network: exact; 2x the rows per GEMM launch)
             B = self.source_image.shape[0]
-            if self._aug_on():
+            rest = [s for s in self._stages() if s is not self.augment]
+            if self._stage_on(self.augment):
                 # both halves augmented and concatenated in ONE pass (no gradient needed: real rows have none, fake rows are detached)
-                # adaptive augmentation: the two tables went through one gate launch of 2B rows (_aug_tables)
+                # adaptive augmentation: the two tables went through one gate launch of 2B rows (_stage_tables)
                 _, _, h, w = self.source_image.shape
-                d_in = ops.diffaugment_cat([self.source_image.detach(), self.target_image.detach()], self._aug_tables(2, B, h, w),
-                                           self.augment.flags, self.augment.cut(h, w), gated=self._ada is not None)
+                d_in = ops.diffaugment_cat([self.source_image.detach(), self.target_image.detach()],
+                                           self._stage_tables(self.augment, 2, B, h, w), self.augment.flags, self.augment.cut(h, w),
+                                           gated=self._ada is not None)
             else:
                 d_in = ops.cat_batch([self.source_image, self.target_image.detach()])
-            if self._geom_on():
-                d_in = self._geom(d_in, 2)                 # the geometric stage on the 2B rows: one launch, tables real then fake
+            d_in = self._aug(d_in, 2, rest)                # the remaining stages on the 2B rows: one launch each, tables real then fake
             # what D read as the real rows (the R1 penalty is taken there)
-            d_real = d_in[:B] if self._aug_on() or self._geom_on() else self.source_image
+            d_real = d_in[:B] if any(self._stage_on(s) for s in self._stages()) else self.source_image
             outs, logits = dp.unwrap(self.D).forward_logits(d_in)
             if self._ada is not None:
                 # the overfitting heuristic on what D says about the real rows; every interval-th call moves p, so the p that
@@ -888,7 +859,7 @@ class SRGAN_training(Checkpointing):
     # ------------------------------------------------------------------------------------------
     # adaptive augmentation probability (extension, no counterpart in the reference; srgan_amd.ada)
     def _ada_check(self):
-        if not self._aug_on():
+        if not self._stage_on(self.augment):
             raise NotImplementedError("SRGAN_training: the adaptive probability gates DiffAugment's groups and "
                                       + ("DiffAugment is off" if self.augment is None else "its policy is empty")
                                       + " (enable_diffaugment(policy=...) first, or disable_ada())")

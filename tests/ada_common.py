@@ -71,17 +71,18 @@ def same_record(got, st):
 
 
 def gate_masks(uniforms, p):
-    """uniforms float32 [n, 3], p float32 -> int64 [n]: bit g set iff not (u_g < p)"""
+    """uniforms float32 [n, groups], p float32 -> int64 [n]: bit g set iff not (u_g < p)"""
     u = np.asarray(uniforms, dtype=F32)
     skip = ~(u < F32(p))                               # a NaN compares false: skipped
-    return skip[:, 0].astype(np.int64) | (skip[:, 1].astype(np.int64) << 1) | (skip[:, 2].astype(np.int64) << 2)
+    return sum(skip[:, g].astype(np.int64) << g for g in range(u.shape[1]))
 
 
-def gate_rows(rows, p):
-    """rows float32 [n, 16] -> the table float32 [n, 8]: slots 0..6 copied (bit for bit), slot 7 the float of the mask"""
+def gate_rows(rows, p, n_groups=3):
+    """rows float32 [n, 16] -> the table float32 [n, 8]: slots 0..6 copied (bit for bit), slot 7 the float of the mask over the
+    first ``n_groups`` uniforms (slots 8 .. 8 + n_groups - 1)"""
     rows = np.asarray(rows, dtype=F32)
     out = rows[:, :8].copy()
-    out[:, 7] = gate_masks(rows[:, 8:11], p).astype(F32)
+    out[:, 7] = gate_masks(rows[:, 8:8 + n_groups], p).astype(F32)
     return out
 
 

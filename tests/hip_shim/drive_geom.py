@@ -29,7 +29,7 @@ def main():
         for gated in (0, 1):
             assert lib.srgan_geom_augment_fwd(p[0], p[1], p[2], n, 3, h, w, 15, gated, None) == 0, lib.srgan_last_error()
             assert lib.srgan_geom_augment_bwd(p[2], p[1], p[0], n, 3, h, w, 15, gated, None) == 0, lib.srgan_last_error()
-        assert lib.srgan_ada_gate_geom(p[0], p[3], p[1], n, None) == 0, lib.srgan_last_error()
+        assert lib.srgan_ada_gate(p[0], p[3], p[1], n, 4, None) == 0, lib.srgan_last_error()
 
 
 if __name__ == "__main__":

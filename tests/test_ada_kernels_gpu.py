@@ -163,6 +163,37 @@ def test_gate_against_the_restatement(n):
             assert (got[~odd, 7] == 0.0).all() and (got[odd, 7] > 0).all()
 
 
+@pytest.mark.parametrize("n", [1, 255, 256, 257])
+@pytest.mark.parametrize("n_groups", [1, 2])
+def test_gate_of_fewer_groups_against_the_restatement(n_groups, n):
+    """the gate reads the first ``n_groups`` uniforms only: every read slot meets exactly 0, exactly p and the largest float32 below
+    1; the slots behind them hold what would set a bit if it were read (uniforms, a NaN), and the bits at and above ``n_groups``
+    stay clear"""
+    from srgan_amd import ops
+    g = torch.Generator().manual_seed(4100 + 10 * n + n_groups)
+    for p in (0.0, 0.5, 1.0):
+        state = ops.ada_state_new("cuda", p, 0.6, 0.01, 1.0, 4)
+        special = [0.0, p, TOP]
+        for shift in range(len(special)):                  # (a batch of one row still meets every special value)
+            rows = torch.randn(n, 16, generator=g)
+            rows[:, 8:12] = torch.rand(n, 4, generator=g)
+            for i in range(min(n, len(special) * n_groups)):
+                rows[i, 8 + i % n_groups] = special[(i // n_groups + shift) % len(special)]
+            rows[0, 8 + n_groups:12] = float("nan")
+            rows[0, 1], rows[0, 7] = -0.0, 123.0           # copied bit for bit / overwritten
+            got = ops.ada_gate(rows.cuda(), state, n_groups).cpu()
+            want = torch.from_numpy(adc.gate_rows(rows.numpy(), p, n_groups))
+            assert torch.equal(got, want) and torch.equal(_bits(got), _bits(want)), (n, n_groups, p, shift)
+            assert (got[:, 7] < (1 << n_groups)).all()
+            if p == 0.0:
+                assert (got[:, 7] == (1 << n_groups) - 1).all()
+        # a three-group call does not read slot 11: whatever it holds (a NaN, values not below p), bit 3 stays clear
+        rows[:, 8:11] = torch.rand(n, 3, generator=g)
+        rows[:, 11] = torch.where(torch.arange(n) % 2 == 0, float("nan"), 1.5)
+        got = ops.ada_gate(rows.cuda(), state, 3).cpu()
+        assert torch.equal(got, torch.from_numpy(adc.gate_rows(rows.numpy(), p, 3))) and (got[:, 7] < 8).all()
+
+
 # ---- observe ------------------------------------------------------------------------------------------------------------------------
 OBSERVE_CASES = [(1, [(1, 1)]), (4, [(16, 16), (8, 8)]), (3, [(7, 5), (4, 3)]), (32, [(1, 1), (1, 1)]), (2, [(250, 280)])]
 INTERVAL = 3

@@ -193,7 +193,7 @@ def test_draw_order_table_then_three_uniforms_from_the_augmentations_generator()
     sg = _cpu_trainer().enable_diffaugment(seed=11)
     sg.enable_ada()
     default_before = torch.get_rng_state()
-    rows = [sg._aug_row_draw(4, 16, 12) for _ in range(3)]
+    rows = [sg._stage_row_draw(sg.augment, 4, 16, 12) for _ in range(3)]
     assert torch.equal(torch.get_rng_state(), default_before)          # the default generator (style noise) is untouched
     ref = DiffAugment(seed=11)
     for r in rows:
@@ -205,7 +205,7 @@ def test_draw_order_table_then_three_uniforms_from_the_augmentations_generator()
     assert torch.equal(sg.augment.generator.get_state(), ref.generator.get_state())
     # injectable beside draw_fn
     sg.augment.gate_fn = lambda n: torch.full((n, 3), 0.5)
-    assert torch.equal(sg._aug_row_draw(4, 16, 12)[:, 8:11], torch.full((4, 3), 0.5))
+    assert torch.equal(sg._stage_row_draw(sg.augment, 4, 16, 12)[:, 8:11], torch.full((4, 3), 0.5))
 
 
 def test_with_the_feature_off_the_generator_advances_as_before():
@@ -213,13 +213,13 @@ def test_with_the_feature_off_the_generator_advances_as_before():
     sg = _cpu_trainer().enable_diffaugment(seed=12)
     ref = DiffAugment(seed=12)
     for _ in range(3):
-        r = sg._aug_row_draw(4, 16, 12)
+        r = sg._stage_row_draw(sg.augment, 4, 16, 12)
         assert tuple(r.shape) == (4, 8) and torch.equal(r, ref.draw(4, 16, 12))
     assert torch.equal(sg.augment.generator.get_state(), ref.generator.get_state())
     sg.enable_ada()
     sg.disable_ada()
-    assert torch.equal(sg._aug_row_draw(4, 16, 12), ref.draw(4, 16, 12))
-    assert sg._aug_draws() == 2 * sg.k + 1
+    assert torch.equal(sg._stage_row_draw(sg.augment, 4, 16, 12), ref.draw(4, 16, 12))
+    assert sg._stage_draws(sg.augment) == 2 * sg.k + 1
 
 
 # ---- the C ABI -----------------------------------------------------------------------------------------------------------------------
@@ -248,10 +248,12 @@ def test_argument_errors_come_back_before_any_launch(lib):
     for k in range(3):
         q = list(p)
         q[k] = None
-        assert gate(q[0], q[1], q[2], 4, None) == -1 and "null pointer" in _err(lib), k
-    assert gate(p[0], p[1], p[2], 0, None) == -1 and "n = 0" in _err(lib)
-    assert gate(ctypes.c_void_p(0x10000004), p[1], p[2], 4, None) == -1 and "aligned" in _err(lib)
-    assert gate(p[0], p[1], p[0], 4, None) == -1 and "alias" in _err(lib)
+        assert gate(q[0], q[1], q[2], 4, 3, None) == -1 and "null pointer" in _err(lib), k
+    assert gate(p[0], p[1], p[2], 0, 3, None) == -1 and "n = 0" in _err(lib)
+    assert gate(ctypes.c_void_p(0x10000004), p[1], p[2], 4, 3, None) == -1 and "aligned" in _err(lib)
+    assert gate(p[0], p[1], p[0], 4, 3, None) == -1 and "alias" in _err(lib)
+    for g in (0, 5, -1):                                                # the uniforms live in slots 8..11: 1 to 4 groups
+        assert gate(p[0], p[1], p[2], 4, g, None) == -1 and f"n_groups = {g} (1 to 4)" in _err(lib), g
     obs = lib.srgan_ada_observe
     maps = (ctypes.c_void_p * 5)(*[0x20000000 + (i << 20) for i in range(5)])
     per = (ctypes.c_longlong * 5)(16, 4, 4, 4, 4)

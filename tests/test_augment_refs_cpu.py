@@ -164,13 +164,13 @@ def test_trainers_host_side():
     with pytest.raises(NotImplementedError, match="SingleGAN_training.*SRGAN_training"):
         single.enable_diffaugment()
     sg = SRGAN_training([G, D, E], [None] * 3, crit, lbd, 3, "cpu", np.eye(4), 4, "mu", 8)
-    assert sg.augment is None and sg._aug_draws() == 0
+    assert sg.augment is None and sg._stage_draws(sg.augment) == 0
     assert sg.enable_diffaugment(policy="color,cutout", translation=0.2, cutout=0.25, seed=3) is sg
-    assert (sg.augment.flags, sg.augment.translation, sg.augment.cutout) == (5, 0.2, 0.25) and sg._aug_draws() == 7      # 2k + 1
+    assert (sg.augment.flags, sg.augment.translation, sg.augment.cutout) == (5, 0.2, 0.25) and sg._stage_draws(sg.augment) == 7      # 2k + 1
     with pytest.raises(ValueError):
         sg.enable_diffaugment(policy="colour")
     sg.enable_diffaugment(policy="")
-    assert sg.augment is not None and sg._aug_draws() == 0 and not sg._aug_on()                                        # identity
+    assert sg.augment is not None and sg._stage_draws(sg.augment) == 0 and not sg._stage_on(sg.augment)                                        # identity
     sg.disable_diffaugment()
     assert sg.augment is None
     from srgan_amd import dp
@@ -188,8 +188,8 @@ def test_trainers_host_side():
         return torch.full((n, 8), float(len(calls)))
 
     sg.augment.draw_fn = fixed
-    pair = sg._aug_tables(2, 4, 16, 12)
-    one = sg._aug_tables(1, 4, 16, 12)
+    pair = sg._stage_tables(sg.augment, 2, 4, 16, 12)
+    one = sg._stage_tables(sg.augment, 1, 4, 16, 12)
     assert calls == [(4, 16, 12)] * 3 and tuple(pair.shape) == (8, 8) and tuple(one.shape) == (4, 8)
     assert torch.equal(pair[:4], torch.full((4, 8), 1.0)) and torch.equal(pair[4:], torch.full((4, 8), 2.0))
 

@@ -196,6 +196,32 @@ def test_extension_absent_from_the_checkpoint_is_missing_and_stays_on():
     assert sg.augment is not None and torch.equal(sg.augment.generator.get_state(), gen)
 
 
+def test_sections_with_the_keys_of_the_first_format_still_load():
+    """``augment``, ``geometry`` and ``ada`` written out as the first release of each wrote them: enabled by the load, nothing
+    missing or unexpected, and each stage draws what a stage made from the saved settings and generator state draws"""
+    from srgan_amd.augment import DiffAugment, GeometricAugment
+    gen_a, gen_g = torch.Generator().manual_seed(21).get_state(), torch.Generator().manual_seed(22).get_state()
+    sd = _trainer().state_dict()
+    sd["augment"] = {"policy": "color,cutout", "translation": 0.125, "cutout": 0.25, "generator": gen_a.clone()}
+    sd["geometry"] = {"policy": "flip,rotate", "scale_std": 0.3, "rotate_max": 0.5, "generator": gen_g.clone()}
+    sd["ada"] = {"target": 0.5, "interval": 3, "kimg": 100.0, "p_max": 0.75, "p": 0.25, "seen": 0, "n_pos": 0, "n_neg": 0,
+                 "n_total": 0, "adjustments": 0, "last_r": 0.0, "n": None}
+    sg = _trainer()
+    report = sg.load_state_dict(sd)
+    assert report.missing == [] and report.unexpected == []
+    assert [type(s) for s in sg._stages()] == [DiffAugment, GeometricAugment]
+    assert (sg.augment.policy, sg.augment.translation, sg.augment.cutout) == ("color,cutout", 0.125, 0.25)
+    assert (sg.geometry.policy, sg.geometry.scale_std, sg.geometry.rotate_max) == ("flip,rotate", 0.3, 0.5)
+    assert (sg._ada.target, sg._ada.interval, sg._ada.kimg, sg._ada.p_max, sg._ada.p) == (0.5, 3, 100.0, 0.75, 0.25)
+    old_a, old_g = DiffAugment("color,cutout", 0.125, 0.25), GeometricAugment("flip,rotate", 0.3, 0.5)
+    old_a.generator.set_state(gen_a)
+    old_g.generator.set_state(gen_g)
+    for stage, old, groups in ((sg.augment, old_a, 3), (sg.geometry, old_g, 4)):
+        assert torch.equal(stage.draw_fn(4, 16, 12), old.draw(4, 16, 12))
+        assert torch.equal(stage.gate_fn(4), torch.rand(4, groups, generator=old.generator, dtype=torch.float32))
+    assert sorted(sg.state_dict()["augment"]) == sorted(sd["augment"]) and sorted(sg.state_dict()["geometry"]) == sorted(sd["geometry"])
+
+
 def test_r1_section_into_singlegan_is_unexpected_not_a_crash():
     sg = _singlegan()
     sd = sg.state_dict()

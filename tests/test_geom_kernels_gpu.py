@@ -1,5 +1,5 @@
 """GPU: the geometric-augmentation kernels (csrc/augment_geom.hip through ops.geom_augment; the gate of csrc/ada.hip through
-ops.ada_gate_geom) against the restatement of tests/geom_common.py -- forward and backward under max(8 * e32, gamma(L)) per
+ops.ada_gate) against the restatement of tests/geom_common.py -- forward and backward under max(8 * e32, gamma(L)) per
 sample, the permutations, the gated form, bit copies, independence of the batch, the two access paths and the device-side
 sanitising bit for bit.  Shapes and tables: geom_common.SHAPES / tables (both sides of every switch-over of the implementation are
 in the list)."""
@@ -163,7 +163,7 @@ def _gate_restated(rows, p):
 
 
 @pytest.mark.parametrize("p", [0.0, 0.3, 1.0])
-def test_ada_gate_geom_against_the_restatement(p):
+def test_gate_of_four_groups_against_the_restatement(p):
     import numpy as np
     from srgan_amd import ops
     pf = float(np.float32(p))
@@ -177,7 +177,7 @@ def test_ada_gate_geom_against_the_restatement(p):
     rows[len(combos):, 8:12] = torch.rand(300, 4, generator=g)
     rows[:, 12:] = torch.randn(rows.shape[0], 4, generator=g)             # the unused slots do not matter
     state = ops.ada_state_new(torch.device("cuda"), pf, 0.6, 0.01, 1.0, 4)
-    got = ops.ada_gate_geom(rows.cuda(), state).cpu()
+    got = ops.ada_gate(rows.cuda(), state, 4).cpu()
     want = _gate_restated(rows, torch.tensor(pf))
     assert torch.equal(got[:, :7], rows[:, :7]) and torch.equal(got, want)
     masks = set(got[:, 7].tolist())
@@ -185,4 +185,4 @@ def test_ada_gate_geom_against_the_restatement(p):
     if p == 1.0:
         assert float(got[len(combos):, 7].max()) == 0.0                   # every uniform in [0, 1) passes
     for n in (1, 255, 257):                                               # the launch's tail
-        assert torch.equal(ops.ada_gate_geom(rows[:n].contiguous().cuda(), state).cpu(), want[:n])
+        assert torch.equal(ops.ada_gate(rows[:n].contiguous().cuda(), state, 4).cpu(), want[:n])

@@ -249,17 +249,17 @@ def test_trainers_host_side():
     single, sg = _cpu_trainers()
     with pytest.raises(NotImplementedError, match="SingleGAN_training.*SRGAN_training.enable_geometric_augment"):
         single.enable_geometric_augment()
-    assert sg.geometry is None and sg._geom_draws() == 0 and not sg._geom_on()
+    assert sg.geometry is None and sg._stage_draws(sg.geometry) == 0 and not sg._stage_on(sg.geometry)
     assert sg.enable_geometric_augment(policy="flip,scale", scale_std=0.1, rotate_max=0.5, seed=3) is sg
     assert isinstance(sg.geometry, GeometricAugment) and sg.geometry in sg._extensions()
-    assert (sg.geometry.flags, sg.geometry.scale_std, sg.geometry.rotate_max) == (5, 0.1, 0.5) and sg._geom_draws() == 7      # 2k + 1
-    assert sg.augment is None and sg._aug_draws() == 0                      # DiffAugment is a switch of its own
+    assert (sg.geometry.flags, sg.geometry.scale_std, sg.geometry.rotate_max) == (5, 0.1, 0.5) and sg._stage_draws(sg.geometry) == 7      # 2k + 1
+    assert sg.augment is None and sg._stage_draws(sg.augment) == 0                      # DiffAugment is a switch of its own
     with pytest.raises(ValueError):
         sg.enable_geometric_augment(policy="turn")
     sg.enable_geometric_augment(policy="")
-    assert sg.geometry is not None and sg._geom_draws() == 0 and not sg._geom_on()                                          # identity
+    assert sg.geometry is not None and sg._stage_draws(sg.geometry) == 0 and not sg._stage_on(sg.geometry)                                          # identity
     img = torch.zeros(4, 3, 8, 8)
-    assert sg._aug(img) is img and sg._geom(img, 1) is img                  # no draw, no launch
+    assert sg._aug(img) is img and sg._aug(img, 1, [sg.geometry]) is img                  # no draw, no launch
     sg.disable_geometric_augment()
     assert sg.geometry is None and sg._extensions() == []
     # the draw order of a step: the injected source is asked 2k + 1 times for [B, 8]; the eager path uploads what it returns
@@ -271,8 +271,8 @@ def test_trainers_host_side():
         return torch.full((n, 8), float(len(calls)))
 
     sg.geometry.draw_fn = fixed
-    pair = sg._geom_tables(2, 4, 16, 12)
-    one = sg._geom_tables(1, 4, 16, 12)
+    pair = sg._stage_tables(sg.geometry, 2, 4, 16, 12)
+    one = sg._stage_tables(sg.geometry, 1, 4, 16, 12)
     assert calls == [(4, 16, 12)] * 3 and tuple(pair.shape) == (8, 8) and tuple(one.shape) == (4, 8)
     assert torch.equal(pair[:4], torch.full((4, 8), 1.0)) and torch.equal(pair[4:], torch.full((4, 8), 2.0))
     # the switches drop a recording
@@ -293,9 +293,9 @@ def test_diffaugment_tables_do_not_depend_on_the_geometric_stage():
         state = torch.get_rng_state()
         aug, geo = [], []
         for count in [2] * sg.k + [1]:                                    # a step's hand-outs, in its order
-            aug.append(sg._aug_tables(count, 4, 16, 16))
+            aug.append(sg._stage_tables(sg.augment, count, 4, 16, 16))
             if geometry:
-                geo.append(sg._geom_tables(count, 4, 16, 16))
+                geo.append(sg._stage_tables(sg.geometry, count, 4, 16, 16))
         assert torch.equal(torch.get_rng_state(), state)                  # the style noise's generator is not touched
         return torch.cat(aug), (torch.cat(geo) if geo else None), sg
 
@@ -310,19 +310,19 @@ def test_diffaugment_tables_do_not_depend_on_the_geometric_stage():
 
 def test_rows_with_the_adaptive_probability_on():
     """the rows a hand-out stages: the table, then four uniforms per sample from the same generator, in slots 8..11"""
-    from srgan_amd.augment import GeometricAugment, join_geom_rows
+    from srgan_amd.augment import GeometricAugment
     _, sg = _cpu_trainers(k=2)
     sg.enable_geometric_augment(seed=9)
-    assert tuple(sg._geom_row_draw(4, 8, 8).shape) == (4, 8)
+    assert tuple(sg._stage_row_draw(sg.geometry, 4, 8, 8).shape) == (4, 8)
     sg.enable_geometric_augment(seed=9)
     sg._ada = object()                                                    # (on: only its presence is read here)
-    rows = sg._geom_row_draw(4, 8, 8)
+    rows = sg._stage_row_draw(sg.geometry, 4, 8, 8)
     ref = GeometricAugment(seed=9)
     t, u = ref.draw(4, 8, 8), ref.draw_gate(4)
     assert tuple(rows.shape) == (4, 16) and torch.equal(rows[:, :8], t) and torch.equal(rows[:, 8:12], u)
-    assert float(rows[:, 12:].abs().max()) == 0.0 and torch.equal(rows, join_geom_rows(t, u))
+    assert float(rows[:, 12:].abs().max()) == 0.0 and torch.equal(rows, ref.join_rows(t, u))
     with pytest.raises(ValueError):
-        join_geom_rows(t, u[:, :3])
+        ref.join_rows(t, u[:, :3])
 
 
 def test_checkpoint_section_is_present_only_when_on():
@@ -359,11 +359,11 @@ def test_argument_errors_come_back_before_any_launch(lib):
             assert call(**kw) == -1, (name, kw)
             err = lib.srgan_last_error()
             assert name in err and word in err, (name, kw, err)
-    gate = lib.srgan_ada_gate_geom
-    for args, word in (((None, p[3], p[1], 4), b"null pointer"), ((p[0], None, p[1], 4), b"null pointer"),
-                       ((p[0], p[3], None, 4), b"null pointer"), ((p[0], p[3], p[1], 0), b"n ="), ((p[0], p[3], p[0], 4), b"alias"),
-                       ((ctypes.c_void_p(0x10000004), p[3], p[1], 4), b"aligned")):
-        assert gate(*args, None) == -1 and b"ada_gate_geom" in lib.srgan_last_error() and word in lib.srgan_last_error(), args
+    gate = lib.srgan_ada_gate
+    for args, word in (((None, p[3], p[1], 4, 4), b"null pointer"), ((p[0], None, p[1], 4, 4), b"null pointer"),
+                       ((p[0], p[3], None, 4, 4), b"null pointer"), ((p[0], p[3], p[1], 0, 4), b"n ="), ((p[0], p[3], p[0], 4, 4), b"alias"),
+                       ((ctypes.c_void_p(0x10000004), p[3], p[1], 4, 4), b"aligned")):
+        assert gate(*args, None) == -1 and b"ada_gate" in lib.srgan_last_error() and word in lib.srgan_last_error(), args
 
 
 def test_ops_refuse_what_the_kernels_do_not_take():
@@ -373,7 +373,7 @@ def test_ops_refuse_what_the_kernels_do_not_take():
     with pytest.raises(_lib.SrganHipError, match="no CPU fallback"):
         ops.geom_augment(x, torch.zeros(2, 8), 15)
     with pytest.raises(_lib.SrganHipError, match="no CPU fallback"):
-        ops.ada_gate_geom(torch.zeros(2, 16), torch.zeros(56, dtype=torch.uint8))
+        ops.ada_gate(torch.zeros(2, 16), torch.zeros(56, dtype=torch.uint8), 4)
 
 
 # ---- launch descriptors (no GPU: tests/hip_shim/launch_shim.c logs them) -------------------------------------------------------------
@@ -400,7 +400,7 @@ def test_launch_descriptors_within_aql_limits_and_launch_counts(lib, tmp_path):
             continue
         kname, gx, gy, gz, bx, by, bz, dyn = line.split()
         gx, gy, gz, bx, by, bz, dyn = map(int, (gx, gy, gz, bx, by, bz, dyn))
-        short = next((s for s in ("ada_gate_geom_kernel", "geom_fwd_kernel", "geom_bwd_kernel") if s in kname), None)
+        short = next((s for s in ("ada_gate_kernel", "geom_fwd_kernel", "geom_bwd_kernel") if s in kname), None)
         assert short is not None, kname
         k = desc[kname]
         ctx = (cur, kname, (gx, gy, gz), (bx, by, bz))
@@ -413,7 +413,7 @@ def test_launch_descriptors_within_aql_limits_and_launch_counts(lib, tmp_path):
     assert len(seen) == len(drive_geom.SHAPES) and set(gc.CASES) <= set(drive_geom.SHAPES)
     for n, h, w in drive_geom.SHAPES:
         grid = min(gc.items((n, h, w)), gc.GRID_CAP)
-        want = [("geom_fwd_kernel", grid), ("geom_bwd_kernel", grid)] * 2 + [("ada_gate_geom_kernel", -(-n // 256))]
+        want = [("geom_fwd_kernel", grid), ("geom_bwd_kernel", grid)] * 2 + [("ada_gate_kernel", -(-n // 256))]
         assert seen[f"{n} {h} {w}"] == want, (n, h, w)
     assert seen["4 128 128"][0][1] == 32 and seen["2049 2 2"][0][1] == 2048 and seen["64 256 256"][0][1] == 2048
     names = [k for k in desc if "geom_fwd_kernel" in k or "geom_bwd_kernel" in k]

@@ -33,7 +33,7 @@ class Feed:
         return t.clone()
 
 
-def _geom_tables(seed, n_steps=1, k=K):
+def _geo_tables(seed, n_steps=1, k=K):
     """2k + 1 tables per step in the draw order: per discriminator update real then fake, then phase 1's"""
     from srgan_amd.augment import GeometricAugment
     geo = GeometricAugment(seed=seed)
@@ -87,7 +87,7 @@ def test_step_vs_the_oracle_on_the_restatement(monkeypatch, with_diffaugment):
     """the same injected tables on both sides: the three losses, every loss term and the parameters after the step at the bounds of
     test_train_gpu.step_vs_oracle (1e-3; close_params), and errG_dis more than 1e-4 away from the plain step's"""
     seed, batch_seed = 5, 42
-    geo_tables = _geom_tables(31)
+    geo_tables = _geo_tables(31)
     aug_tables, cut = _aug_tables(21)
     x, label = otrainer.synthetic_batch(BATCH, SIZE, 4, seed=batch_seed)
     real_d = otrainer.nets.discriminator
@@ -268,7 +268,7 @@ def test_p_pinned_at_0_is_the_plain_step():
 
 def test_p_pinned_at_1_is_the_ungated_step():
     aug_tables, _ = _aug_tables(21, 2)
-    geo_tables = _geom_tables(22, 2)
+    geo_tables = _geo_tables(22, 2)
 
     def build(ada):
         sg = make_trainer("T", BATCH, K, 4).enable_diffaugment(seed=0).enable_geometric_augment(seed=0)
@@ -316,7 +316,7 @@ def test_checkpoint_resume_is_bit_identical(tmp_path, graph):
 
 
 def test_generic_discriminator_path_matches_the_fused_one():
-    geo_tables = _geom_tables(23)
+    geo_tables = _geo_tables(23)
     aug_tables, _ = _aug_tables(24)
     x, label = otrainer.synthetic_batch(BATCH, SIZE, 4, seed=44)
 
@@ -340,7 +340,7 @@ def test_generic_discriminator_path_matches_the_fused_one():
 
 def test_bf16_compute_mode_step():
     from srgan_amd import ops
-    geo_tables = _geom_tables(25)
+    geo_tables = _geo_tables(25)
     x, label = otrainer.synthetic_batch(BATCH, SIZE, 4, seed=46)
 
     def run():
