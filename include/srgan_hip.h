@@ -658,6 +658,48 @@ int srgan_r1_seed(const float* h1, const float* h2, const void* state, float* u0
                   size_t ws_bytes, void* stream);
 int srgan_r1_finalize(const void* ws, size_t ws_bytes, int n, int h, int w, void* state, void* stream);
 
+/* Balanced consistency regularisation of the discriminator (Zhang et al., 2020; on real and generated samples: Zhao et al., 2020).
+ * Extension, no counterpart in the reference.  D reads 2n images, [the n it reads anyway | T of each], and is trained to give row r
+ * and row r + n the same score; T is an x-flip followed by an integer translation with zeros shifted in.
+ * srgan_cr_pairs_fwd: one or two fp32 NHWC-dense sources [n0, h, w, 3] and [n1, h, w, 3] (x1 NULL exactly when n1 is 0), n = n0 + n1;
+ * table: n rows of 8 floats [fx, ty, tx, 0, ...]; flags: flip 1, translation 2 (a group that is off is the identity).  ONE launch
+ * writes y[2n, h, w, 3]: rows [0, n) are a bit copy of the concatenated sources, row n + r is T(x_r)[i, j] = xf[i - ty, j - tx] inside
+ * the image, else 0, with xf[i, j] = fx ? x[i, w - 1 - j] : x[i, j].  T copies values (no arithmetic: -0.0 and NaN payloads arrive as
+ * they are); forward only.  Whatever a row holds: fx, ty, tx are truncated and clamped (fx into {0, 1}, |ty| <= h - 1, |tx| <= w - 1)
+ * while still floats, a non-finite value reads 0, every index is bounds-tested: no access outside the image for any table.  16-byte
+ * accesses when 3 w % 4 == 0 and x0, x1, y are 16-byte aligned, else a scalar path that gives the same bits.  -1 with
+ * srgan_last_error() before any launch: c != 3, a NULL pointer (or x1 without rows, rows without x1), n0 <= 0, n1 < 0, h or w <= 0,
+ * 3 h w >= 2^31, an unknown flag bit, a pointer not 4-byte aligned, y overlapping a source.
+ * Record (srgan_cr_state_bytes() = 32 bytes, device memory): {float lambda_real, float lambda_fake, int every, float cr_real,
+ * float cr_fake, int updates, int pad[2]}.  srgan_cr_state_init writes the weights and every and zeroes the rest; srgan_cr_state_set
+ * rewrites the weights and every between steps and keeps the counters (a recorded step reads the weights from the record);
+ * srgan_cr_state_set_updates writes the count of penalised updates and nothing else (resuming from a checkpoint).  One one-thread
+ * launch each.  -1 before any launch: a NULL record, a weight < 0 or not finite, every < 1, a negative count.
+ * srgan_d_losses_cr: srgan_d_losses_crit on maps of rows = 2 * pairs rows whose row r + pairs is the consistency partner of row r.
+ * ONE launch, one workgroup, no atomics, a fixed order.  The front `pairs` rows get everything srgan_d_losses_crit computes for a map of
+ * `pairs` rows (rows_first <= pairs: the split of t_first / t_rest and the rows with a class loss); the back rows carry no GAN and no
+ * class loss (dz = 0 there).  With m_s(r) the mean of row r of o[s], pairs [0, pairs_first) in group 1 (lambda_real), the rest in
+ * group 2 (lambda_fake), B_g the group's pair count and c_g = lambda_g * every read from the record:
+ *   cr_g = (1 / S) sum_s (1 / B_g) sum_{r in g} (m_s(r) - m_s(r + pairs))^2,
+ *   d_o[s][r, j] += 2 c_g / (S B_g per_row[s]) * (m_s(r) - m_s(r + pairs)) for r < pairs, and the negative of that at r + pairs.
+ * vals[7] = {gan_first, class, gan_rest, total, cr_first, cr_rest, total_with_cr = total + c_1 cr_first + c_2 cr_rest}; the record's
+ * cr_real / cr_fake = cr_first / cr_rest and updates += 1.  A group with c_g == 0 or no pair is taken out by a select, not a product:
+ * it adds exactly 0 to total_with_cr, its back rows' d_o is exactly 0 whatever those rows hold (NaN, Inf), and its front rows' d_o is
+ * the GAN gradient's bits; an empty group's cr term is 0.  With both weights 0, vals[0..3] and the front rows of d_o and dz equal bit
+ * for bit what srgan_d_losses_crit gives on the `pairs`-row prefix.  The row means of a scale are staged in LDS: pairs <=
+ * SRGAN_CR_MAX_PAIRS.  -1 before any launch: what srgan_d_losses_crit refuses, a NULL record, pairs outside [1, SRGAN_CR_MAX_PAIRS],
+ * rows != 2 * pairs, pairs_first or rows_first outside [0, pairs], rows * per_row[s] >= 2^31. */
+#define SRGAN_CR_MAX_PAIRS 1024
+int srgan_cr_pairs_fwd(const float* x0, int n0, const float* x1, int n1, const float* table, float* y, int c, int h, int w, int flags,
+                       void* stream);
+size_t srgan_cr_state_bytes(void);
+int srgan_cr_state_init(void* state, float lambda_real, float lambda_fake, int every, void* stream);
+int srgan_cr_state_set(void* state, float lambda_real, float lambda_fake, int every, void* stream);
+int srgan_cr_state_set_updates(void* state, int updates, void* stream);
+int srgan_d_losses_cr(const float* const* o, const long long* per_row, const float* const* z, int n_scales, int rows, int rows_first,
+                      int n_class, const long long* label, float t_first, float t_rest, float w_class, int gan_kind, int class_kind,
+                      float* vals, float* const* d_o, float* const* dz, int pairs, int pairs_first, void* state, void* stream);
+
 /* Small host -> device upload (pointer tables: <= 1 MiB, multiple of 4 bytes) carried in kernel arguments: nothing to keep
  * alive on the host after the call returns, and a captured hipGraph stores the bytes in its node instead of re-reading a host
  * address at replay (no reference counterpart; plumbing of the multi-tensor ops above). */

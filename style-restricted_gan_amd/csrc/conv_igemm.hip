@@ -49,8 +49,10 @@ static const char* const kProfNames[] = {
     "in_stats_partial", "in_apply", "in_bwd_partial", "in_bwd_apply", "in_fwd_slab", "in_bwd_slab", "igemm16_kernel",
     "wino42_kernel",
     // the fused norm + Winograd-transform kernels of the trunk (conv_wino43.hip), HBM-bound too: bytes in the "flops" slot
-    "in_fwd_slab_v", "in_bwd_slab_vz"};
-constexpr int kProfKernels = 40;
+    "in_fwd_slab_v", "in_bwd_slab_vz",
+    // balanced consistency regularisation (consistency.hip): launch counts and per-launch times only, nothing in the "flops" slot
+    "cr_pairs_kernel", "d_losses_cr_kernel"};
+constexpr int kProfKernels = 42;
 
 struct ProfScope {
   bool on;

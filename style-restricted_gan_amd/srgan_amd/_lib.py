@@ -212,6 +212,14 @@ SIGNATURES = {
     "srgan_r1_workspace": (c_size_t, [c_int, c_int, c_int]),
     "srgan_r1_seed": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     "srgan_r1_finalize": (c_int, [P, c_size_t, c_int, c_int, c_int, P, P]),
+    # balanced consistency regularisation (csrc/consistency.hip)
+    "srgan_cr_pairs_fwd": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
+    "srgan_cr_state_bytes": (c_size_t, []),
+    "srgan_cr_state_init": (c_int, [P, c_float, c_float, c_int, P]),
+    "srgan_cr_state_set": (c_int, [P, c_float, c_float, c_int, P]),
+    "srgan_cr_state_set_updates": (c_int, [P, c_int, P]),
+    "srgan_d_losses_cr": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, c_float, c_float, c_float, c_int, c_int, P, P, P, c_int, c_int,
+                                  P, P]),
     "srgan_upload_small": (c_int, [P, P, c_size_t, P]),
     "srgan_maxpool2_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "srgan_pairwise_dist": (c_int, [P, c_int, P, c_int, c_int, P, P]),

@@ -2815,3 +2815,121 @@ def r1_finalize_(ws, n, h, w, state):
     into the record.  hipGraph-capturable; nothing comes back to the host."""
     _lib.check(_lib.load().srgan_r1_finalize(_ptr(ws), ws.numel() * ws.element_size(), int(n), int(h), int(w), _ptr(state),
                                              _stream()), "r1_finalize")
+
+
+# ---- balanced consistency regularisation of the discriminator (srgan_amd.consistency; extension, no counterpart in the reference) ----
+CR_FLIP, CR_TRANSLATION = 1, 2
+CR_ROW = 8                     # floats per table row: [fx, ty, tx, 0, 0, 0, 0, 0]
+CR_MAX_PAIRS = 1024            # SRGAN_CR_MAX_PAIRS of include/srgan_hip.h: the fused loss stages the row means in LDS
+
+
+def cr_pairs(xs, table, flags):
+    """The rows D reads in a consistency-regularised update, in ONE launch: ``xs`` (one or two batches ``[n_i, 3, H, W]``, n rows
+    together) -> ``y[2n, 3, H, W]`` whose rows ``[0, n)`` are a bit copy of ``cat_batch(xs)`` and whose row ``n + r`` is ``T`` of row
+    ``r``: an x-flip, then an integer translation with zeros shifted in, from one device row ``[fx, ty, tx, 0, ...]`` of
+    ``table[n, 8]``, whichever of the two ``flags`` names (CR_FLIP | CR_TRANSLATION).  Forward only: an input that requires grad
+    is refused.  hipGraph-capturable."""
+    if not 1 <= len(xs) <= 2:
+        raise _lib.SrganHipError(f"cr_pairs: {len(xs)} sources (one or two)")
+    if any(x.requires_grad for x in xs):
+        raise _lib.SrganHipError("cr_pairs: an input requires grad; the pair builder has no backward (detach it)")
+    with torch.no_grad():
+        xs = [to_nhwc(x) for x in xs]
+        for x in xs:
+            _require_gpu(x, "cr_pairs")
+            if x.dim() != 4 or x.shape[1] != 3 or x.shape[1:] != xs[0].shape[1:] or x.dtype != torch.float32:
+                raise _lib.SrganHipError(f"cr_pairs: images of shape {tuple(x.shape)}, {x.dtype} (float32, three channels, one size "
+                                         "for all sources)")
+        n = sum(x.shape[0] for x in xs)
+        _require_gpu(table, "cr_pairs table")
+        if tuple(table.shape) != (n, CR_ROW) or not table.is_contiguous() or table.dtype != torch.float32:
+            raise _lib.SrganHipError(f"cr_pairs: table of shape {tuple(table.shape)}, a contiguous float32 [{n}, {CR_ROW}] expected")
+        flags = int(flags)
+        if flags & ~3:
+            raise _lib.SrganHipError(f"cr_pairs: flags = {flags} (flip 1, translation 2)")
+        _, _, h, w = xs[0].shape
+        y = nhwc_empty(2 * n, 3, h, w, xs[0].device)
+        x1 = xs[1] if len(xs) > 1 else None
+        _lib.check(_lib.load().srgan_cr_pairs_fwd(_ptr(xs[0]), xs[0].shape[0], _ptr(x1), x1.shape[0] if x1 is not None else 0,
+                                                  _ptr(table), _ptr(y), 3, h, w, flags, _stream()), "cr_pairs_fwd")
+        return y
+
+
+def cr_state_new(device, lambda_real, lambda_fake, every):
+    """Device-resident record {lambda_real, lambda_fake, every, cr_real, cr_fake, updates, pad, pad}, counters at zero."""
+    lib = _lib.load()
+    st = torch.empty(lib.srgan_cr_state_bytes(), dtype=torch.uint8, device=device)
+    _lib.check(lib.srgan_cr_state_init(_ptr(st), float(lambda_real), float(lambda_fake), int(every), _stream()), "cr_state_init")
+    return st
+
+
+def cr_state_set(state, lambda_real, lambda_fake, every):
+    """Rewrite the weights and every between steps; the counters stay (a recorded step reads the record)."""
+    _lib.check(_lib.load().srgan_cr_state_set(_ptr(state), float(lambda_real), float(lambda_fake), int(every), _stream()), "cr_state_set")
+
+
+def cr_state_set_updates(state, updates):
+    """Write the count of penalised updates between steps (resume from a checkpoint); everything else stays."""
+    _lib.check(_lib.load().srgan_cr_state_set_updates(_ptr(state), int(updates), _stream()), "cr_state_set_updates")
+
+
+def cr_state_read(state):
+    """The record as a dict; synchronises the current stream."""
+    torch.cuda.current_stream(state.device).synchronize()
+    lr, lf, every, cr_real, cr_fake, updates = struct.unpack("ffiffi", state.cpu().numpy().tobytes()[:24])
+    return dict(lambda_real=lr, lambda_fake=lf, every=every, cr_real=cr_real, cr_fake=cr_fake, updates=updates)
+
+
+class _DLossesCrFn(Function):
+    @staticmethod
+    def forward(ctx, label, rows_first, t_first, t_rest, w_class, n_scales, gan_kind, class_kind, state, pairs_first, *tensors):
+        outs, logits = tensors[:n_scales], tensors[n_scales:]
+        lib = _lib.load()
+        dev = outs[0].device
+        rows = outs[0].shape[0]
+        if rows % 2:
+            raise _lib.SrganHipError(f"d_losses_cr: maps of {rows} rows; 2 * pairs expected (ops.cr_pairs builds them)")
+        o = [t if (t.is_contiguous() or is_nhwc_dense(t)) else t.contiguous() for t in outs]
+        for t in o:
+            _require_gpu(t, "d_losses_cr")
+            if t.dim() == 4 and t.shape[1] != 1:
+                raise _lib.SrganHipError("d_losses_cr: the GAN maps must have one channel")
+        z = [_dense2d(t) for t in logits]
+        nc = z[0].shape[1] if z else 0
+        d_o = [torch.empty_like(t) for t in o]
+        dz = [torch.empty_like(t) for t in z]
+        vals = torch.empty(7, dtype=torch.float32, device=dev)
+        S = n_scales
+        arr = ctypes.c_void_p * S
+        per = (ctypes.c_longlong * S)(*[t.numel() // rows for t in o])
+        if label is not None:
+            label = label.to(device=dev, dtype=torch.int64).contiguous()
+        _lib.check(lib.srgan_d_losses_cr(arr(*[t.data_ptr() for t in o]), per, arr(*[t.data_ptr() for t in z]) if z else None, S, rows,
+                                         int(rows_first), int(nc), _ptr(label), float(t_first), float(t_rest), float(w_class),
+                                         gan_kind, class_kind, _ptr(vals), arr(*[t.data_ptr() for t in d_o]),
+                                         arr(*[t.data_ptr() for t in dz]) if z else None, rows // 2, int(pairs_first), _ptr(state),
+                                         _stream()), "d_losses_cr")
+        ctx.save_for_backward(*d_o, *dz)
+        total_cr, parts = vals[6], vals[:6]
+        ctx.mark_non_differentiable(parts)
+        return total_cr, parts
+
+    @staticmethod
+    def backward(ctx, g, _gp):
+        grads = torch._foreach_mul(list(ctx.saved_tensors), g)      # one multi-tensor launch
+        return (None,) * 10 + tuple(grads)
+
+
+def d_losses_cr(outs, logits, label, rows_first, t_first, t_rest, w_class, state, gan_kind=CRIT_MSE, class_kind=CRIT_MSE,
+                pairs_first=None):
+    """``d_losses`` of a consistency-regularised discriminator evaluation, in one launch: the maps hold ``2 P`` rows, row ``r + P``
+    the partner ``cr_pairs`` made of row ``r``.  The front ``P`` rows get what ``d_losses`` computes for ``P`` rows; on top come
+    ``cr_g = mean_s mean_{r in g} (m_s(r) - m_s(r + P))^2`` over the pairs ``[0, pairs_first)`` (g = first, weight ``lambda_real *
+    every`` of the device record ``state``) and the rest (``lambda_fake * every``), ``m_s`` the patch mean of scale s's map
+    (``pairs_first``: ``rows_first`` by default).  -> (total_with_cr, tensor([gan_first, class, gan_rest, total, cr_first,
+    cr_rest])): the first is what to back-propagate, the six others carry no gradient.  The record takes the two unweighted terms
+    and counts the call."""
+    logits = list(logits) if logits else []
+    return _DLossesCrFn.apply(label, rows_first, t_first, t_rest, w_class, len(outs), _crit_kind(gan_kind, "d_losses_cr"),
+                              _crit_kind(class_kind, "d_losses_cr"), state, rows_first if pairs_first is None else pairs_first,
+                              *outs, *logits)

@@ -4,7 +4,8 @@
 (``_capture``, ``_Recording``), replays it, and drops the recording when something it baked in has changed.  It names no optional
 feature: a feature joins ``_fingerprint()`` and the keep-alive list by being in ``sg._extensions()``, the host-side counters a
 recording advances are those of ``sg._mirrors()``, and the augmentation stages whose host-drawn tables are staged beside the noise
-(one ``_Staged`` per stage, keyed by its ``section``) are those of ``sg._stages()``.
+(one ``_Staged`` per stage, keyed by its ``section``) are those of ``sg._drawing_stages()``: the stages applied to everything D reads
+and any other stage whose tables the step consumes.
 """
 import gc
 import os
@@ -60,7 +61,7 @@ class _StepGraph:
         self.graph = None
         self.x = self.out = None
         self.staged_noise = _Staged("noise draws")            # [len(sg._noise_kinds()), B, ndim]
-        self.staged = {}         # a stage's section -> _Staged of [2k + 1, B, row width], for the stages of sg._stages() that draw
+        self.staged = {}         # a stage's section -> _Staged of [its draws per step, B, row width], for the stages that draw
         self.lab = {}
         self._onehot = {}
         self._versions = None
@@ -263,9 +264,10 @@ class _StepGraph:
             self.lab = {w: torch.empty(nb, dtype=torch.int64, device=dev) for w in ("source", "target")}
             self.table = torch.tensor(np.asarray(sg.ref_label), dtype=torch.float32).to(dev)
         _, _, h, w = x.shape
-        for stage in sg._stages():
-            # a stage's 2k + 1 rows, drawn up front in the order the eager step draws them (SRGAN_training._stage_tables), stage by
-            # stage: each draws from its own generator; what a row holds and how wide it is, is the trainer's business
+        for stage in sg._drawing_stages():
+            # a stage's rows (2k + 1 where it is applied to everything D reads; the trainer says how many: _stage_draws), drawn up
+            # front in the order the eager step draws them (SRGAN_training._stage_tables), stage by stage: each draws from its own
+            # generator; what a row holds and how wide it is, is the trainer's business
             n = sg._stage_draws(stage)
             if n:
                 st = self.staged.setdefault(stage.section, _Staged(stage.section + " tables"))

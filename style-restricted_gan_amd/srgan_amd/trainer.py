@@ -33,6 +33,7 @@ import torch.optim as optim
 from . import dp, ema, ops, spectral
 from . import ada as _adamod
 from .augment import DiffAugment, GeometricAugment
+from . import consistency as _crmod
 from .checkpoint import Checkpointing
 from . import r1 as _r1mod
 from .losses import class_encode, criterion_kind, get_domainloss_D, get_loss_D, has_fused_kind, histogram_imitation
@@ -102,6 +103,7 @@ class SRGAN_training(Checkpointing):
         self.geometry = None           # geometric augmentation of the discriminator's inputs, after DiffAugment (enable_geometric_augment)
         self._ada = None               # adaptive augmentation probability on the device (enable_ada)
         self._r1 = None                # R1 gradient penalty on the real rows (enable_r1)
+        self.bcr = None                # balanced consistency regularisation of D (enable_bcr)
         self._label_cache = {}         # (kind, which) -> (label tensor, its device form): _cached
         self._d_pending = None         # an update_D left its all-reduce / optimiser step to _finish_D: the reducer, or True
         self._sn_cache = (None, None)  # (key, spectral controller or None): _sn
@@ -176,15 +178,28 @@ class SRGAN_training(Checkpointing):
         """Does the step run this stage?  (None, or an empty policy, is the plain step: no draw, no launch)"""
         return stage is not None and stage.flags != 0
 
+    def _drawing_stages(self):
+        """Every stage whose host-drawn tables a step consumes: those of ``_stages()``, then the consistency pairs' (which is not
+        applied to everything D reads: its tables go to the penalised discriminator updates alone)."""
+        return self._stages() + ([self.bcr.stage] if self.bcr is not None else [])
+
+    def _gated(self, stage):
+        """Does the adaptive probability gate this stage's groups?  Those applied to everything D reads; never the consistency
+        transform."""
+        return self._ada is not None and any(stage is s for s in self._stages())
+
     def _stage_draws(self, stage):
-        """tables of a stage a step consumes: 2 per discriminator update, 1 for phase 1"""
+        """tables of a stage a step consumes: 2 per discriminator update, 1 for phase 1; the consistency pairs: 2 per PENALISED
+        discriminator update (real rows, then fake rows), none for phase 1, also with an empty policy"""
+        if self.bcr is not None and stage is self.bcr.stage:
+            return 2 * sum(_crmod.schedule(self.k, self.bcr.every))
         return 2 * self.k + 1 if self._stage_on(stage) else 0
 
     def _stage_row_draw(self, stage, nb, h, w):
         """One host draw of the step: the CPU table [nb, 8] of the stage's ``draw_fn``; with adaptive augmentation on, followed by
         one uniform per group and sample of its ``gate_fn`` and joined into the [nb, 16] rows ``ops.ada_gate`` reads."""
         table = stage.draw_fn(nb, h, w).to(torch.float32)
-        if self._ada is None:
+        if not self._gated(stage):
             return table
         return stage.join_rows(table, stage.gate_fn(nb))
 
@@ -200,7 +215,7 @@ class SRGAN_training(Checkpointing):
         else:
             tabs = [self._stage_row_draw(stage, nb, h, w) for _ in range(count)]
             rows = host_to_device(tabs[0] if count == 1 else torch.cat(tabs, 0), self.device)
-        if self._ada is None:
+        if not self._gated(stage):
             return rows
         self._ada._ensure(rows.device, nb)
         return self._ada.gate(rows, stage.n_groups)
@@ -230,7 +245,7 @@ class SRGAN_training(Checkpointing):
         return (self.optG, self.optD, self.optE)
 
     def _extensions(self):
-        return [x for x in (self._ema, self._sn(), *self._stages(), self._ada, self._r1) if x is not None]
+        return [x for x in (self._ema, self._sn(), *self._stages(), self._ada, self._r1, self.bcr) if x is not None]
 
     def _mirrors(self):
         """who mirrors, on the host, a device-side count that the step advances: Adam's step counts, the EMA's update count"""
@@ -405,7 +420,8 @@ class SRGAN_training(Checkpointing):
         Data parallel: ``_fake`` hands in a pre-computed translation, ``_next_fake`` is work to run UNDER this update's gradient
         all-reduce (the next translation: G does not change during the discriminator loop), ``_defer`` leaves the wait for the
         all-reduce and the optimiser step to ``_finish_D()`` so that the caller can put more independent work in between.
-        ``_index``: which of the step's k updates this is (the R1 penalty runs on update i iff i % every == 0)."""
+        ``_index``: which of the step's k updates this is (the R1 penalty and the consistency terms run on update i iff
+        i % every == 0, each with its own every)."""
         self._finish_D()
         self.D.zero_grad()
         sn = self._sn()
@@ -418,22 +434,34 @@ class SRGAN_training(Checkpointing):
 
         if self._ada is not None:
             self._ada_check()
+        cr = self.bcr if self.bcr is not None and _index % self.bcr.every == 0 else None
+        if self.bcr is not None:
+            self._bcr_check()
         if self._fused_paths():
             # real and fake halves through D as ONE batch (per-sample network: exact; 2x the rows per GEMM launch)
             B = self.source_image.shape[0]
             rest = [s for s in self._stages() if s is not self.augment]
-            if self._stage_on(self.augment):
+            staged = any(self._stage_on(s) for s in self._stages())
+            _, _, h, w = self.source_image.shape
+            if cr is not None and not staged:
+                # consistency pairs straight from the two halves: [real | fake | T(real) | T(fake)] in the launch that would have
+                # concatenated them (tables: real rows, then fake rows, from the pairs' own generator)
+                d_in = ops.cr_pairs([self.source_image.detach(), self.target_image.detach()],
+                                    self._stage_tables(cr.stage, 2, B, h, w), cr.stage.flags)
+            elif self._stage_on(self.augment):
                 # both halves augmented and concatenated in ONE pass (no gradient needed: real rows have none, fake rows are detached)
                 # adaptive augmentation: the two tables went through one gate launch of 2B rows (_stage_tables)
-                _, _, h, w = self.source_image.shape
                 d_in = ops.diffaugment_cat([self.source_image.detach(), self.target_image.detach()],
                                            self._stage_tables(self.augment, 2, B, h, w), self.augment.flags, self.augment.cut(h, w),
                                            gated=self._ada is not None)
             else:
                 d_in = ops.cat_batch([self.source_image, self.target_image.detach()])
             d_in = self._aug(d_in, 2, rest)                # the remaining stages on the 2B rows: one launch each, tables real then fake
+            if cr is not None and staged:
+                # the partners are made of what D reads AFTER every stage: one more launch, the front 2B rows a bit copy
+                d_in = ops.cr_pairs([d_in], self._stage_tables(cr.stage, 2, B, h, w), cr.stage.flags)
             # what D read as the real rows (the R1 penalty is taken there)
-            d_real = d_in[:B] if any(self._stage_on(s) for s in self._stages()) else self.source_image
+            d_real = d_in[:B] if staged else self.source_image
             outs, logits = dp.unwrap(self.D).forward_logits(d_in)
             if self._ada is not None:
                 # the overfitting heuristic on what D says about the real rows; every interval-th call moves p, so the p that
@@ -441,16 +469,26 @@ class SRGAN_training(Checkpointing):
                 self._ada.observe(outs, B, _adamod.threshold(self._kinds()[0]))
                 self.loss_terms["ada_p"] = self._ada.p_tensor()
             # criterion(real, 1) + class loss * lbd + criterion(fake, 0) over both scales, values and gradients: one launch
-            errD, parts = ops.d_losses(outs, logits, self._label_dev("source"), B, 1., 0., self.lbd["class"], *self._kinds())
+            if cr is None:
+                errD, parts = ops.d_losses(outs, logits, self._label_dev("source"), B, 1., 0., self.lbd["class"], *self._kinds())
+                loss_D = errD
+            else:
+                # the same over the front 2B rows, plus the consistency terms between row n and row n + 2B and their gradients
+                # (weights from the device record), still one launch; errD stays the value without them
+                loss_D, parts = ops.d_losses_cr(outs, logits, self._label_dev("source"), B, 1., 0., self.lbd["class"],
+                                                cr._ensure(outs[0].device), *self._kinds())
+                errD = parts[3]
+                self.loss_terms.update(errD_cr_real=parts[4], errD_cr_fake=parts[5])
             errD_real, errD_class, errD_fake = parts[0], parts[1], parts[2]
         else:
             d_real = self._aug(self.source_image)
             errD_real, errD_class = self._d_losses(d_real, 1., "source", True)
             errD_fake, _ = self._d_losses(self._aug(self.target_image.detach()), 0., None, False)
             errD = errD_real + errD_class * self.lbd["class"] + errD_fake
+            loss_D = errD
         self._reduce_arm("D", self.optD)
         with ops.fused_param_grads(not dp.hooks_need_live_grads(), self.device):
-            errD.backward()
+            loss_D.backward()
         if self._r1 is not None and _index % self._r1.every == 0:
             # R1 on the real rows D just read: dP/dW is added to the gradients the backward left, before the optimiser step (and
             # so before the spectral-norm projection and the gradient guard); errD is unchanged
@@ -964,6 +1002,61 @@ class SRGAN_training(Checkpointing):
         return self._r1.stats() if self._r1 is not None else None
 
     # ------------------------------------------------------------------------------------------
+    # balanced consistency regularisation of D (extension, no counterpart in the reference; srgan_amd.consistency)
+    def _bcr_check(self):
+        if dp.world_size() > 1:
+            raise NotImplementedError(f"SRGAN_training: consistency regularisation is on and the process group has {dp.world_size()} "
+                                      "ranks; the doubled discriminator batch is not ordered against the gradient reducer's buckets "
+                                      "(run one process, or disable_bcr())")
+        if not self._fused_paths():
+            raise NotImplementedError("SRGAN_training: consistency regularisation is wired into the fused discriminator pass only "
+                                      "(this package's own G / D / E modules with forward_logits, a one-hot ref_label, criteria "
+                                      "with a fused kernel); use those, or disable_bcr()")
+
+    def enable_bcr(self, lambda_real=10.0, lambda_fake=10.0, every=1, policy="flip,translation", translation=0.125, seed=None):
+        """Balanced consistency regularisation (Zhang et al., 2020; Zhao et al., 2020): from now on discriminator update ``i`` of a
+        step's k reads ``[real | fake | T(real) | T(fake)]`` -- 4B rows, the front 2B exactly what it reads anyway, after every
+        augmentation stage that is on -- iff ``i % every == 0`` and back-propagates ``errD + every * (lambda_real * cr_real +
+        lambda_fake * cr_fake)``, ``cr = mean over the scales and the samples of (m_s(x) - m_s(T(x)))^2`` with ``m_s`` the patch
+        mean of scale s's GAN map (the score R1 uses).  ``T`` is an x-flip (probability 1/2) and an integer translation by up to
+        ``int(size * translation + 0.5)`` pixels with zeros shifted in (``policy``: any comma-separated subset of ``flip``,
+        ``translation``), one draw per row from the regulariser's OWN generator (``seed``): two tables per penalised update (real
+        rows, then fake rows), none for phase 1; the step's noise and the other stages' tables are what they are without it, and
+        the adaptive probability never gates ``T``.  ``T`` exists in the discriminator update only, so it cannot leak into G.
+        ``errD`` and the returned losses are unchanged; ``loss_terms["errD_cr_real"]`` / ``["errD_cr_fake"]`` are the unweighted
+        terms of the step's last penalised update (device scalars).  A penalised update launches the pair builder instead of the
+        concatenation (or after the last stage, with a stage on) and ``d_losses_cr`` instead of ``d_losses``; D's passes run on
+        twice the rows; an unpenalised update is the plain one.  Captured with the step in graph mode, where the tables are staged
+        beside the other stages' (a recording made before is dropped); the weights are device state (``set_bcr_weights``).  R1 is
+        still taken at the front B rows, the adaptive probability still observes them.  Off: no draw, no launch, no allocation, the
+        step is bit-identical to the plain one.  Refused: more than one rank, the generic (non-fused) discriminator path."""
+        state = _crmod.BalancedCR(lambda_real, lambda_fake, every, policy, translation, seed)
+        self.bcr = state
+        try:
+            self._bcr_check()
+        except NotImplementedError:
+            self.bcr = None
+            raise
+        self._guard_changed()
+        return self
+
+    def disable_bcr(self):
+        self.bcr = None
+        self._guard_changed()
+
+    def set_bcr_weights(self, lambda_real, lambda_fake):
+        """Write new weights into the regulariser's device record, between steps; a recorded step reads them from there and stays
+        valid."""
+        if self.bcr is None:
+            raise RuntimeError("set_bcr_weights: consistency regularisation is off (enable_bcr)")
+        self.bcr.set_weights(lambda_real, lambda_fake)
+
+    def bcr_stats(self):
+        """The regulariser's device record as a dict (``lambda_real``, ``lambda_fake``, ``every``, ``cr_real``, ``cr_fake``,
+        ``updates``), or None with the feature off.  SYNCHRONISES the stream."""
+        return self.bcr.stats() if self.bcr is not None else None
+
+    # ------------------------------------------------------------------------------------------
     # device-side gradient guard (extension, no counterpart in the reference; srgan_amd.optim.Adam.enable_grad_guard)
     _GUARD_NETS = ("G", "D", "E")
 
@@ -1123,6 +1216,11 @@ class SingleGAN_training(Checkpointing):
     def enable_r1(self, *args, **kwargs):
         raise NotImplementedError("SingleGAN_training: the R1 penalty is not wired into this trainer's discriminator passes (per-domain "
                                   "sub-batches); use SRGAN_training.enable_r1, or r1.r1_accumulate in a loop of your own")
+
+    def enable_bcr(self, *args, **kwargs):
+        raise NotImplementedError("SingleGAN_training: consistency regularisation is not wired into this trainer's discriminator "
+                                  "passes (per-domain sub-batches); use SRGAN_training.enable_bcr, or consistency.BalancedCR in a "
+                                  "loop of your own")
 
     def opt_sche_initialization(self, lr=[0.0001, 0.0001, 0.0001]):
         lr_G, lr_D, lr_E = lr
