@@ -728,7 +728,7 @@ int srgan_preprocess_u8(const unsigned char* src, int B, int Hs, int Ws, int top
 /* ---- evaluation path (pyfiles/evaluation.py:13-110) ------------------------------------------------
  * The VGG19-bn feature extractor (evaluation.py:13-36: torchvision's vgg19_bn features + avgpool + classifier[:6]) runs its
  * 3x3 convolutions (BatchNorm folded in eval mode, bias + ReLU in the epilogue) and Linear layers on srgan_conv2d_fwd; the
- * one op it needs beyond the train step is nn.MaxPool2d(2, 2): */
+ * one op it needs beyond the train step is nn.MaxPool2d(2, 2) (NHWC, C a multiple of 4; a NaN in a window comes out, as there): */
 int srgan_maxpool2_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream);
 /* PRDC (evaluation.py:98-110 -> prdc.compute_prdc, prdc==0.2, Docker/requirements.txt:13), in the steps of that package:
  * compute_pairwise_distance: dist[i][j] = ||x_i - y_j||_2 for x[N][D], y[M][D] (row-major fp32);

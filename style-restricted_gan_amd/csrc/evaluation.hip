@@ -20,9 +20,15 @@ __global__ void maxpool2_fwd_kernel(const float* __restrict__ x, float* __restri
     const int n = (int)(r / Ho);
     const f32x4* b = reinterpret_cast<const f32x4*>(x) + ((size_t)(n * H + oy * 2) * W + ox * 2) * C4 + c;
     const f32x4 v0 = b[0], v1 = b[C4], v2 = b[(size_t)W * C4], v3 = b[(size_t)W * C4 + C4];
-    f32x4 m;
+    // nn.MaxPool2d's rule, window in row-major order: a later value replaces the maximum if it is larger or NaN, so that a NaN
+    // anywhere in the window comes out (fmaxf would drop it: a NaN from a bad weight file has to reach the features)
+    f32x4 m = v0;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) m[e] = fmaxf(fmaxf(v0[e], v1[e]), fmaxf(v2[e], v3[e]));
+    for (int e = 0; e < 4; ++e) {
+      if (v1[e] > m[e] || v1[e] != v1[e]) m[e] = v1[e];
+      if (v2[e] > m[e] || v2[e] != v2[e]) m[e] = v2[e];
+      if (v3[e] > m[e] || v3[e] != v3[e]) m[e] = v3[e];
+    }
     reinterpret_cast<f32x4*>(y)[i] = m;
   }
 }
