@@ -741,6 +741,32 @@ size_t srgan_prdc_workspace(int N, int M);
 int srgan_prdc_from_dist(const float* dist, int N, int M, const float* r_real, const float* r_fake, int nearest_k,
                          float* out4, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- set metrics beyond the reference (csrc/metrics.hip): Frechet distance and KID over feature matrices.
+ * All entries enqueue on `stream` and never synchronise; a bad argument (N < 2, m < 2, m larger than a set, D < 1, a
+ * workspace that is too small, a null pointer) returns -1 before any launch and writes nothing.
+ * gram_f32: g[na][nb] = A B^T for row-major fp32 matrices of D columns; row r of the product is row idx_a[r] of a[rows_a][D]
+ *   (idx_a = NULL: row r; an index outside [0, rows_a) reads as a row of zeros), the same for b.  Every entry is the fp32 fma
+ *   chain over the features in ascending order.
+ * feature_stats: mean[D] = column means of x[N][D] (float64 sums, rounded once), a[N][D] = (x - mean) / sqrt(N - 1) in fp32,
+ *   *trace = sum a^2 in float64 = the trace of the unbiased covariance.
+ * kid_poly3: for every subset s, rows idx_x[s][m] of x and idx_y[s][m] of y: sums[s] = {sum_{i != j} k(x_i, x_j),
+ *   sum_{i != j} k(y_i, y_j), sum_{i, j} k(x_i, y_j)} with k(u, v) = (u . v / D + 1)^3, and
+ *   *kid = (1 / S) sum_s [(sums[s][0] + sums[s][1]) / (m (m - 1)) - 2 sums[s][2] / m^2].
+ * jacobi_sweep: one sweep of one-sided Jacobi rotations over the n vectors of w[n][L] (in place); *rotations = the number of
+ *   pairs it rotated (0: the vectors are orthogonal to working precision).  nuclear_from_rows: *out = sum_i |w_i|_2 in float64,
+ *   the nuclear norm of w once a sweep has rotated nothing.  Both use srgan_jacobi_workspace(n) bytes, 8-byte aligned. */
+int srgan_gram_f32(const float* a, int rows_a, const int* idx_a, int na, const float* b, int rows_b, const int* idx_b, int nb,
+                   int D, float* g, void* stream);
+size_t srgan_feature_stats_workspace(int N, int D);
+int srgan_feature_stats(const float* x, int N, int D, float* mean, float* a, double* trace, void* ws, size_t ws_bytes,
+                        void* stream);
+size_t srgan_kid_workspace(int num_subsets, int m);
+int srgan_kid_poly3(const float* x, int n_real, const float* y, int n_fake, int D, const int* idx_x, const int* idx_y,
+                    int num_subsets, int m, double* sums, double* kid, void* ws, size_t ws_bytes, void* stream);
+size_t srgan_jacobi_workspace(int n);
+int srgan_jacobi_sweep(float* w, int n, int L, int* rotations, void* ws, size_t ws_bytes, void* stream);
+int srgan_nuclear_from_rows(const float* w, int n, int L, double* out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- collectives of the data-parallel step (SURVEY.md 8 e) -----------------------------------------------------------
  * What replaces torch.nn.DataParallel(net, devices=[0,1,2,3]) of notebook/05-train_Style-Restricted_GAN.ipynb:404-407,446
  * (scatter the batch, replicate the module, gather the outputs, reduce the gradients on device 0): one process per GPU with

@@ -226,6 +226,15 @@ SIGNATURES = {
     "srgan_kth_smallest_rows": (c_int, [P, c_int, c_int, c_int, P, P]),
     "srgan_prdc_workspace": (c_size_t, [c_int, c_int]),
     "srgan_prdc_from_dist": (c_int, [P, c_int, c_int, P, P, c_int, P, P, c_size_t, P]),
+    # Frechet distance and KID (csrc/metrics.hip)
+    "srgan_gram_f32": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, c_int, P, P]),
+    "srgan_feature_stats_workspace": (c_size_t, [c_int, c_int]),
+    "srgan_feature_stats": (c_int, [P, c_int, c_int, P, P, P, P, c_size_t, P]),
+    "srgan_kid_workspace": (c_size_t, [c_int, c_int]),
+    "srgan_kid_poly3": (c_int, [P, c_int, P, c_int, c_int, P, P, c_int, c_int, P, P, P, c_size_t, P]),
+    "srgan_jacobi_workspace": (c_size_t, [c_int]),
+    "srgan_jacobi_sweep": (c_int, [P, c_int, c_int, P, P, c_size_t, P]),
+    "srgan_nuclear_from_rows": (c_int, [P, c_int, c_int, P, P, c_size_t, P]),
 }
 
 _lib = None

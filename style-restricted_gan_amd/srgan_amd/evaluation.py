@@ -10,6 +10,11 @@ imports are not in this image and are provided here:
   launches on the train step's Winograd / implicit-GEMM kernels, five 2x2 max pools and the two Linear layers as 1x1
   convolutions (flattened in NCHW order like ``torch.flatten``).  Inference only (no backward).
 * ``compute_prdc`` -- prdc 0.2's function of that name over the HIP distance / k-th value / set-statistics kernels.
+
+Beyond the reference (csrc/metrics.hip): ``compute_frechet_distance`` (FID's formula over whatever features it is
+given), ``compute_kid`` / ``kid_subsets`` (Kernel Inception Distance, StyleGAN2-ADA's estimator) and the ``get_fd`` /
+``get_kid`` / ``get_metrics`` methods of ``GAN_evaluation``.  Over the VGG19-bn features of this path the Frechet number is NOT
+comparable with published Inception-v3 FIDs; it ranks runs of this project against each other.
 """
 import ctypes
 
@@ -22,7 +27,8 @@ from .inference import cuda2numpy, image_from_output
 from .losses import weights_init
 from .ops import ACT_NONE, ACT_RELU, PAD_ZERO
 
-__all__ = ["VGG19_bn", "vgg19_bn", "vgg_model", "GAN_evaluation", "evaluation_init", "compute_prdc", "maxpool2"]
+__all__ = ["VGG19_bn", "vgg19_bn", "vgg_model", "GAN_evaluation", "evaluation_init", "compute_prdc", "maxpool2",
+           "compute_frechet_distance", "compute_kid", "kid_subsets", "FD_MAX_SIDE"]
 
 VGG19_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512, "M"]
 
@@ -191,6 +197,120 @@ def compute_prdc(real_features, fake_features, nearest_k, device="cuda"):
     return dict(precision=p, recall=r, density=dn, coverage=c)
 
 
+FD_MAX_SIDE = 4096        # the smaller set of compute_frechet_distance: its Gram matrix W [n, L] is what the Jacobi sweeps work on
+
+
+def _feature_pair(real_features, fake_features, who):
+    """Shape checks on the host arrays / tensors as given (before anything touches the library)."""
+    rs, fs = tuple(real_features.shape), tuple(fake_features.shape)
+    if len(rs) != 2 or len(fs) != 2:
+        raise ValueError(f"{who}: features must be [N, D] matrices, got {rs} and {fs}")
+    if rs[1] != fs[1]:
+        raise ValueError(f"{who}: feature dimensions differ ({rs[1]} and {fs[1]})")
+    if rs[1] < 1:
+        raise ValueError(f"{who}: no feature columns")
+    return rs[0], fs[0], rs[1]
+
+
+def _feature_stats(lib, x, st):
+    """(mean [D] fp32, A = (x - mean) / sqrt(N - 1) fp32, trace: 1-element float64 tensor) on the device."""
+    n, d = x.shape
+    mean = torch.empty(d, dtype=torch.float32, device=x.device)
+    a = torch.empty_like(x)
+    trace = torch.empty(1, dtype=torch.float64, device=x.device)
+    nb = lib.srgan_feature_stats_workspace(n, d)
+    ws = torch.empty(nb // 8, dtype=torch.float64, device=x.device)
+    _lib.check(lib.srgan_feature_stats(ops._ptr(x), n, d, ops._ptr(mean), ops._ptr(a), ops._ptr(trace), ops._ptr(ws), nb, st),
+               "feature_stats")
+    return mean, a, trace
+
+
+def compute_frechet_distance(real_features, fake_features, device="cuda", max_sweeps=30, return_terms=False):
+    """pytorch-fid's ``calculate_frechet_distance`` on the sets' means and unbiased covariances (``np.cov``):
+    ``|mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr sqrt(S1 S2)``, a Python float, not clamped at 0.  ``tr sqrt(S1 S2)`` is the nuclear
+    norm of ``A1 A2^T`` with ``A = (X - mean) / sqrt(N - 1)``: only that ``n1 x n2`` matrix is decomposed (one-sided Jacobi sweeps
+    over its shorter side until a sweep rotates nothing; the host reads one counter per sweep).  ``return_terms=True``: a dict of
+    ``fd``, the four terms (``mean_term``, ``trace_real``, ``trace_fake``, ``nuclear``) and ``sweeps``."""
+    n1, n2, d = _feature_pair(real_features, fake_features, "compute_frechet_distance")
+    if n1 < 2 or n2 < 2:
+        raise ValueError(f"compute_frechet_distance: a set has fewer than 2 rows ({n1} and {n2}): no covariance")
+    if min(n1, n2) > FD_MAX_SIDE:
+        raise ValueError(f"compute_frechet_distance: the smaller set has {min(n1, n2)} rows, the limit is {FD_MAX_SIDE}")
+    if int(max_sweeps) < 1:
+        raise ValueError("compute_frechet_distance: max_sweeps must be at least 1")
+    lib = _lib.load()
+    x, y = _dev_f32(real_features, device), _dev_f32(fake_features, device)
+    st = ops._stream()
+    mu1, a1, t1 = _feature_stats(lib, x, st)
+    mu2, a2, t2 = _feature_stats(lib, y, st)
+    # the shorter side carries the vectors: n = min(n1, n2) of length L = max(n1, n2)
+    p, q = (a1, a2) if n1 <= n2 else (a2, a1)
+    n, length = p.shape[0], q.shape[0]
+    w = torch.empty(n, length, dtype=torch.float32, device=x.device)
+    _lib.check(lib.srgan_gram_f32(ops._ptr(p), n, None, n, ops._ptr(q), length, None, length, d, ops._ptr(w), st), "gram_f32")
+    nb = lib.srgan_jacobi_workspace(n)
+    ws = torch.empty(-(-nb // 8), dtype=torch.float64, device=x.device)
+    count = torch.empty(1, dtype=torch.int32, device=x.device)
+    sweeps = 0
+    while True:
+        if sweeps == int(max_sweeps):
+            raise RuntimeError(f"compute_frechet_distance: the Jacobi sweeps still rotated after max_sweeps = {max_sweeps}")
+        _lib.check(lib.srgan_jacobi_sweep(ops._ptr(w), n, length, ops._ptr(count), ops._ptr(ws), nb, st), "jacobi_sweep")
+        sweeps += 1
+        if int(count.item()) == 0:
+            break
+    nuc = torch.empty(1, dtype=torch.float64, device=x.device)
+    _lib.check(lib.srgan_nuclear_from_rows(ops._ptr(w), n, length, ops._ptr(nuc), ops._ptr(ws), nb, st), "nuclear_from_rows")
+    diff = mu1.cpu().numpy().astype(np.float64) - mu2.cpu().numpy().astype(np.float64)
+    mean_term = float(np.dot(diff, diff))
+    tr1, tr2, nuclear = float(t1.item()), float(t2.item()), float(nuc.item())
+    fd = mean_term + tr1 + tr2 - 2.0 * nuclear
+    if return_terms:
+        return dict(fd=fd, mean_term=mean_term, trace_real=tr1, trace_fake=tr2, nuclear=nuclear, sweeps=sweeps)
+    return fd
+
+
+def kid_subsets(n_real, n_fake, num_subsets, max_subset_size, seed):
+    """The subset tables of ``compute_kid``: two int32 arrays [num_subsets, m], m = min(n_real, n_fake, max_subset_size); row s
+    is ``np.random.default_rng([seed, s, which]).choice(n, m, replace=False)`` (which = 0 real, 1 fake)."""
+    n_real, n_fake, num_subsets, max_subset_size = int(n_real), int(n_fake), int(num_subsets), int(max_subset_size)
+    if num_subsets < 1:
+        raise ValueError("kid_subsets: num_subsets must be at least 1")
+    m = min(n_real, n_fake, max_subset_size)
+    if m < 1:
+        raise ValueError("kid_subsets: an empty set or max_subset_size < 1")
+    tabs = []
+    for which, n in enumerate((n_real, n_fake)):
+        tabs.append(np.stack([np.random.default_rng([int(seed), s, which]).choice(n, m, replace=False)
+                              for s in range(num_subsets)]).astype(np.int32))
+    return tabs[0], tabs[1]
+
+
+def compute_kid(real_features, fake_features, num_subsets=100, max_subset_size=1000, seed=0, device="cuda"):
+    """Kernel Inception Distance in StyleGAN2-ADA's ``kernel_inception_distance`` estimator with k(x, y) = (x . y / D + 1)^3:
+    ``(1 / S) sum_s [(Sxx_s + Syy_s) / (m (m - 1)) - 2 Sxy_s / m^2]`` over S = ``num_subsets`` subsets of m rows
+    (``kid_subsets``), Sxx / Syy the off-diagonal sums, Sxy the full sum.  Unbiased: it may be negative.  A Python float."""
+    n1, n2, d = _feature_pair(real_features, fake_features, "compute_kid")
+    if not 1 <= int(num_subsets) <= 65535:
+        raise ValueError(f"compute_kid: num_subsets = {num_subsets} outside 1..65535")
+    m = min(n1, n2, int(max_subset_size))
+    if m < 2:
+        raise ValueError(f"compute_kid: subset size min(n_real, n_fake, max_subset_size) = {m}, the estimator needs at least 2")
+    ix, iy = kid_subsets(n1, n2, num_subsets, max_subset_size, seed)
+    lib = _lib.load()
+    x, y = _dev_f32(real_features, device), _dev_f32(fake_features, device)
+    st = ops._stream()
+    s = int(num_subsets)
+    dx, dy = torch.as_tensor(ix).to(x.device), torch.as_tensor(iy).to(x.device)
+    sums = torch.empty(s, 3, dtype=torch.float64, device=x.device)
+    kid = torch.empty(1, dtype=torch.float64, device=x.device)
+    nb = lib.srgan_kid_workspace(s, m)
+    ws = torch.empty(nb // 8, dtype=torch.float64, device=x.device)
+    _lib.check(lib.srgan_kid_poly3(ops._ptr(x), n1, ops._ptr(y), n2, d, ops._ptr(dx), ops._ptr(dy), s, m, ops._ptr(sums),
+                                   ops._ptr(kid), ops._ptr(ws), nb, st), "kid_poly3")
+    return float(kid.item())
+
+
 class GAN_evaluation():
     """evaluation.py:38-110.  ``feature_extractor``: "vgg-initialization" (default-initialised VGG19-bn, as the reference's
     ``models.vgg19_bn(pretrained=False)`` + the no-op ``weights_init``), or "vgg-ImageNet" / "vgg-CelebA" with ``weights=`` a
@@ -250,6 +370,40 @@ class GAN_evaluation():
         if f1.shape[1] == 0:
             return {"precision": None, "recall": None, "density": None, "coverage": None}
         return compute_prdc(real_features=f1, fake_features=f2, nearest_k=nearest_k, device=self.device)
+
+    def _features_of(self, true, pred, preprocess):
+        """Each set through the extractor once."""
+        self.run_preprocess = preprocess
+        if preprocess:
+            true = self.preprocess(true)
+            pred = self.preprocess(pred)
+        return self.get_feature(true), self.get_feature(pred)
+
+    def get_fd(self, true, pred, preprocess=True):
+        """Frechet distance of the two sets' features (``compute_frechet_distance``); not an Inception-v3 FID."""
+        f1, f2 = self._features_of(true, pred, preprocess)
+        return compute_frechet_distance(f1, f2, device=self.device)
+
+    def get_kid(self, true, pred, num_subsets=100, max_subset_size=1000, seed=0, preprocess=True):
+        f1, f2 = self._features_of(true, pred, preprocess)
+        return compute_kid(f1, f2, num_subsets=num_subsets, max_subset_size=max_subset_size, seed=seed, device=self.device)
+
+    def get_metrics(self, true, pred, metrics=("prdc", "fd", "kid"), nearest_k=5, num_subsets=100, max_subset_size=1000, seed=0,
+                    preprocess=True):
+        """The chosen metrics from ONE extraction of each set, as one flat dict: precision / recall / density / coverage
+        ("prdc"), ``fd``, ``kid``."""
+        unknown = [m for m in metrics if m not in ("prdc", "fd", "kid")]
+        if unknown:
+            raise ValueError(f"get_metrics: unknown metrics {unknown} (prdc, fd, kid)")
+        f1, f2 = self._features_of(true, pred, preprocess)
+        out = {}
+        if "prdc" in metrics:
+            out.update(compute_prdc(real_features=f1, fake_features=f2, nearest_k=nearest_k, device=self.device))
+        if "fd" in metrics:
+            out["fd"] = compute_frechet_distance(f1, f2, device=self.device)
+        if "kid" in metrics:
+            out["kid"] = compute_kid(f1, f2, num_subsets=num_subsets, max_subset_size=max_subset_size, seed=seed, device=self.device)
+        return out
 
 
 def evaluation_init(fe_list, classes, metrics):
