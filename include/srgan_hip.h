@@ -700,6 +700,40 @@ int srgan_d_losses_cr(const float* const* o, const long long* per_row, const flo
                       int n_class, const long long* label, float t_first, float t_rest, float w_class, int gan_kind, int class_kind,
                       float* vals, float* const* d_o, float* const* dz, int pairs, int pairs_first, void* state, void* stream);
 
+/* Mode-seeking (diversity) regularisation of the generator: restates lossModeSeeking of MSGAN (Mao et al., CVPR 2019:
+ * 1 / (mean|I1 - I2| / mean|z1 - z2| + eps)) and the per-sample clamped term of DSGAN (Yang et al., ICLR 2019:
+ * -mean_i min(mean|I1_i - I2_i| / mean|z1_i - z2_i|, tau)).  Extension, no counterpart in the reference.
+ * i1, i2: fp32 [b, e], dense rows of e = C H W floats, 4-byte aligned (16-byte loads are used per row where both row bases allow
+ * them, with the same bits either way); z1, z2: fp32 [b, d], dense.  s_i = sum |i1_i - i2_i|, t_i = sum |z1_i - z2_i|.
+ * Record (srgan_ms_state_bytes() = 32 bytes, device memory): {float weight, float eps, float tau, float ms, float weighted,
+ * float d_image, float d_latent, int updates}.  srgan_ms_state_init writes the three settings and zeroes the rest; srgan_ms_state_set
+ * rewrites the settings between steps and keeps the rest (a recorded step reads them from the record); srgan_ms_state_restore writes
+ * updates, ms, d_image, d_latent (weighted = weight * ms) and nothing else (resuming from a checkpoint).  One one-thread launch each.
+ * -1 before any launch: a NULL record, weight < 0, eps <= 0, tau < 0, a value not finite, updates < 0.
+ * srgan_ms_workspace(b, e): bytes of the workspace of the two passes below (the partial sums, then 2 b doubles), 0 on bad geometry.
+ * srgan_ms_rows: ONE launch; ws[n * ceil(e / 4096) + c] = the fp32 sum of |i1 - i2| over floats [4096 c, 4096 c + 4096) of row n, in
+ * an order that depends on e only (csrc/diversity.hip).  Forward only.
+ * srgan_ms_finish: ONE launch, one workgroup, float64 throughout: s_i from the partials in ascending order, t_i over d ascending,
+ * dI = sum s_i / (b e), dz = sum t_i / (b d);
+ *   form 0 (msgan): ms = dz / (dI + eps dz), 0 when dz == 0; coef[i] = -weight dz / (dI + eps dz)^2 / (b e), 0 when dz == 0;
+ *   form 1 (dsgan): r_i = (s_i / e) / (t_i / d); ms = -(1 / b) sum_i (t_i == 0 or r_i > tau ? tau : r_i);
+ *                   coef[i] = -weight / b * (d / t_i) / e where t_i != 0 and r_i <= tau, else 0.
+ * vals[2] = {weight * ms, ms}; the record takes ms, weight * ms, dI, dz and updates += 1; weight, eps, tau are READ from the record.
+ * srgan_ms_grad: ONE launch; d1[i, p] = *g * coef[i] * sign(i1[i, p] - i2[i, p]), d2 = -d1, sign(0) = 0; g a device scalar; d1 or d2
+ * may be NULL (nothing is written for it), not both.  No atomics anywhere; every sum has a fixed order.
+ * -1 with srgan_last_error() before any launch: a NULL pointer, b, e or d <= 0, e >= 2^31 - 4096, an unknown form, a workspace too
+ * small or not 8-byte aligned, a pointer not 4-byte aligned, an output of srgan_ms_grad aliasing an input or the other output. */
+size_t srgan_ms_state_bytes(void);
+int srgan_ms_state_init(void* state, float weight, float eps, float tau, void* stream);
+int srgan_ms_state_set(void* state, float weight, float eps, float tau, void* stream);
+int srgan_ms_state_restore(void* state, int updates, float ms, float d_image, float d_latent, void* stream);
+size_t srgan_ms_workspace(int b, long long e);
+int srgan_ms_rows(const float* i1, const float* i2, int b, long long e, void* ws, size_t ws_bytes, void* stream);
+int srgan_ms_finish(const void* ws, size_t ws_bytes, const float* z1, const float* z2, int b, long long e, int d, int form,
+                    void* state, float* vals, float* coef, void* stream);
+int srgan_ms_grad(const float* i1, const float* i2, const float* coef, const float* g, float* d1, float* d2, int b, long long e,
+                  void* stream);
+
 /* Small host -> device upload (pointer tables: <= 1 MiB, multiple of 4 bytes) carried in kernel arguments: nothing to keep
  * alive on the host after the call returns, and a captured hipGraph stores the bytes in its node instead of re-reading a host
  * address at replay (no reference counterpart; plumbing of the multi-tensor ops above). */

@@ -51,8 +51,10 @@ static const char* const kProfNames[] = {
     // the fused norm + Winograd-transform kernels of the trunk (conv_wino43.hip), HBM-bound too: bytes in the "flops" slot
     "in_fwd_slab_v", "in_bwd_slab_vz",
     // balanced consistency regularisation (consistency.hip): launch counts and per-launch times only, nothing in the "flops" slot
-    "cr_pairs_kernel", "d_losses_cr_kernel"};
-constexpr int kProfKernels = 42;
+    "cr_pairs_kernel", "d_losses_cr_kernel",
+    // mode-seeking regularisation (diversity.hip): the bytes the pass must move in the "flops" slot of the two streaming passes
+    "ms_rows_kernel", "ms_finish_kernel", "ms_grad_kernel"};
+constexpr int kProfKernels = 45;
 
 struct ProfScope {
   bool on;

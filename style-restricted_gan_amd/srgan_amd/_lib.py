@@ -220,6 +220,15 @@ SIGNATURES = {
     "srgan_cr_state_set_updates": (c_int, [P, c_int, P]),
     "srgan_d_losses_cr": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, c_float, c_float, c_float, c_int, c_int, P, P, P, c_int, c_int,
                                   P, P]),
+    # mode-seeking regularisation of the generator (csrc/diversity.hip)
+    "srgan_ms_state_bytes": (c_size_t, []),
+    "srgan_ms_state_init": (c_int, [P, c_float, c_float, c_float, P]),
+    "srgan_ms_state_set": (c_int, [P, c_float, c_float, c_float, P]),
+    "srgan_ms_state_restore": (c_int, [P, c_int, c_float, c_float, c_float, P]),
+    "srgan_ms_workspace": (c_size_t, [c_int, c_longlong]),
+    "srgan_ms_rows": (c_int, [P, P, c_int, c_longlong, P, c_size_t, P]),
+    "srgan_ms_finish": (c_int, [P, c_size_t, P, P, c_int, c_longlong, c_int, c_int, P, P, P, P]),
+    "srgan_ms_grad": (c_int, [P, P, P, P, P, P, c_int, c_longlong, P]),
     "srgan_upload_small": (c_int, [P, P, c_size_t, P]),
     "srgan_maxpool2_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "srgan_pairwise_dist": (c_int, [P, c_int, P, c_int, c_int, P, P]),

@@ -12,10 +12,11 @@ dict`` -- a file written from it loads with ``torch.load(path, weights_only=True
     hist_target              the histogram-imitation target the constructor drew (``lbd["hist"] > 0``)
     ema, augment, geometry,  the step's extensions that are on: the averaged copies and their update count, DiffAugment's settings
     ada, r1, bcr,            and generator, the geometric stage's settings and generator, the adaptive probability's settings and
-    grad_guard               whole record (p, seen, the three counts, adjustments, last_r, the record's batch size n), R1's
+    mode_seeking, grad_guard whole record (p, seen, the three counts, adjustments, last_r, the record's batch size n), R1's
                              gamma / every / updates (and the record's batch size n), consistency regularisation's weights / every /
-                             policy / translation / generator / updates, per guarded net max_norm and the cumulative steps /
-                             skipped / clipped
+                             policy / translation / generator / updates, mode seeking's weight / form / eps / tau / generator /
+                             updates and last ms / d_image / d_latent, per guarded net max_norm and the cumulative steps / skipped /
+                             clipped
     rng                      the CPU default generator (style and reparametrisation noise) and numpy's global one (``get_target``)
 
 Not saved: the last step's images, ``loss_terms``, the label cache, workspaces, packed operands, the guard's decision and R1's
@@ -44,7 +45,7 @@ LoadReport.__doc__ = """Sections the trainer has but the checkpoint lacks (they 
 use for (skipped)."""
 
 _NETS = ("G", "D", "E")
-_EXTENSIONS = ("ema", "augment", "geometry", "ada", "r1", "bcr", "grad_guard")
+_EXTENSIONS = ("ema", "augment", "geometry", "ada", "r1", "bcr", "mode_seeking", "grad_guard")
 # the augmentation stages (srgan_amd.augment): (section, the trainer attribute the stage lives in, the switch that makes one, the keys
 # of a saved section the switch takes, in its order), in the order of application
 _STAGES = (("augment", "augment", "enable_diffaugment", ("policy", "translation", "cutout")),
@@ -139,7 +140,8 @@ class Checkpointing:
         out += [n for n in ("optG", "optD", "optE", "scheG", "scheD", "scheE") if getattr(self, n, None) is not None]
         if getattr(self, "hi", None) is not None:
             out.append("hist_target")
-        for name, attr in (("ema", "_ema"), *(s[:2] for s in _STAGES), ("ada", "_ada"), ("r1", "_r1"), ("bcr", "bcr")):
+        for name, attr in (("ema", "_ema"), *(s[:2] for s in _STAGES), ("ada", "_ada"), ("r1", "_r1"), ("bcr", "bcr"),
+                           ("mode_seeking", "_ms")):
             if getattr(self, attr, None) is not None:
                 out.append(name)
         out += [f"grad_guard.{n}" for n in self._ckpt_guards()]
@@ -166,7 +168,7 @@ class Checkpointing:
     # ---- save ---------------------------------------------------------------------------------------------------------------------
     def state_dict(self, rng=True):
         """A snapshot of everything the next ``train()`` depends on (module docstring): CPU clones and plain values.  Between steps
-        only; reads the adaptive-probability, R1, consistency and gradient-guard records, so it SYNCHRONISES the stream.  ``rng=False`` leaves the two host
+        only; reads the adaptive-probability, R1, consistency, mode-seeking and gradient-guard records, so it SYNCHRONISES the stream.  ``rng=False`` leaves the two host
         generators out.  Per process: no collective."""
         self._ckpt_between_steps("state_dict")
         sd = {"version": VERSION, "config": self._ckpt_config()}
@@ -192,6 +194,8 @@ class Checkpointing:
                         "n": None if st["n"] is None else int(st["n"])}
         if getattr(self, "bcr", None) is not None:
             sd["bcr"] = _plain(self.bcr.state_dict(), "bcr")
+        if getattr(self, "_ms", None) is not None:
+            sd["mode_seeking"] = _plain(self._ms.state_dict(), "mode_seeking")
         guards = self._ckpt_guards()
         if guards:
             sd["grad_guard"] = {}
@@ -248,7 +252,8 @@ class Checkpointing:
         fields BEFORE anything is written.  A recording of the step and the warm-up of its input shape are forgotten (torch's
         optimiser load replaces the moment tensors a recording points at): the next step runs eagerly, the one after records
         again; graph mode stays enabled.  Cached packed operands of every network and of the averaged copies are marked stale.
-        ``ema_updates``, ``grad_guard_stats()``, ``r1_stats()`` and ``bcr_stats()`` continue from the saved counts."""
+        ``ema_updates``, ``grad_guard_stats()``, ``r1_stats()``, ``bcr_stats()`` and ``mode_seeking_stats()`` continue from the saved
+        counts."""
         self._ckpt_between_steps("load_state_dict")
         who = type(self).__name__
         if not isinstance(sd, dict) or "version" not in sd:
@@ -325,6 +330,11 @@ class Checkpointing:
             if self.bcr is None or self.bcr.every != int(c["every"]):
                 self.enable_bcr(c["lambda_real"], c["lambda_fake"], int(c["every"]), c["policy"], c["translation"])
             self.bcr.load_state_dict(c, next(dp.unwrap(self.D).parameters()).device)
+        if use("mode_seeking"):
+            m = sd["mode_seeking"]
+            if self._ms is None or self._ms.form != m["form"]:
+                self.enable_mode_seeking(m["weight"], m["form"], m["eps"], m["tau"])
+            self._ms.load_state_dict(m, next(dp.unwrap(self.G).parameters()).device)
         for n, g in (sd.get("grad_guard") or {}).items():
             if f"grad_guard.{n}" in unexpected:
                 continue

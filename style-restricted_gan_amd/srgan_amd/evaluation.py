@@ -17,6 +17,7 @@ given), ``compute_kid`` / ``kid_subsets`` (Kernel Inception Distance, StyleGAN2-
 comparable with published Inception-v3 FIDs; it ranks runs of this project against each other.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -28,7 +29,7 @@ from .losses import weights_init
 from .ops import ACT_NONE, ACT_RELU, PAD_ZERO
 
 __all__ = ["VGG19_bn", "vgg19_bn", "vgg_model", "GAN_evaluation", "evaluation_init", "compute_prdc", "maxpool2",
-           "compute_frechet_distance", "compute_kid", "kid_subsets", "FD_MAX_SIDE"]
+           "compute_frechet_distance", "compute_kid", "kid_subsets", "FD_MAX_SIDE", "compute_style_diversity"]
 
 VGG19_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512, "M"]
 
@@ -311,6 +312,24 @@ def compute_kid(real_features, fake_features, num_subsets=100, max_subset_size=1
     return float(kid.item())
 
 
+def compute_style_diversity(images):
+    """Pixel-space style diversity of translations: ``images[S, N, ...]`` on the device, S styles of each of N sources -> the mean,
+    over the N sources and the S (S - 1) / 2 style pairs, of ``mean |a - b|`` (``ops.rowwise_l1``: one launch per style pair over
+    the N rows; the mean over the N S (S - 1) / 2 float64 row values is their exactly rounded sum, ``math.fsum``, over their number).  The number mode-seeking regularisation
+    (``srgan_amd.diversity``) is meant to raise.  A Python float."""
+    if not torch.is_tensor(images) or images.dim() < 3:
+        raise ValueError("compute_style_diversity: a tensor [S, N, ...] expected (S styles of N sources)")
+    s, n = int(images.shape[0]), int(images.shape[1])
+    if s < 2:
+        raise ValueError(f"compute_style_diversity: S = {s} styles; a pair needs at least 2")
+    if n < 1:
+        raise ValueError("compute_style_diversity: no sources")
+    flat = images.to(torch.float32).reshape(s, n, -1).contiguous()
+    rows = [ops.rowwise_l1(flat[i], flat[j]) for i in range(s) for j in range(i + 1, s)]
+    values = torch.cat(rows).to(torch.float64).cpu().tolist()
+    return math.fsum(values) / len(values)
+
+
 class GAN_evaluation():
     """evaluation.py:38-110.  ``feature_extractor``: "vgg-initialization" (default-initialised VGG19-bn, as the reference's
     ``models.vgg19_bn(pretrained=False)`` + the no-op ``weights_init``), or "vgg-ImageNet" / "vgg-CelebA" with ``weights=`` a
@@ -388,13 +407,19 @@ class GAN_evaluation():
         f1, f2 = self._features_of(true, pred, preprocess)
         return compute_kid(f1, f2, num_subsets=num_subsets, max_subset_size=max_subset_size, seed=seed, device=self.device)
 
+    def get_diversity(self, images):
+        """Pixel-space style diversity of ``images[S, N, ...]`` (``compute_style_diversity``): no feature extraction."""
+        return compute_style_diversity(torch.as_tensor(images).to(self.device))
+
     def get_metrics(self, true, pred, metrics=("prdc", "fd", "kid"), nearest_k=5, num_subsets=100, max_subset_size=1000, seed=0,
-                    preprocess=True):
+                    preprocess=True, styles=None):
         """The chosen metrics from ONE extraction of each set, as one flat dict: precision / recall / density / coverage
-        ("prdc"), ``fd``, ``kid``."""
-        unknown = [m for m in metrics if m not in ("prdc", "fd", "kid")]
+        ("prdc"), ``fd``, ``kid``; ``diversity`` only when asked for, from ``styles[S, N, ...]`` (``get_diversity``)."""
+        unknown = [m for m in metrics if m not in ("prdc", "fd", "kid", "diversity")]
         if unknown:
-            raise ValueError(f"get_metrics: unknown metrics {unknown} (prdc, fd, kid)")
+            raise ValueError(f"get_metrics: unknown metrics {unknown} (prdc, fd, kid, diversity)")
+        if "diversity" in metrics and styles is None:
+            raise ValueError("get_metrics: 'diversity' needs styles=[S, N, ...], S translations of each of N sources")
         f1, f2 = self._features_of(true, pred, preprocess)
         out = {}
         if "prdc" in metrics:
@@ -403,6 +428,8 @@ class GAN_evaluation():
             out["fd"] = compute_frechet_distance(f1, f2, device=self.device)
         if "kid" in metrics:
             out["kid"] = compute_kid(f1, f2, num_subsets=num_subsets, max_subset_size=max_subset_size, seed=seed, device=self.device)
+        if "diversity" in metrics:
+            out["diversity"] = self.get_diversity(styles)
         return out
 
 

@@ -2933,3 +2933,122 @@ def d_losses_cr(outs, logits, label, rows_first, t_first, t_rest, w_class, state
     return _DLossesCrFn.apply(label, rows_first, t_first, t_rest, w_class, len(outs), _crit_kind(gan_kind, "d_losses_cr"),
                               _crit_kind(class_kind, "d_losses_cr"), state, rows_first if pairs_first is None else pairs_first,
                               *outs, *logits)
+
+
+# ---- mode-seeking regularisation of the generator (srgan_amd.diversity; extension, no counterpart in the reference) ----
+MS_FORMS = {"msgan": 0, "dsgan": 1}
+MS_CHUNK = 4096                # kMsChunk of csrc/diversity.hip: floats of one row per partial sum
+
+
+def ms_state_new(device, weight, eps, tau):
+    """Device-resident record {weight, eps, tau, ms, weighted, d_image, d_latent, updates}, the last five at zero."""
+    lib = _lib.load()
+    st = torch.empty(lib.srgan_ms_state_bytes(), dtype=torch.uint8, device=device)
+    _lib.check(lib.srgan_ms_state_init(_ptr(st), float(weight), float(eps), float(tau), _stream()), "ms_state_init")
+    return st
+
+
+def ms_state_set(state, weight, eps, tau):
+    """Rewrite the settings between steps; the values and the counter stay (a recorded step reads the record)."""
+    _lib.check(_lib.load().srgan_ms_state_set(_ptr(state), float(weight), float(eps), float(tau), _stream()), "ms_state_set")
+
+
+def ms_state_restore(state, updates, ms, d_image, d_latent):
+    """Write a checkpoint's counter and last values between steps; the settings stay."""
+    _lib.check(_lib.load().srgan_ms_state_restore(_ptr(state), int(updates), float(ms), float(d_image), float(d_latent), _stream()),
+               "ms_state_restore")
+
+
+def ms_state_read(state):
+    """The record as a dict; synchronises the current stream."""
+    torch.cuda.current_stream(state.device).synchronize()
+    w, eps, tau, ms, wd, di, dz, updates = struct.unpack("fffffffi", state.cpu().numpy().tobytes()[:32])
+    return dict(weight=w, eps=eps, tau=tau, ms=ms, weighted=wd, d_image=di, d_latent=dz, updates=updates)
+
+
+def _ms_rows_of(t, what):
+    """An operand of the mode-seeking kernels as dense rows: NHWC-dense 4-d (a row slice of a larger batch included) or contiguous."""
+    _require_gpu(t, what)
+    if t.dim() < 2:
+        raise _lib.SrganHipError(f"{what}: a tensor of shape {tuple(t.shape)}; [B, ...] expected")
+    if t.dim() == 4:
+        return to_nhwc(t)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _ms_pair(a, b, what):
+    a, b = _ms_rows_of(a, what), _ms_rows_of(b, what)
+    if a.shape != b.shape or a.device != b.device:
+        raise _lib.SrganHipError(f"{what}: operands of shape {tuple(a.shape)} and {tuple(b.shape)}")
+    rows = a.shape[0]
+    return a, b, rows, a.numel() // rows
+
+
+def _ms_partials(a, b, rows, e, what):
+    lib = _lib.load()
+    nb = lib.srgan_ms_workspace(rows, e)
+    if nb == 0:
+        raise _lib.SrganHipError(f"{what}: {rows} rows of {e} floats (both > 0, a row under 2^31 - 4096 floats)")
+    ws = workspace(a.device, nb)
+    _lib.check(lib.srgan_ms_rows(_ptr(a), _ptr(b), rows, e, _ptr(ws), nb, _stream()), "ms_rows")
+    return ws, nb
+
+
+class _ModeSeekingFn(Function):
+    @staticmethod
+    def forward(ctx, i1, i2, z1, z2, state, form):
+        a, b, rows, e = _ms_pair(i1, i2, "mode_seeking")
+        _require_gpu(z1, "mode_seeking")
+        _require_gpu(z2, "mode_seeking")
+        z1, z2 = _dense2d(z1), _dense2d(z2)
+        if z1.dim() != 2 or z1.shape != z2.shape or z1.shape[0] != rows:
+            raise _lib.SrganHipError(f"mode_seeking: latents of shape {tuple(z1.shape)} and {tuple(z2.shape)} for {rows} images")
+        ws, nb = _ms_partials(a, b, rows, e, "mode_seeking")
+        vals = torch.empty(2, dtype=torch.float32, device=a.device)
+        coef = torch.empty(rows, dtype=torch.float32, device=a.device)
+        _lib.check(_lib.load().srgan_ms_finish(_ptr(ws), nb, _ptr(z1), _ptr(z2), rows, e, z1.shape[1], form, _ptr(state), _ptr(vals),
+                                               _ptr(coef), _stream()), "ms_finish")
+        ctx.save_for_backward(a, b, coef)
+        ctx.geom = (rows, e)
+        weighted, unweighted = vals[0], vals[1]
+        ctx.mark_non_differentiable(unweighted)
+        return weighted, unweighted
+
+    @staticmethod
+    def backward(ctx, g, _gu):
+        a, b, coef = ctx.saved_tensors
+        rows, e = ctx.geom
+        need1, need2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        d1 = torch.empty_like(a) if need1 else None
+        d2 = torch.empty_like(b) if need2 else None
+        if need1 or need2:
+            g = g.to(torch.float32).contiguous()
+            _lib.check(_lib.load().srgan_ms_grad(_ptr(a), _ptr(b), _ptr(coef), _ptr(g), _ptr(d1), _ptr(d2), rows, e, _stream()),
+                       "ms_grad")
+        return d1, d2, None, None, None, None
+
+
+def mode_seeking(i1, i2, z1, z2, record, form="msgan"):
+    """The mode-seeking term of two translations ``i1``, ``i2`` [B, C, H, W] of the same sources under the latent codes ``z1``,
+    ``z2`` [B, d]: ``form="msgan"``: ``dz / (dI + eps dz)`` with ``dI``, ``dz`` the batch means of ``|i1 - i2|`` and ``|z1 - z2|``
+    (MSGAN's ``1 / (dI / dz + eps)``); ``form="dsgan"``: ``-mean_i min(r_i, tau)``, ``r_i`` the per-row ratio of the two means.
+    ``weight``, ``eps`` and ``tau`` are read from the device ``record`` (``ms_state_new``), which takes the values and counts the
+    call.  -> (weight * ms, ms) as device scalars: the first is differentiable in ``i1`` and ``i2`` independently (either may not
+    require a gradient: nothing is computed for it), the second carries no gradient; none goes to the latents.  Two launches
+    forward, one backward; no atomics, a fixed order of every sum.  hipGraph-capturable."""
+    if form not in MS_FORMS:
+        raise _lib.SrganHipError(f"mode_seeking: form = {form!r} (one of {sorted(MS_FORMS)})")
+    return _ModeSeekingFn.apply(i1, i2, z1.detach(), z2.detach(), record, MS_FORMS[form])
+
+
+def rowwise_l1(a, b):
+    """Per-row ``mean |a - b|`` of two batches of the same shape -> float64 ``[B]``, on the reduction pass of the mode-seeking
+    kernels (one launch; a row's float32 partial sums of 4096 terms are then added and divided in float64, so a row whose sums are
+    exact gives the exact mean).  No gradient."""
+    with torch.no_grad():
+        a, b, rows, e = _ms_pair(a.detach(), b.detach(), "rowwise_l1")
+        ws, _ = _ms_partials(a, b, rows, e, "rowwise_l1")
+        nchunk = -(-e // MS_CHUNK)
+        part = ws[:rows * nchunk * 4].view(torch.float32).view(rows, nchunk)
+        # (a tensor divisor: dividing by a Python scalar multiplies by its rounded reciprocal on the device)
+        return part.to(torch.float64).sum(1) / torch.full((), float(e), dtype=torch.float64, device=a.device)

@@ -5,7 +5,7 @@
 feature: a feature joins ``_fingerprint()`` and the keep-alive list by being in ``sg._extensions()``, the host-side counters a
 recording advances are those of ``sg._mirrors()``, and the augmentation stages whose host-drawn tables are staged beside the noise
 (one ``_Staged`` per stage, keyed by its ``section``) are those of ``sg._drawing_stages()``: the stages applied to everything D reads
-and any other stage whose tables the step consumes.
+and any other object whose host draws the step consumes (the consistency pairs' tables, mode seeking's second latent code).
 """
 import gc
 import os

@@ -34,6 +34,7 @@ from . import dp, ema, ops, spectral
 from . import ada as _adamod
 from .augment import DiffAugment, GeometricAugment
 from . import consistency as _crmod
+from . import diversity as _msmod
 from .checkpoint import Checkpointing
 from . import r1 as _r1mod
 from .losses import class_encode, criterion_kind, get_domainloss_D, get_loss_D, has_fused_kind, histogram_imitation
@@ -104,6 +105,7 @@ class SRGAN_training(Checkpointing):
         self._ada = None               # adaptive augmentation probability on the device (enable_ada)
         self._r1 = None                # R1 gradient penalty on the real rows (enable_r1)
         self.bcr = None                # balanced consistency regularisation of D (enable_bcr)
+        self._ms = None                # mode-seeking regularisation of G (enable_mode_seeking)
         self._label_cache = {}         # (kind, which) -> (label tensor, its device form): _cached
         self._d_pending = None         # an update_D left its all-reduce / optimiser step to _finish_D: the reducer, or True
         self._sn_cache = (None, None)  # (key, spectral controller or None): _sn
@@ -180,8 +182,10 @@ class SRGAN_training(Checkpointing):
 
     def _drawing_stages(self):
         """Every stage whose host-drawn tables a step consumes: those of ``_stages()``, then the consistency pairs' (which is not
-        applied to everything D reads: its tables go to the penalised discriminator updates alone)."""
-        return self._stages() + ([self.bcr.stage] if self.bcr is not None else [])
+        applied to everything D reads: its tables go to the penalised discriminator updates alone), then mode seeking's object,
+        whose one "table" per step is the second latent code [B, ndim] of phase 1 (staged under its ``section``)."""
+        return (self._stages() + ([self.bcr.stage] if self.bcr is not None else [])
+                + ([self._ms] if self._ms is not None else []))            # (mode seeking: the second latent code, one draw per step)
 
     def _gated(self, stage):
         """Does the adaptive probability gate this stage's groups?  Those applied to everything D reads; never the consistency
@@ -190,14 +194,18 @@ class SRGAN_training(Checkpointing):
 
     def _stage_draws(self, stage):
         """tables of a stage a step consumes: 2 per discriminator update, 1 for phase 1; the consistency pairs: 2 per PENALISED
-        discriminator update (real rows, then fake rows), none for phase 1, also with an empty policy"""
+        discriminator update (real rows, then fake rows), none for phase 1, also with an empty policy; mode seeking: 1"""
         if self.bcr is not None and stage is self.bcr.stage:
             return 2 * sum(_crmod.schedule(self.k, self.bcr.every))
+        if stage is self._ms and stage is not None:
+            return 1                            # mode seeking: the second latent code of phase 1
         return 2 * self.k + 1 if self._stage_on(stage) else 0
 
     def _stage_row_draw(self, stage, nb, h, w):
         """One host draw of the step: the CPU table [nb, 8] of the stage's ``draw_fn``; with adaptive augmentation on, followed by
         one uniform per group and sample of its ``gate_fn`` and joined into the [nb, 16] rows ``ops.ada_gate`` reads."""
+        if stage is self._ms:
+            return stage.draw_fn(nb, self.ndim).to(torch.float32)      # mode seeking: [nb, ndim] standard normals, its own generator
         table = stage.draw_fn(nb, h, w).to(torch.float32)
         if not self._gated(stage):
             return table
@@ -245,7 +253,7 @@ class SRGAN_training(Checkpointing):
         return (self.optG, self.optD, self.optE)
 
     def _extensions(self):
-        return [x for x in (self._ema, self._sn(), *self._stages(), self._ada, self._r1, self.bcr) if x is not None]
+        return [x for x in (self._ema, self._sn(), *self._stages(), self._ada, self._r1, self.bcr, self._ms) if x is not None]
 
     def _mirrors(self):
         """who mirrors, on the host, a device-side count that the step advances: Adam's step counts, the EMA's update count"""
@@ -537,6 +545,14 @@ class SRGAN_training(Checkpointing):
             # engine's input buffer would hold).
             cut = pair and dp.recording() and self.target_image.requires_grad
             t_img = self.target_image.detach().requires_grad_(True) if cut else self.target_image
+            ms = self._ms
+            i2 = z2 = None
+            if ms is not None:
+                # mode seeking: the second translation of the source, by the G that made target_image (no optimiser step has run
+                # since), under a second latent code from the feature's own generator
+                self._ms_check()
+                z2 = self._stage_tables(ms, 1, src.shape[0], src.shape[2], src.shape[3])
+                c2 = torch.cat([self._onehot("target"), z2], 1)
             if pair:
                 # the reference calls E(source) a second time for the identity path: same weights, same input -> same
                 # mu; only the reparametrisation noise is drawn again (keeps the CPU RNG sequence identical).  The
@@ -545,11 +561,19 @@ class SRGAN_training(Checkpointing):
                 pick = 0 if self.encoded_feature == "latent" else 1
                 oh = self._onehot("source")
                 c_pair = torch.cat([torch.cat([oh, source_enc_info[pick]], 1), torch.cat([oh, idt_info[pick]], 1)], 0)
-                both = self.G(ops.cat_batch([t_img, src]), c_pair)
                 nb = src.shape[0]
-                recon_image, identity_image = both[:nb], both[nb:]
+                if ms is not None and self._ms_rides(nb, src):
+                    # ... and the second translation as a third group of rows: per-sample network, so exact, and no convolution
+                    # launch more than the step without the feature
+                    both = self.G(ops.cat_batch([t_img, src, src]), torch.cat([c_pair, c2], 0))
+                    i2 = both[2 * nb:]
+                else:
+                    both = self.G(ops.cat_batch([t_img, src]), c_pair)
+                recon_image, identity_image = both[:nb], both[nb:2 * nb]
             else:
                 recon_image, _ = self.G_transformation("source", self.target_image, True, src, _enc_info=source_enc_info)
+            if ms is not None and i2 is None:
+                i2 = self.G(src, c2)                       # a forward of its own: no batched pass, or 3B rows would cross 4 GiB
             self._finish_D()                               # (data parallel: the last D update's all-reduce ran under the passes above)
             fused = self._fused_paths()
             # loss terms as (device scalar, weight) lists: the optimised sums and the two reported sums are each ONE launch
@@ -604,7 +628,14 @@ class SRGAN_training(Checkpointing):
                 rep_terms.append((total, 1.0))
                 terms.update(errE_bKL=parts[0], errE_corr=parts[1], errE_hist=parts[2])
 
-            total_p1 = ops.lincomb(g_terms + e_terms)
+            ms_terms = []
+            if ms is not None:
+                # weight * ms from the device record, optimised with weight 1; its gradient reaches G through i2's graph and
+                # through the kept target_image graph, never E or D.  errG stays the reference's sum without it.
+                ms_weighted, ms_value = ms.loss(t_img, i2, self.c_rand, z2)
+                ms_terms.append((ms_weighted, 1.0))
+                terms["errG_ms"] = ms_value
+            total_p1 = ops.lincomb(g_terms + ms_terms + e_terms)
             with torch.no_grad():
                 errG = ops.lincomb(g_terms)
                 errE_output = ops.lincomb(rep_terms)
@@ -1057,6 +1088,67 @@ class SRGAN_training(Checkpointing):
         return self.bcr.stats() if self.bcr is not None else None
 
     # ------------------------------------------------------------------------------------------
+    # mode-seeking regularisation of G (extension, no counterpart in the reference; srgan_amd.diversity)
+    def _ms_check(self):
+        if dp.world_size() > 1:
+            raise NotImplementedError(f"SRGAN_training: mode seeking is on and the process group has {dp.world_size()} ranks; the "
+                                      "msgan ratio is a statistic of the global batch and no reduced form exists (run one process, "
+                                      "or disable_mode_seeking())")
+        if not self._g_per_sample:
+            raise NotImplementedError("SRGAN_training: mode seeking is on and the generator normalises with batch statistics; the "
+                                      "second translation would advance its running buffers once more per step (build G with "
+                                      "per-sample norms, or disable_mode_seeking())")
+
+    def _ms_rides(self, nb, src):
+        """May the second translation ride phase 1's batched forward as rows [2B, 3B)?  The kernels address an activation with
+        32-bit byte offsets: the widest one of 3B images must stay under the limit ``UnrolledUpdate`` keeps for its groups."""
+        Gm = dp.unwrap(self.G)
+        if not isinstance(Gm, SingleGenerator):
+            return False
+        widest = max(int(Gm.down_convs[0].weight.shape[0]), 3) * src.shape[2] * src.shape[3] * 4
+        return 3 * nb * widest <= (1 << 32) - (1 << 26)
+
+    def enable_mode_seeking(self, weight=1.0, form="msgan", eps=1e-5, tau=None, seed=None):
+        """Mode-seeking regularisation of the generator (Mao et al., 2019; per-sample clamped form: Yang et al., 2019): from now on
+        phase 1 of ``update_GandE`` translates the source a second time, ``I2 = G(src, [onehot(target) | z2])`` with ``z2 ~ N(0, I)``
+        drawn once per step from the feature's OWN generator (``seed``; the default generator and the step's noise order are what
+        they are without it), and back-propagates ``weight * ms`` on top of the phase's loss: ``form="msgan"``: ``ms = dz / (dI +
+        eps dz)``, ``dI`` / ``dz`` the batch means of ``|target_image - I2|`` and ``|z1 - z2|``; ``form="dsgan"``: ``ms = -mean_i
+        min(r_i, tau)`` with the per-sample ratio ``r_i`` (``tau`` has no default).  The gradient reaches G through ``I2`` and
+        through the kept ``target_image`` graph, never E or D.  ``I2`` rides phase 1's batched generator forward as a third group of
+        rows (no convolution launch more), or takes a forward of its own where that batch is not formed or would cross the 4 GiB
+        activation limit; three launches of ``csrc/diversity.hip`` per step.  The returned ``errG`` is unchanged;
+        ``loss_terms["errG_ms"]`` is the unweighted term.  Captured with the step in graph mode (``z2`` staged beside the stages'
+        tables; a recording made before is dropped); the weight is device state (``set_mode_seeking_weight``).  Off: no draw, no
+        launch, no allocation, the step is bit-identical to the plain one.  Refused: more than one rank, a generator with
+        batch-statistics norms."""
+        state = _msmod.ModeSeeking(weight, form, eps, tau, seed)
+        prev, self._ms = self._ms, state
+        try:
+            self._ms_check()
+        except NotImplementedError:
+            self._ms = prev
+            raise
+        self._guard_changed()
+        return self
+
+    def disable_mode_seeking(self):
+        self._ms = None
+        self._guard_changed()
+
+    def set_mode_seeking_weight(self, weight):
+        """Write a new weight into the regulariser's device record, between steps; a recorded step reads it from there and stays
+        valid."""
+        if self._ms is None:
+            raise RuntimeError("set_mode_seeking_weight: mode seeking is off (enable_mode_seeking)")
+        self._ms.set_weight(weight)
+
+    def mode_seeking_stats(self):
+        """``weight``, ``form``, ``eps``, ``tau`` and the device record's ``ms``, ``d_image``, ``d_latent``, ``updates`` as a dict, or
+        None with the feature off.  SYNCHRONISES the stream."""
+        return self._ms.stats() if self._ms is not None else None
+
+    # ------------------------------------------------------------------------------------------
     # device-side gradient guard (extension, no counterpart in the reference; srgan_amd.optim.Adam.enable_grad_guard)
     _GUARD_NETS = ("G", "D", "E")
 
@@ -1221,6 +1313,10 @@ class SingleGAN_training(Checkpointing):
         raise NotImplementedError("SingleGAN_training: consistency regularisation is not wired into this trainer's discriminator "
                                   "passes (per-domain sub-batches); use SRGAN_training.enable_bcr, or consistency.BalancedCR in a "
                                   "loop of your own")
+
+    def enable_mode_seeking(self, *args, **kwargs):
+        raise NotImplementedError("SingleGAN_training: mode seeking is not wired into this trainer's generator update (per-domain "
+                                  "sub-batches); use SRGAN_training.enable_mode_seeking, or diversity.ModeSeeking in a loop of your own")
 
     def opt_sche_initialization(self, lr=[0.0001, 0.0001, 0.0001]):
         lr_G, lr_D, lr_E = lr
