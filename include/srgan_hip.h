@@ -507,7 +507,7 @@ int srgan_ema_multi_dev(const void* table, int n_records, long long total_chunks
  * No atomics: the result does not depend on the grid.  srgan_adam_multi_dev_guard = srgan_adam_multi_dev behind the record: the
  * tick runs as always (t += 1 even for a skipped step), the update stores nothing when skip is set and otherwise runs the same
  * arithmetic on g * scale (one fp32 multiply; the gradients are not written; scale = 1 leaves every result bit-identical).
- * srgan_grad_guard_state_set_counters (extension, no counterpart in the reference; resuming from a checkpoint): one one-thread
+ * srgan_grad_guard_state_set_counters (extension, no counterpart in the reference; resuming from a checkpoint): one
  * launch that writes the three cumulative counters between steps and nothing else -- max_norm keeps its own setter, norm / scale /
  * skip stay those of the last step; a negative count is refused (-1 with srgan_last_error(), no launch). */
 size_t srgan_grad_guard_state_bytes(void);
@@ -585,7 +585,7 @@ int srgan_diffaugment_bwd_gated(const float* gy, const float* table, float* gx, 
  *          24 int64 n_pos     32 int64 n_neg     40 int64 n_total   48 int adjustments 52 float last_r
  * srgan_ada_state_init writes p and the settings and zeroes the counters; srgan_ada_state_set rewrites target, step, p_max,
  * interval and (set_p != 0) p and keeps the counters; srgan_ada_state_set_counters writes seen, the three counts, adjustments and
- * last_r and nothing else (resuming from a checkpoint).  One one-thread launch each, stream-ordered.
+ * last_r and nothing else (resuming from a checkpoint).  One launch each, stream-ordered.
  * srgan_ada_gate: the one gate of every augmentation stage.  rows = n rows of 16 floats: slots 0..6 the stage's table row, slots
  * 8..8 + n_groups - 1 one uniform in [0, 1) per gated group, the other slots unread -- DiffAugment (n_groups = 3):
  * [b, s, a, ty, tx, cy, cx, -, u_colour, u_translation, u_cutout, ...]; the geometric stage below (n_groups = 4):
@@ -646,7 +646,7 @@ int srgan_geom_augment_bwd(const float* gy, const float* table, float* gx, int n
  * writes mean_sq_norm = S / n, penalty = gamma * every / 2 * S / n, updates += 1.  No atomics: a sample's u0 and partials depend
  * neither on n nor on its position.  -1 with srgan_last_error() before any launch: c != 3, a NULL pointer, n / h / w <= 0,
  * gamma < 0 or not finite, every < 1, a workspace too small, u0 aliasing h1 or h2.
- * srgan_r1_state_set_updates (extension, no counterpart in the reference; resuming from a checkpoint): one one-thread launch that
+ * srgan_r1_state_set_updates (extension, no counterpart in the reference; resuming from a checkpoint): one launch that
  * writes the count of penalised updates between steps and nothing else -- gamma, every, c and n keep srgan_r1_state_set, penalty and
  * mean_sq_norm stay those of the last finalize; a negative count is refused (-1 with srgan_last_error(), no launch). */
 size_t srgan_r1_state_bytes(void);
@@ -673,7 +673,7 @@ int srgan_r1_finalize(const void* ws, size_t ws_bytes, int n, int h, int w, void
  * Record (srgan_cr_state_bytes() = 32 bytes, device memory): {float lambda_real, float lambda_fake, int every, float cr_real,
  * float cr_fake, int updates, int pad[2]}.  srgan_cr_state_init writes the weights and every and zeroes the rest; srgan_cr_state_set
  * rewrites the weights and every between steps and keeps the counters (a recorded step reads the weights from the record);
- * srgan_cr_state_set_updates writes the count of penalised updates and nothing else (resuming from a checkpoint).  One one-thread
+ * srgan_cr_state_set_updates writes the count of penalised updates and nothing else (resuming from a checkpoint).  One
  * launch each.  -1 before any launch: a NULL record, a weight < 0 or not finite, every < 1, a negative count.
  * srgan_d_losses_cr: srgan_d_losses_crit on maps of rows = 2 * pairs rows whose row r + pairs is the consistency partner of row r.
  * ONE launch, one workgroup, no atomics, a fixed order.  The front `pairs` rows get everything srgan_d_losses_crit computes for a map of
@@ -708,8 +708,8 @@ int srgan_d_losses_cr(const float* const* o, const long long* per_row, const flo
  * Record (srgan_ms_state_bytes() = 32 bytes, device memory): {float weight, float eps, float tau, float ms, float weighted,
  * float d_image, float d_latent, int updates}.  srgan_ms_state_init writes the three settings and zeroes the rest; srgan_ms_state_set
  * rewrites the settings between steps and keeps the rest (a recorded step reads them from the record); srgan_ms_state_restore writes
- * updates, ms, d_image, d_latent (weighted = weight * ms) and nothing else (resuming from a checkpoint).  One one-thread launch each.
- * -1 before any launch: a NULL record, weight < 0, eps <= 0, tau < 0, a value not finite, updates < 0.
+ * updates, ms, d_image, d_latent and nothing else (resuming from a checkpoint; weighted waits for the next srgan_ms_finish).  One
+ * launch each.  -1 before any launch: a NULL record, weight < 0, eps <= 0, tau < 0, a value not finite, updates < 0.
  * srgan_ms_workspace(b, e): bytes of the workspace of the two passes below (the partial sums, then 2 b doubles), 0 on bad geometry.
  * srgan_ms_rows: ONE launch; ws[n * ceil(e / 4096) + c] = the fp32 sum of |i1 - i2| over floats [4096 c, 4096 c + 4096) of row n, in
  * an order that depends on e only (csrc/diversity.hip).  Forward only.

@@ -22,6 +22,7 @@
 //
 // Plain global stores, no atomics, fp contraction off.
 #include "common.h"
+#include "records.h"
 #include <cstdint>
 
 #pragma clang fp contract(off)
@@ -33,34 +34,10 @@ constexpr int kAdaRowIn = 16;       // floats per row the gate reads
 constexpr int kAdaRowOut = 8;       // floats per row it writes (the table row of augment.hip and augment_geom.hip)
 constexpr int kAdaMaxGroups = 4;    // uniforms per row it can read (slots 8..11)
 
-// p, seen, the three counts, adjustments and last_r are moved by ada_observe_kernel; the rest is written by the host between steps
-struct AdaState {
-  float p, target, step, p_max;
-  int interval, seen;
-  long long n_pos, n_neg, n_total;
-  int adjustments;
-  float last_r;
-};
-static_assert(sizeof(AdaState) == 56, "AdaState layout");
-
 struct AdaMaps {
   const float* map[kAdaMaxScales];
   long long count[kAdaMaxScales];   // elements of the first B rows
 };
-
-__global__ void ada_state_init_kernel(AdaState* s, float p, float target, float step, float p_max, int interval) {
-  s->p = p; s->target = target; s->step = step; s->p_max = p_max; s->interval = interval; s->seen = 0;
-  s->n_pos = 0; s->n_neg = 0; s->n_total = 0; s->adjustments = 0; s->last_r = 0.f;
-}
-__global__ void ada_state_set_kernel(AdaState* s, float target, float step, float p_max, int interval, int set_p, float p) {
-  s->target = target; s->step = step; s->p_max = p_max; s->interval = interval;
-  if (set_p) s->p = p;
-}
-// resume: a checkpoint's counters; the settings and p stay
-__global__ void ada_state_counters_kernel(AdaState* s, int seen, long long n_pos, long long n_neg, long long n_total, int adjustments,
-                                          float last_r) {
-  s->seen = seen; s->n_pos = n_pos; s->n_neg = n_neg; s->n_total = n_total; s->adjustments = adjustments; s->last_r = last_r;
-}
 
 __global__ __launch_bounds__(256) void ada_gate_kernel(const float* __restrict__ rows, const AdaState* __restrict__ st,
                                                        float* __restrict__ table, int n, int n_groups) {
@@ -138,27 +115,28 @@ extern "C" size_t srgan_ada_state_bytes(void) { return sizeof(srgan::AdaState); 
 extern "C" int srgan_ada_state_init(void* state, float p, float target, float step, float p_max, int interval, void* stream) {
   SRGAN_REQUIRE(state && srgan::ada_settings_ok(target, step, p_max, interval) && p >= 0.f && p <= p_max,
                 "ada_state_init: bad argument (target finite, step >= 0 and finite, 0 <= p <= p_max <= 1, interval >= 1; NaN refused)");
-  hipLaunchKernelGGL(srgan::ada_state_init_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::AdaState*>(state), p,
-                     target, step, p_max, interval);
-  return check_launch("ada_state_init_kernel");
+  srgan::AdaState s = {};                // the counters and last_r at zero
+  s.p = p; s.target = target; s.step = step; s.p_max = p_max; s.interval = interval;
+  return srgan::record_write(state, &s, sizeof s, srgan::record_all_words<srgan::AdaState>(), as_stream(stream), "ada_state_init");
 }
 
 extern "C" int srgan_ada_state_set(void* state, float target, float step, float p_max, int interval, int set_p, float p,
                                    void* stream) {
   SRGAN_REQUIRE(state && srgan::ada_settings_ok(target, step, p_max, interval) && (!set_p || (p >= 0.f && p <= p_max)),
                 "ada_state_set: bad argument (target finite, step >= 0 and finite, 0 <= p <= p_max <= 1, interval >= 1; NaN refused)");
-  hipLaunchKernelGGL(srgan::ada_state_set_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::AdaState*>(state),
-                     target, step, p_max, interval, set_p ? 1 : 0, set_p ? p : 0.f);
-  return check_launch("ada_state_set_kernel");
+  srgan::AdaState s = {};
+  s.target = target; s.step = step; s.p_max = p_max; s.interval = interval; s.p = set_p ? p : 0.f;
+  return srgan::record_write(state, &s, sizeof s, srgan::kAdaSet | (set_p ? srgan::kAdaSetP : 0u), as_stream(stream),
+                             "ada_state_set");
 }
 
 extern "C" int srgan_ada_state_set_counters(void* state, int seen, long long n_pos, long long n_neg, long long n_total,
                                             int adjustments, float last_r, void* stream) {
   SRGAN_REQUIRE(state && seen >= 0 && n_pos >= 0 && n_neg >= 0 && n_total >= 0 && n_pos + n_neg <= n_total && adjustments >= 0,
                 "ada_state_set_counters: bad argument (counts >= 0, n_pos + n_neg <= n_total)");
-  hipLaunchKernelGGL(srgan::ada_state_counters_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::AdaState*>(state),
-                     seen, n_pos, n_neg, n_total, adjustments, last_r);
-  return check_launch("ada_state_counters_kernel");
+  srgan::AdaState s = {};                // resume: the settings and p stay
+  s.seen = seen; s.n_pos = n_pos; s.n_neg = n_neg; s.n_total = n_total; s.adjustments = adjustments; s.last_r = last_r;
+  return srgan::record_write(state, &s, sizeof s, srgan::kAdaSetCounters, as_stream(stream), "ada_state_set_counters");
 }
 
 extern "C" int srgan_ada_gate(const float* rows, const void* state, float* table, int n, int n_groups, void* stream) {

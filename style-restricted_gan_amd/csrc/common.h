@@ -51,6 +51,10 @@ inline int check_launch(const char* what) {
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// pointwise.hip: the one write path of the device records (records.h).  `image`: a host struct of `bytes` bytes, carried by value in
+// the launch packet (nothing has to outlive the call); bit i of `mask` = store its 32-bit word i.  Returns check_launch(name).
+int record_write(void* rec, const void* image, size_t bytes, unsigned mask, hipStream_t st, const char* name);
+
 inline long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
 inline long long round_up(long long a, long long b) { return ceil_div(a, b) * b; }
 

@@ -18,6 +18,7 @@
 // weights 0 its vals[0..3], d_o and dz of the front rows are that kernel's bits (tests/test_cr_kernels_gpu.py holds it to that).
 #include "common.h"
 #include "loss_math.h"
+#include "records.h"
 #include <algorithm>
 #include <cstdint>
 
@@ -27,21 +28,6 @@ constexpr int kCrRow = 8;           // floats per table row
 constexpr int kCrItem = 4096;       // floats per item
 constexpr int kCrGridCap = 2048;    // 256 CUs x 8 workgroups; the rest by grid stride
 constexpr int CR_FLIP = 1, CR_TRANSLATION = 2, CR_ALL = 3;
-
-// lambda_real, lambda_fake and every are written by the host between steps (srgan_cr_state_init / _set); cr_real, cr_fake are the
-// unweighted terms of the last srgan_d_losses_cr, updates counts them.
-struct CrState { float lambda_real; float lambda_fake; int every; float cr_real; float cr_fake; int updates; int pad[2]; };
-static_assert(sizeof(CrState) == 32, "CrState layout");
-
-__global__ void cr_state_init_kernel(CrState* s, float lr, float lf, int every) {
-  s->lambda_real = lr; s->lambda_fake = lf; s->every = every;
-  s->cr_real = 0.f; s->cr_fake = 0.f; s->updates = 0; s->pad[0] = 0; s->pad[1] = 0;
-}
-__global__ void cr_state_set_kernel(CrState* s, float lr, float lf, int every) {
-  s->lambda_real = lr; s->lambda_fake = lf; s->every = every;
-}
-// resume: a checkpoint's count of penalised updates; everything else stays
-__global__ void cr_state_updates_kernel(CrState* s, int updates) { s->updates = updates; }
 
 // A table value as an integer in [lo, hi]: truncated, clamped while still a float; a non-finite value reads 0.
 __device__ __forceinline__ int cr_int(float v, int lo, int hi) {
@@ -298,23 +284,24 @@ extern "C" size_t srgan_cr_state_bytes(void) { return sizeof(srgan::CrState); }
 extern "C" int srgan_cr_state_init(void* state, float lambda_real, float lambda_fake, int every, void* stream) {
   SRGAN_REQUIRE(state && cr_weights_ok(lambda_real, lambda_fake, every),
                 "cr_state_init: bad argument (a record; weights >= 0 and finite, every >= 1; NaN refused)");
-  hipLaunchKernelGGL(cr_state_init_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<CrState*>(state), lambda_real,
-                     lambda_fake, every);
-  return check_launch("cr_state_init_kernel");
+  CrState s = {};                        // the two terms and the counter at zero
+  s.lambda_real = lambda_real; s.lambda_fake = lambda_fake; s.every = every;
+  return record_write(state, &s, sizeof s, record_all_words<CrState>(), as_stream(stream), "cr_state_init");
 }
 
 extern "C" int srgan_cr_state_set(void* state, float lambda_real, float lambda_fake, int every, void* stream) {
   SRGAN_REQUIRE(state && cr_weights_ok(lambda_real, lambda_fake, every),
                 "cr_state_set: bad argument (a record; weights >= 0 and finite, every >= 1; NaN refused)");
-  hipLaunchKernelGGL(cr_state_set_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<CrState*>(state), lambda_real,
-                     lambda_fake, every);
-  return check_launch("cr_state_set_kernel");
+  CrState s = {};
+  s.lambda_real = lambda_real; s.lambda_fake = lambda_fake; s.every = every;
+  return record_write(state, &s, sizeof s, kCrSet, as_stream(stream), "cr_state_set");
 }
 
 extern "C" int srgan_cr_state_set_updates(void* state, int updates, void* stream) {
   SRGAN_REQUIRE(state && updates >= 0, "cr_state_set_updates: bad argument (a record; updates >= 0)");
-  hipLaunchKernelGGL(cr_state_updates_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<CrState*>(state), updates);
-  return check_launch("cr_state_updates_kernel");
+  CrState s = {};                        // resume: everything else stays
+  s.updates = updates;
+  return record_write(state, &s, sizeof s, kCrSetUpdates, as_stream(stream), "cr_state_set_updates");
 }
 
 extern "C" int srgan_d_losses_cr(const float* const* o, const long long* per_row, const float* const* z, int n_scales, int rows,

@@ -20,6 +20,7 @@
 //
 // No atomics, plain stores, every sum has one owner and an order that depends on E, d and B only -- not on the grid.
 #include "common.h"
+#include "records.h"
 #include <algorithm>
 #include <cstdint>
 
@@ -32,20 +33,6 @@ constexpr int kMsChunk = 4096;      // floats of ONE row per workgroup item: a r
 constexpr int kMsRowsPerItem = 1;   // an item never holds more than one row
 constexpr int kMsGridCap = 2048;    // 256 CUs x 8 workgroups; the rest by grid stride
 static_assert(kMsRowsPerItem == 1 && kMsChunk == 16 * kMsBlock, "16 elements per thread and item, one row per item");
-
-// weight, eps, tau are written by the host between steps; the rest by ms_finish_kernel
-struct MsState { float weight; float eps; float tau; float ms; float weighted; float d_image; float d_latent; int updates; };
-static_assert(sizeof(MsState) == 32, "MsState layout");
-
-__global__ void ms_state_init_kernel(MsState* s, float weight, float eps, float tau) {
-  s->weight = weight; s->eps = eps; s->tau = tau;
-  s->ms = 0.f; s->weighted = 0.f; s->d_image = 0.f; s->d_latent = 0.f; s->updates = 0;
-}
-__global__ void ms_state_set_kernel(MsState* s, float weight, float eps, float tau) { s->weight = weight; s->eps = eps; s->tau = tau; }
-// resume: a checkpoint's counter and last values; the settings stay
-__global__ void ms_state_restore_kernel(MsState* s, int updates, float ms, float d_image, float d_latent) {
-  s->updates = updates; s->ms = ms; s->weighted = s->weight * ms; s->d_image = d_image; s->d_latent = d_latent;
-}
 
 __device__ __forceinline__ bool ms_aligned16(const float* a, const float* b) {
   return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
@@ -222,24 +209,24 @@ static bool ms_settings_ok(float weight, float eps, float tau) {
 extern "C" int srgan_ms_state_init(void* state, float weight, float eps, float tau, void* stream) {
   SRGAN_REQUIRE(state && ms_settings_ok(weight, eps, tau),
                 "ms_state_init: bad argument (weight >= 0, eps > 0, tau >= 0, all finite; NaN refused)");
-  hipLaunchKernelGGL(srgan::ms_state_init_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::MsState*>(state), weight,
-                     eps, tau);
-  return check_launch("ms_state_init_kernel");
+  srgan::MsState s = {};                 // the last values and the counter at zero
+  s.weight = weight; s.eps = eps; s.tau = tau;
+  return srgan::record_write(state, &s, sizeof s, srgan::record_all_words<srgan::MsState>(), as_stream(stream), "ms_state_init");
 }
 
 extern "C" int srgan_ms_state_set(void* state, float weight, float eps, float tau, void* stream) {
   SRGAN_REQUIRE(state && ms_settings_ok(weight, eps, tau),
                 "ms_state_set: bad argument (weight >= 0, eps > 0, tau >= 0, all finite; NaN refused)");
-  hipLaunchKernelGGL(srgan::ms_state_set_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::MsState*>(state), weight,
-                     eps, tau);
-  return check_launch("ms_state_set_kernel");
+  srgan::MsState s = {};
+  s.weight = weight; s.eps = eps; s.tau = tau;
+  return srgan::record_write(state, &s, sizeof s, srgan::kMsSet, as_stream(stream), "ms_state_set");
 }
 
 extern "C" int srgan_ms_state_restore(void* state, int updates, float ms, float d_image, float d_latent, void* stream) {
   SRGAN_REQUIRE(state && updates >= 0, "ms_state_restore: bad argument (updates >= 0)");
-  hipLaunchKernelGGL(srgan::ms_state_restore_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::MsState*>(state),
-                     updates, ms, d_image, d_latent);
-  return check_launch("ms_state_restore_kernel");
+  srgan::MsState s = {};                 // resume: the settings stay, and `weighted` until the next ms_finish
+  s.updates = updates; s.ms = ms; s.d_image = d_image; s.d_latent = d_latent;
+  return srgan::record_write(state, &s, sizeof s, srgan::kMsRestore, as_stream(stream), "ms_state_restore");
 }
 
 extern "C" size_t srgan_ms_workspace(int b, long long e) {

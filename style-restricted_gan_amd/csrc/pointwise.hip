@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstring>
 #include "common.h"
+#include "records.h"
 
 namespace srgan {
 
@@ -332,15 +333,24 @@ __global__ __launch_bounds__(256) void upload_small_kernel(unsigned int* __restr
   for (int i = threadIdx.x; i < nwords; i += 256) dst[i] = blob.w[i];
 }
 
-// ---- device-resident Adam state ---------------------------------------------------------------------------------------
-// {step, lr, beta1, beta2, eps, step_size, inv_sqrt_bc2}: the step counter lives on the device so that a captured train step
-// (hipGraph) advances it on every replay; the host mirrors the count for checkpoints only.
-struct AdamState { int step; float lr, beta1, beta2, eps, step_size, inv_sqrt_bc2; int pad; };
-static_assert(sizeof(AdamState) == 32, "AdamState layout");
-__global__ void adam_state_init_kernel(AdamState* s, int step, float lr, float beta1, float beta2, float eps) {
-  s->step = step; s->lr = lr; s->beta1 = beta1; s->beta2 = beta2; s->eps = eps; s->step_size = 0.f; s->inv_sqrt_bc2 = 0.f; s->pad = 0;
+// The one write path of the device records (records.h): one wave, lane i < 16 stores word i of the by-value image iff bit i of
+// `mask` is set.  Ordinary stream work, like the launches that read the record; a word that is not named keeps what it holds.
+__global__ __launch_bounds__(64) void record_write_kernel(unsigned int* __restrict__ rec, RecordImage img, unsigned mask) {
+  const unsigned i = threadIdx.x;
+  if (i < (unsigned)kRecordWords && ((mask >> i) & 1u)) rec[i] = img.w[i];
 }
-__global__ void adam_state_lr_kernel(AdamState* s, float lr) { s->lr = lr; }
+int record_write(void* rec, const void* image, size_t bytes, unsigned mask, hipStream_t st, const char* name) {
+  SRGAN_REQUIRE(rec && (reinterpret_cast<uintptr_t>(rec) & 3) == 0 && bytes % 4 == 0 && bytes <= sizeof(RecordImage) &&
+                    (mask >> (bytes / 4)) == 0, "%s: words %#x of a record of %zu bytes at %p", name, mask, bytes, rec);
+  RecordImage img = {};
+  std::memcpy(img.w, image, bytes);
+  hipLaunchKernelGGL(record_write_kernel, dim3(1), dim3(64), 0, st, static_cast<unsigned int*>(rec), img, mask);
+  return check_launch(name);
+}
+
+// ---- device-resident Adam state ---------------------------------------------------------------------------------------
+// AdamState (records.h): the step counter lives on the device so that a captured train step (hipGraph) advances it on every
+// replay; the host mirrors the count for checkpoints only.
 // torch 1.4: p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)   (bias corrections in double, as the host path did)
 __global__ void adam_tick_kernel(AdamState* s) {
   const int t = s->step + 1;
@@ -413,17 +423,8 @@ __global__ __launch_bounds__(256) void adam_multi_dev_kernel(const unsigned long
 
 // ---- device-side gradient guard (extension, no counterpart in the reference) ------------------------------------------------------
 // GradScaler's "found inf: skip the step" and clip_grad_norm_ (norm type 2) for an optimiser whose step the host never sees (a
-// replayed hipGraph).  One record per optimiser; norm / scale / skip are those of the last step, the counters are cumulative.
-struct GuardState { float max_norm, norm, scale; int skip, steps, skipped, clipped, pad; };
-static_assert(sizeof(GuardState) == 32, "GuardState layout");
-__global__ void guard_state_init_kernel(GuardState* s, float max_norm) {
-  s->max_norm = max_norm; s->norm = 0.f; s->scale = 1.f; s->skip = 0; s->steps = 0; s->skipped = 0; s->clipped = 0; s->pad = 0;
-}
-__global__ void guard_state_max_norm_kernel(GuardState* s, float max_norm) { s->max_norm = max_norm; }
-// resume: the cumulative counters of a checkpoint; the threshold and the last step's decision stay
-__global__ void guard_state_counters_kernel(GuardState* s, int steps, int skipped, int clipped) {
-  s->steps = steps; s->skipped = skipped; s->clipped = clipped;
-}
+// replayed hipGraph).  One record per optimiser (GuardState, records.h); norm / scale / skip are those of the last step, the
+// counters are cumulative.
 
 // Sum of squares of every gradient, one fp32 partial per 4096-element chunk.  `table`: n_records records of three 64-bit words
 // {g, numel, chunk0}; the work is the flat chunk list of ema_multi_dev_kernel (chunk0 = prefix sum of ceil(numel / 4096)), so 300
@@ -514,14 +515,8 @@ __global__ __launch_bounds__(256) void adam_multi_dev_guard_kernel(const unsigne
 }
 
 // ---- exponential moving average of the sampling weights (extension, no counterpart in the reference) ------------------
-// {n, ramp, decay, c}: n = updates done, c = 1 - d_n of the update in flight.  Like AdamState the count lives on the device so
-// that a captured train step advances it on every replay; the host mirrors n for checkpoints only.
-struct EmaState { int n; int ramp; float decay; float c; };
-static_assert(sizeof(EmaState) == 16, "EmaState layout");
-__global__ void ema_state_init_kernel(EmaState* s, int n, int ramp, float decay) {
-  s->n = n; s->ramp = ramp; s->decay = decay; s->c = 0.f;
-}
-__global__ void ema_state_decay_kernel(EmaState* s, float decay) { s->decay = decay; }
+// EmaState (records.h) {n, ramp, decay, c}: n = updates done, c = 1 - d_n of the update in flight.  Like AdamState the count lives
+// on the device so that a captured train step advances it on every replay; the host mirrors n for checkpoints only.
 // d_n = ramp ? min(decay, (1 + n) / (10 + n)) : decay in double, rounded to float once; c = 1 - d_n in float
 __global__ void ema_tick_kernel(EmaState* s) {
   const int n = s->n + 1;
@@ -792,15 +787,16 @@ extern "C" size_t srgan_adam_state_bytes(void) { return sizeof(srgan::AdamState)
 
 extern "C" int srgan_adam_state_init(void* state, float lr, float beta1, float beta2, float eps, int steps_done, void* stream) {
   SRGAN_REQUIRE(state && steps_done >= 0, "adam_state_init: bad argument");
-  hipLaunchKernelGGL(srgan::adam_state_init_kernel, dim3(1), dim3(1), 0, as_stream(stream),
-                     static_cast<srgan::AdamState*>(state), steps_done, lr, beta1, beta2, eps);
-  return check_launch("adam_state_init_kernel");
+  srgan::AdamState s = {};               // step_size, inv_sqrt_bc2 (the tick derives them) and the pad at zero
+  s.step = steps_done; s.lr = lr; s.beta1 = beta1; s.beta2 = beta2; s.eps = eps;
+  return srgan::record_write(state, &s, sizeof s, srgan::record_all_words<srgan::AdamState>(), as_stream(stream), "adam_state_init");
 }
 
 extern "C" int srgan_adam_state_set_lr(void* state, float lr, void* stream) {
   SRGAN_REQUIRE(state, "adam_state_set_lr: bad argument");
-  hipLaunchKernelGGL(srgan::adam_state_lr_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::AdamState*>(state), lr);
-  return check_launch("adam_state_lr_kernel");
+  srgan::AdamState s = {};
+  s.lr = lr;
+  return srgan::record_write(state, &s, sizeof s, srgan::kAdamSetLr, as_stream(stream), "adam_state_set_lr");
 }
 
 extern "C" int srgan_adam_multi_dev(const void* table, int n_tensors, long long max_numel, void* state, void* stream) {
@@ -816,24 +812,25 @@ extern "C" size_t srgan_grad_guard_state_bytes(void) { return sizeof(srgan::Guar
 
 extern "C" int srgan_grad_guard_state_init(void* state, float max_norm, void* stream) {
   SRGAN_REQUIRE(state && max_norm > 0.f, "grad_guard_state_init: bad argument (max_norm > 0, +inf = no clipping; NaN refused)");
-  hipLaunchKernelGGL(srgan::guard_state_init_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::GuardState*>(state),
-                     max_norm);
-  return check_launch("guard_state_init_kernel");
+  srgan::GuardState s = {};              // the last step's decision and the counters at zero
+  s.max_norm = max_norm; s.scale = 1.f;
+  return srgan::record_write(state, &s, sizeof s, srgan::record_all_words<srgan::GuardState>(), as_stream(stream),
+                             "grad_guard_state_init");
 }
 
 extern "C" int srgan_grad_guard_state_set_max_norm(void* state, float max_norm, void* stream) {
   SRGAN_REQUIRE(state && max_norm > 0.f, "grad_guard_state_set_max_norm: bad argument (max_norm > 0, +inf = no clipping; NaN refused)");
-  hipLaunchKernelGGL(srgan::guard_state_max_norm_kernel, dim3(1), dim3(1), 0, as_stream(stream),
-                     static_cast<srgan::GuardState*>(state), max_norm);
-  return check_launch("guard_state_max_norm_kernel");
+  srgan::GuardState s = {};
+  s.max_norm = max_norm;
+  return srgan::record_write(state, &s, sizeof s, srgan::kGuardSetMaxNorm, as_stream(stream), "grad_guard_state_set_max_norm");
 }
 
 extern "C" int srgan_grad_guard_state_set_counters(void* state, int steps, int skipped, int clipped, void* stream) {
   SRGAN_REQUIRE(state && steps >= 0 && skipped >= 0 && clipped >= 0,
                 "grad_guard_state_set_counters: bad argument (steps, skipped, clipped >= 0)");
-  hipLaunchKernelGGL(srgan::guard_state_counters_kernel, dim3(1), dim3(1), 0, as_stream(stream),
-                     static_cast<srgan::GuardState*>(state), steps, skipped, clipped);
-  return check_launch("guard_state_counters_kernel");
+  srgan::GuardState s = {};              // resume: the threshold and the last step's decision stay
+  s.steps = steps; s.skipped = skipped; s.clipped = clipped;
+  return srgan::record_write(state, &s, sizeof s, srgan::kGuardSetCounters, as_stream(stream), "grad_guard_state_set_counters");
 }
 
 extern "C" size_t srgan_grad_guard_workspace(long long total_chunks) {
@@ -878,16 +875,16 @@ extern "C" size_t srgan_ema_chunk(void) { return (size_t)srgan::kEmaChunk; }
 
 extern "C" int srgan_ema_state_init(void* state, float decay, int ramp, int n_done, void* stream) {
   SRGAN_REQUIRE(state && decay >= 0.f && decay < 1.f && n_done >= 0, "ema_state_init: bad argument (decay in [0, 1), n_done >= 0)");
-  hipLaunchKernelGGL(srgan::ema_state_init_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::EmaState*>(state),
-                     n_done, ramp ? 1 : 0, decay);
-  return check_launch("ema_state_init_kernel");
+  srgan::EmaState s = {};                // c (the tick derives it) at zero
+  s.n = n_done; s.ramp = ramp ? 1 : 0; s.decay = decay;
+  return srgan::record_write(state, &s, sizeof s, srgan::record_all_words<srgan::EmaState>(), as_stream(stream), "ema_state_init");
 }
 
 extern "C" int srgan_ema_state_set_decay(void* state, float decay, void* stream) {
   SRGAN_REQUIRE(state && decay >= 0.f && decay < 1.f, "ema_state_set_decay: bad argument (decay in [0, 1))");
-  hipLaunchKernelGGL(srgan::ema_state_decay_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::EmaState*>(state),
-                     decay);
-  return check_launch("ema_state_decay_kernel");
+  srgan::EmaState s = {};
+  s.decay = decay;
+  return srgan::record_write(state, &s, sizeof s, srgan::kEmaSetDecay, as_stream(stream), "ema_state_set_decay");
 }
 
 extern "C" int srgan_ema_multi_dev(const void* table, int n_records, long long total_chunks, void* state, void* stream) {

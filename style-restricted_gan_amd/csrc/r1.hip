@@ -19,6 +19,7 @@
 // No atomics, plain global stores, every sum has one owner and an order that depends on H and W only: a sample's u0 and partials
 // depend neither on N nor on its position in the batch nor on the grid.  fp contraction is off: both paths round alike.
 #include "common.h"
+#include "records.h"
 #include <algorithm>
 #include <cstdint>
 
@@ -28,21 +29,6 @@ namespace srgan {
 
 constexpr int kR1Chunk = 4096;      // floats per partial sum
 constexpr int kR1GridCap = 2048;    // 256 CUs x 8 workgroups; the rest by grid stride
-
-// gamma, every and n are written by the host between steps (srgan_r1_state_init / _set), c = gamma * every / n with them;
-// penalty, mean_sq_norm are those of the last finalize, updates counts them.
-struct R1State { float gamma; int every_scale; float c; float penalty; float mean_sq_norm; int updates; int n; int pad; };
-static_assert(sizeof(R1State) == 32, "R1State layout");
-
-__global__ void r1_state_init_kernel(R1State* s, float gamma, int every, int n) {
-  s->gamma = gamma; s->every_scale = every; s->c = gamma * (float)every / (float)n;
-  s->penalty = 0.f; s->mean_sq_norm = 0.f; s->updates = 0; s->n = n; s->pad = 0;
-}
-__global__ void r1_state_set_kernel(R1State* s, float gamma, int every, int n) {
-  s->gamma = gamma; s->every_scale = every; s->c = gamma * (float)every / (float)n; s->n = n;
-}
-// resume: a checkpoint's count of penalised updates; everything else stays
-__global__ void r1_state_updates_kernel(R1State* s, int updates) { s->updates = updates; }
 
 // rows (or columns) of the image the pooled coordinate k averages: those of 2k - 1 .. 2k + 1 inside [0, len)
 __device__ __forceinline__ int r1_span(int k, int len) { return min(2 * k + 1, len - 1) - max(2 * k - 1, 0) + 1; }
@@ -131,6 +117,14 @@ __global__ __launch_bounds__(256) void r1_finalize_kernel(const float* __restric
   }
 }
 
+// The settings of a record (R1State, records.h) with c = gamma * every / n: one fp32 multiply, one fp32 divide, each rounded once
+// (contraction is off in this file and there is nothing to contract); the rest at zero.
+static R1State r1_settings(float gamma, int every, int n) {
+  R1State s = {};
+  s.gamma = gamma; s.every_scale = every; s.c = gamma * (float)every / (float)n; s.n = n;
+  return s;
+}
+
 static long long r1_chunks(int h, int w) { return ceil_div(3LL * h * w, kR1Chunk); }
 static bool r1_geometry_ok(int n, int h, int w) {
   return n > 0 && h > 0 && w > 0 && 3LL * h * w < (1LL << 31) - kR1Chunk && (long long)n * r1_chunks(h, w) < (1LL << 40);
@@ -145,24 +139,22 @@ extern "C" size_t srgan_r1_state_bytes(void) { return sizeof(srgan::R1State); }
 extern "C" int srgan_r1_state_init(void* state, float gamma, int every, int n, void* stream) {
   SRGAN_REQUIRE(state && gamma >= 0.f && gamma <= 3.0e38f && every >= 1 && n >= 1,
                 "r1_state_init: bad argument (gamma >= 0 and finite, every >= 1, n >= 1; NaN refused)");
-  hipLaunchKernelGGL(srgan::r1_state_init_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::R1State*>(state), gamma,
-                     every, n);
-  return check_launch("r1_state_init_kernel");
+  const srgan::R1State s = srgan::r1_settings(gamma, every, n);
+  return srgan::record_write(state, &s, sizeof s, srgan::record_all_words<srgan::R1State>(), as_stream(stream), "r1_state_init");
 }
 
 extern "C" int srgan_r1_state_set(void* state, float gamma, int every, int n, void* stream) {
   SRGAN_REQUIRE(state && gamma >= 0.f && gamma <= 3.0e38f && every >= 1 && n >= 1,
                 "r1_state_set: bad argument (gamma >= 0 and finite, every >= 1, n >= 1; NaN refused)");
-  hipLaunchKernelGGL(srgan::r1_state_set_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::R1State*>(state), gamma,
-                     every, n);
-  return check_launch("r1_state_set_kernel");
+  const srgan::R1State s = srgan::r1_settings(gamma, every, n);
+  return srgan::record_write(state, &s, sizeof s, srgan::kR1Set, as_stream(stream), "r1_state_set");
 }
 
 extern "C" int srgan_r1_state_set_updates(void* state, int updates, void* stream) {
   SRGAN_REQUIRE(state && updates >= 0, "r1_state_set_updates: bad argument (updates >= 0)");
-  hipLaunchKernelGGL(srgan::r1_state_updates_kernel, dim3(1), dim3(1), 0, as_stream(stream), static_cast<srgan::R1State*>(state),
-                     updates);
-  return check_launch("r1_state_updates_kernel");
+  srgan::R1State s = {};                 // resume: everything else stays
+  s.updates = updates;
+  return srgan::record_write(state, &s, sizeof s, srgan::kR1SetUpdates, as_stream(stream), "r1_state_set_updates");
 }
 
 extern "C" size_t srgan_r1_workspace(int n, int h, int w) {

@@ -36,6 +36,27 @@ class ConvDesc(ctypes.Structure):
                 ("sO", c_longlong), ("sI", c_longlong), ("sH", c_longlong), ("sW", c_longlong)]
 
 
+# The device records: csrc/records.h declares each once and tests/test_records_cpu.py holds the two sides together.  A field is
+# named as the key ``ops.*_state_read`` returns it under; pads carry a leading underscore and are left out of that dict.
+def _record(name, **fields):
+    """A ctypes.Structure of the keyword arguments, in their order."""
+    return type(name, (ctypes.Structure,), {"_fields_": list(fields.items())})
+
+
+AdamState = _record("AdamState", step=c_int, lr=c_float, beta1=c_float, beta2=c_float, eps=c_float, step_size=c_float,
+                    inv_sqrt_bc2=c_float, _pad=c_int)
+GuardState = _record("GuardState", max_norm=c_float, norm=c_float, scale=c_float, skip=c_int, steps=c_int, skipped=c_int,
+                     clipped=c_int, _pad=c_int)
+EmaState = _record("EmaState", n=c_int, ramp=c_int, decay=c_float, c=c_float)
+AdaState = _record("AdaState", p=c_float, target=c_float, step=c_float, p_max=c_float, interval=c_int, seen=c_int,
+                   n_pos=c_longlong, n_neg=c_longlong, n_total=c_longlong, adjustments=c_int, last_r=c_float)
+R1State = _record("R1State", gamma=c_float, every=c_int, c=c_float, penalty=c_float, mean_sq_norm=c_float, updates=c_int,
+                  n=c_int, _pad=c_int)
+CrState = _record("CrState", lambda_real=c_float, lambda_fake=c_float, every=c_int, cr_real=c_float, cr_fake=c_float,
+                  updates=c_int, _pad=c_int * 2)
+MsState = _record("MsState", weight=c_float, eps=c_float, tau=c_float, ms=c_float, weighted=c_float, d_image=c_float,
+                  d_latent=c_float, updates=c_int)
+
 P = c_void_p
 _DESC = POINTER(ConvDesc)
 

@@ -21,16 +21,11 @@ and then, in discriminator updates only
 import math
 
 import numpy as np
-import torch
 
-from . import ops
+from . import _lib, ops
 from .augment import DiffAugment
 
 __all__ = ["AdaptiveP", "join_rows", "threshold"]
-
-
-def _capturing():
-    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
 
 def _number(v, name, what):
@@ -73,11 +68,13 @@ def threshold(gan_kind):
 join_rows = DiffAugment.join_rows     # DiffAugment's rows; every stage has its own ``join_rows(table, uniforms)``
 
 
-class AdaptiveP:
+class AdaptiveP(ops.RecordOwner):
     """The settings and the device record of the controller.  ``target``: the value of ``r`` to hold (0.6 in the paper);
     ``interval``: observed discriminator updates per adjustment; ``kimg``: thousands of real images in which p can travel from 0 to
     1; ``p``: where it starts; ``p_max``: its ceiling -- 0.8 is the bound below which translation- and cutout-like transforms stay
     non-leaking in the paper.  The record is made at the first eager use, never inside a hipGraph capture."""
+
+    layout = _lib.AdaState
 
     def __init__(self, target=0.6, interval=4, kimg=500.0, p=0.0, p_max=0.8):
         self.target = check_target(target)
@@ -99,14 +96,10 @@ class AdaptiveP:
     def _ensure(self, device, n):
         n = int(n)
         if self.state is None:
-            if _capturing():
-                raise RuntimeError("AdaptiveP: the device record would be allocated inside a hipGraph capture; run one eager "
-                                   "step first")
-            self.state = ops.ada_state_new(device, self.p, self.target, self.step_size(n), self.p_max, self.interval)
+            self._make_record(ops.ada_state_new, device, self.p, self.target, self.step_size(n), self.p_max, self.interval)
             self._n, self._interval = n, self.interval
         elif self._n != n or self._interval != self.interval:
-            if _capturing():
-                raise RuntimeError("AdaptiveP: the batch size changed inside a hipGraph capture; run one eager step first")
+            ops.refuse_in_capture("AdaptiveP: the batch size changed inside a hipGraph capture; run one eager step first")
             ops.ada_state_set(self.state, self.target, self.step_size(n), self.p_max, self.interval)
             self._n, self._interval = n, self.interval
 
@@ -117,15 +110,13 @@ class AdaptiveP:
 
     def set_p(self, p):
         """A new p (0 <= p <= p_max), written into the device record between steps: a recorded step reads it from there."""
-        if _capturing():
-            raise RuntimeError("set_ada_p inside a hipGraph capture")
+        ops.refuse_in_capture("set_ada_p inside a hipGraph capture")
         self.p, _ = check_p(p, self.p_max, "set_ada_p")
         self._write(self.p)
 
     def set_target(self, target):
         """A new target, written into the device record between steps: a recorded step reads it from there."""
-        if _capturing():
-            raise RuntimeError("set_ada_target inside a hipGraph capture")
+        ops.refuse_in_capture("set_ada_target inside a hipGraph capture")
         self.target = check_target(target, "set_ada_target")
         self._write()
 
@@ -142,7 +133,7 @@ class AdaptiveP:
 
     def p_tensor(self):
         """p as a device scalar (a copy of the record's field; no synchronisation)"""
-        return self.state.view(torch.float32)[0].clone()
+        return self._record_field("p")
 
     def stats(self):
         """The record as a dict (``p``, ``target``, ``step``, ``p_max``, ``interval``, ``seen``, ``n_pos``, ``n_neg``, ``n_total``,
@@ -166,8 +157,7 @@ class AdaptiveP:
         """Restore ``state_dict()``, between steps.  The record is written in place; a controller that has not run yet makes it
         here for the saved batch size on ``device`` (the step re-derives ``step`` should its batch differ).  Without a record and
         without a saved batch size only the settings and the starting p are taken: the counters of such a checkpoint are zero."""
-        if _capturing():
-            raise RuntimeError("AdaptiveP: state loaded inside a hipGraph capture")
+        ops.refuse_in_capture("AdaptiveP: state loaded inside a hipGraph capture")
         target, interval = check_target(sd["target"]), check_interval(sd["interval"])
         kimg = float(sd["kimg"])
         if not (kimg > 0.0 and math.isfinite(kimg)):
@@ -189,10 +179,7 @@ class AdaptiveP:
         ops.ada_state_set_counters(self.state, *counters, float(sd["last_r"]))
 
     # -- hipGraph support -------------------------------------------------------------------------------------------------------
-    def graph_keepalive(self):
-        return [self.state] if self.state is not None else []
-
     def fingerprint(self):
         """What a recording bakes in: the object, the record, ``interval`` and the batch size.  Not p, target or step: they are
         device state."""
-        return (id(self), self.state.data_ptr() if self.state is not None else 0, self.interval, self._n)
+        return (id(self), self._record_ptr(), self.interval, self._n)

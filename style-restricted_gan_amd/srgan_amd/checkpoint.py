@@ -110,10 +110,6 @@ def _set_numpy_rng_state(sd):
                          float(sd["cached_gaussian"])))
 
 
-def _capturing():
-    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-
-
 class Checkpointing:
     """Mixin of the two trainer classes.  It reads the trainer through the attributes both keep (``G/D/E``, ``optG/D/E``,
     ``scheG/D/E``, ``hi``, ``lbd`` ...) and the extensions through the switches of ``SRGAN_training`` where they exist."""
@@ -162,8 +158,7 @@ class Checkpointing:
     def _ckpt_between_steps(self, what):
         if getattr(self, "_ema_scope", False):
             raise RuntimeError(f"{type(self).__name__}.{what} inside ema_weights(): self.G / self.E are the averaged copies there")
-        if _capturing():
-            raise RuntimeError(f"{type(self).__name__}.{what} inside a hipGraph capture; checkpoints are taken between steps")
+        ops.refuse_in_capture(f"{type(self).__name__}.{what} inside a hipGraph capture; checkpoints are taken between steps")
 
     # ---- save ---------------------------------------------------------------------------------------------------------------------
     def state_dict(self, rng=True):

@@ -25,10 +25,6 @@ __all__ = ["ConsistencyPairs", "BalancedCR", "CR_GROUPS", "schedule"]
 CR_GROUPS = {"flip": ops.CR_FLIP, "translation": ops.CR_TRANSLATION}
 
 
-def _capturing():
-    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-
-
 def schedule(k, every):
     """Which of a step's k discriminator updates are penalised: update i iff i % every == 0 (static per step)."""
     return [i % every == 0 for i in range(k)]
@@ -102,7 +98,7 @@ def check_weights(lambda_real, lambda_fake, every, what="BalancedCR"):
     return out[0], out[1], int(every)
 
 
-class BalancedCR:
+class BalancedCR(ops.RecordOwner):
     """The two weights, ``every``, the stage that draws ``T`` (``self.stage``) and the device record, made at the first use -- never
     inside a hipGraph capture.  ``SRGAN_training.enable_bcr`` wires it into the train step; ``pairs`` / ``loss`` serve a training loop
     of one's own:
@@ -121,25 +117,20 @@ class BalancedCR:
     # -- device side -----------------------------------------------------------------------------------------------------------
     def _ensure(self, device):
         if self.state is None:
-            if _capturing():
-                raise RuntimeError("BalancedCR: the device record would be allocated inside a hipGraph capture; run one eager "
-                                   "step first")
-            self.state = ops.cr_state_new(device, self.lambda_real, self.lambda_fake, self.every)
+            self._make_record(ops.cr_state_new, device, self.lambda_real, self.lambda_fake, self.every)
         return self.state
 
     def set_weights(self, lambda_real, lambda_fake):
         """New weights (>= 0), written into the device record between steps: a recorded step reads them from there."""
         self.lambda_real, self.lambda_fake, _ = check_weights(lambda_real, lambda_fake, self.every, "set_bcr_weights")
         if self.state is not None:
-            if _capturing():
-                raise RuntimeError("set_bcr_weights inside a hipGraph capture")
+            ops.refuse_in_capture("set_bcr_weights inside a hipGraph capture")
             ops.cr_state_set(self.state, self.lambda_real, self.lambda_fake, self.every)
 
     def set_updates(self, updates, device=None):
         """Resume: write a checkpoint's count of penalised updates into the device record, between steps.  A regulariser that has
         not run yet has no record: a count of 0 is what a fresh one starts at, any other makes the record here, on ``device``."""
-        if _capturing():
-            raise RuntimeError("BalancedCR: updates written inside a hipGraph capture")
+        ops.refuse_in_capture("BalancedCR: updates written inside a hipGraph capture")
         updates = int(updates)
         if updates < 0:
             raise ValueError(f"BalancedCR: updates must be >= 0, got {updates}")
@@ -171,13 +162,10 @@ class BalancedCR:
                                class_kind, pairs_first)
 
     # -- hipGraph support, checkpoints -----------------------------------------------------------------------------------------------
-    def graph_keepalive(self):
-        return [self.state] if self.state is not None else []
-
     def fingerprint(self):
         """What a recording bakes in: the object, ``every`` (the schedule and the launches), the policy, the settings and the draw
         source of the stage, the record.  Not the weights: they are device state."""
-        return (id(self), self.every, self.stage.fingerprint(), self.state.data_ptr() if self.state is not None else 0)
+        return (id(self), self.every, self.stage.fingerprint(), self._record_ptr())
 
     def state_dict(self):
         """weights, every, the stage's policy / translation / generator and the record's count of penalised updates; SYNCHRONISES"""

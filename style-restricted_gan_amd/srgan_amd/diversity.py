@@ -21,10 +21,6 @@ __all__ = ["ModeSeeking", "FORMS", "check_settings"]
 FORMS = tuple(sorted(ops.MS_FORMS))
 
 
-def _capturing():
-    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-
-
 def _number(name, v, what, low_open=False):
     try:
         f = float(v)
@@ -51,7 +47,7 @@ def check_settings(weight, form, eps, tau, what="ModeSeeking"):
     return weight, form, eps, tau
 
 
-class ModeSeeking:
+class ModeSeeking(ops.RecordOwner):
     """The settings, a CPU generator of its own for the second latent code and the device record, made at the first use -- never
     inside a hipGraph capture.  ``SRGAN_training.enable_mode_seeking`` wires it into the train step; for a loop of one's own:
 
@@ -82,18 +78,14 @@ class ModeSeeking:
 
     def _ensure(self, device):
         if self.state is None:
-            if _capturing():
-                raise RuntimeError("ModeSeeking: the device record would be allocated inside a hipGraph capture; run one eager "
-                                   "step first")
-            self.state = ops.ms_state_new(device, self.weight, self.eps, self._tau())
+            self._make_record(ops.ms_state_new, device, self.weight, self.eps, self._tau())
         return self.state
 
     def set_weight(self, weight):
         """A new weight (>= 0), written into the device record between steps: a recorded step reads it from there."""
         self.weight = check_settings(weight, self.form, self.eps, self.tau, "set_mode_seeking_weight")[0]
         if self.state is not None:
-            if _capturing():
-                raise RuntimeError("set_mode_seeking_weight inside a hipGraph capture")
+            ops.refuse_in_capture("set_mode_seeking_weight inside a hipGraph capture")
             ops.ms_state_set(self.state, self.weight, self.eps, self._tau())
 
     def loss(self, i1, i2, z1, z2):
@@ -109,14 +101,10 @@ class ModeSeeking:
         return out
 
     # -- hipGraph support, checkpoints -----------------------------------------------------------------------------------------------
-    def graph_keepalive(self):
-        return [self.state] if self.state is not None else []
-
     def fingerprint(self):
         """What a recording bakes in: the object, the form (a kernel argument), the draw source, the record.  Not the weight (nor
         eps, tau): they are device state."""
-        return (id(self), self.form, id(getattr(self.draw_fn, "__func__", self.draw_fn)),
-                self.state.data_ptr() if self.state is not None else 0)
+        return (id(self), self.form, id(getattr(self.draw_fn, "__func__", self.draw_fn)), self._record_ptr())
 
     def state_dict(self):
         """the settings, the generator's state, the record's counter and last values; SYNCHRONISES"""
@@ -130,8 +118,7 @@ class ModeSeeking:
         otherwise)."""
         if sd["form"] != self.form:
             raise ValueError(f"ModeSeeking.load_state_dict: form = {sd['form']!r} in the state, {self.form!r} here")
-        if _capturing():
-            raise RuntimeError("ModeSeeking.load_state_dict inside a hipGraph capture")
+        ops.refuse_in_capture("ModeSeeking.load_state_dict inside a hipGraph capture")
         self.weight, _, self.eps, self.tau = check_settings(sd["weight"], sd["form"], sd["eps"], sd["tau"], "ModeSeeking.load_state_dict")
         updates = int(sd["updates"])
         if updates < 0:

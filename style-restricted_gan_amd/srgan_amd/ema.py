@@ -39,8 +39,7 @@ def make_copy(net):
 
 def read_state(state):
     """(n, ramp, decay, c) of a device record; synchronises."""
-    raw = state.cpu().numpy().tobytes()
-    return struct.unpack("iiff", raw[:16])
+    return tuple(ops.ema_state_read(state).values())
 
 
 def _records(live, twin):
@@ -84,8 +83,7 @@ class WeightEMA:
     def __init__(self, nets, decay=0.999, ramp=True, updates=0):
         if not 0.0 <= float(decay) < 1.0:
             raise ValueError("ema: decay must lie in [0, 1)")
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("ema: the averaged copies first appear inside a hipGraph capture -- enable the EMA between steps")
+        ops.refuse_in_capture("ema: the averaged copies first appear inside a hipGraph capture -- enable the EMA between steps")
         self.live = {k: dp.unwrap(v) for k, v in nets.items()}
         self.twins = {k: make_copy(v) for k, v in self.live.items()}
         self.decay, self.ramp, self.updates = float(decay), bool(ramp), int(updates)
@@ -124,8 +122,7 @@ class WeightEMA:
     def set_decay(self, decay):
         if not 0.0 <= float(decay) < 1.0:
             raise ValueError("ema: decay must lie in [0, 1)")
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("ema: decay changed inside a hipGraph capture")
+        ops.refuse_in_capture("ema: decay changed inside a hipGraph capture")
         ops.ema_state_set_decay(self.state, decay)
         self.decay = float(decay)
 
@@ -133,8 +130,7 @@ class WeightEMA:
         """Re-seed the device record IN PLACE (a recording that points at it stays valid)."""
         if not 0.0 <= float(decay) < 1.0:
             raise ValueError("ema: decay must lie in [0, 1)")
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("ema: record re-seeded inside a hipGraph capture")
+        ops.refuse_in_capture("ema: record re-seeded inside a hipGraph capture")
         ops.ema_state_init(self.state, decay, ramp, updates)
         self.decay, self.ramp, self.updates = float(decay), bool(ramp), int(updates)
 

@@ -512,7 +512,7 @@ def _wgrad_arena(device=None):
     key = ("wgrad_arena", dev.index)
     a = _workspaces.get(key)
     want = min(max(_WGRAD_ARENA_BYTES, _arena_want.get(dev.index, 0)), _WGRAD_ARENA_MAX)
-    if a is None or (a.numel() < want and not torch.cuda.is_current_stream_capturing()):
+    if a is None or (a.numel() < want and not capturing()):
         if a is not None:
             bump_structure_epoch()
         want = (want + (16 << 20) - 1) // (16 << 20) * (16 << 20)
@@ -2377,17 +2377,67 @@ def adam_step_(p, g, m, v, lr, beta1, beta2, eps, step):
                                            float(beta2), float(eps), int(step), _stream()), "adam_step")
 
 
-def adam_state_new(device, lr, beta1, beta2, eps, steps_done):
-    """Device-resident Adam record {t, lr, betas, eps, derived step size} seeded with ``steps_done`` completed steps."""
-    lib = _lib.load()
-    st = torch.empty(lib.srgan_adam_state_bytes(), dtype=torch.uint8, device=device)
-    _lib.check(lib.srgan_adam_state_init(_ptr(st), float(lr), float(beta1), float(beta2), float(eps), int(steps_done), _stream()),
-               "adam_state_init")
+# ---- device records: state a recorded step reads, written by the host between steps (csrc/records.h; layouts: _lib.*State) ------
+def capturing():
+    """Is the current stream recording a hipGraph?  (Never without a GPU.)  Records, workspaces and tables are made and rewritten
+    between steps only: their owners refuse while this holds."""
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+def refuse_in_capture(what):
+    """RuntimeError(what) while the current stream records: the caller allocates or rewrites what a recording points at."""
+    if capturing():
+        raise RuntimeError(what)
+
+
+def _record_call(entry, state, *args):
+    """``srgan_<entry>(state, *args, stream)``: one write of a record on the current stream"""
+    _lib.check(getattr(_lib.load(), "srgan_" + entry)(_ptr(state), *args, _stream()), entry)
+
+
+def _record_new(layout, device, init, *args):
+    """A record of ``layout`` on ``device``, written by its ``init`` entry"""
+    st = torch.empty(ctypes.sizeof(layout), dtype=torch.uint8, device=device)
+    _record_call(init, st, *args)
     return st
 
 
+def _record_read(layout, state):
+    """The record as a dict of its fields, pads left out; synchronises the current stream."""
+    torch.cuda.current_stream(state.device).synchronize()
+    rec = layout.from_buffer_copy(state.cpu().numpy().tobytes())
+    return {name: getattr(rec, name) for name, _ in layout._fields_ if not name.startswith("_")}
+
+
+class RecordOwner:
+    """What the owners of one device record (``self.state``, of ``self.layout``) share: it is made at the first use, never inside
+    a hipGraph capture, and a recording bakes its address in."""
+
+    state = None
+
+    def _make_record(self, new, *args):
+        refuse_in_capture(f"{type(self).__name__}: the device record would be allocated inside a hipGraph capture; run one eager "
+                          "step first")
+        self.state = new(*args)
+
+    def _record_ptr(self):
+        return self.state.data_ptr() if self.state is not None else 0
+
+    def _record_field(self, name):
+        """A float field of the record as a device scalar (a copy; no synchronisation)."""
+        return self.state.view(torch.float32)[getattr(self.layout, name).offset // 4].clone()
+
+    def graph_keepalive(self):
+        return [self.state] if self.state is not None else []
+
+
+def adam_state_new(device, lr, beta1, beta2, eps, steps_done):
+    """Device-resident Adam record {t, lr, betas, eps, derived step size} seeded with ``steps_done`` completed steps."""
+    return _record_new(_lib.AdamState, device, "adam_state_init", float(lr), float(beta1), float(beta2), float(eps), int(steps_done))
+
+
 def adam_state_set_lr(state, lr):
-    _lib.check(_lib.load().srgan_adam_state_set_lr(_ptr(state), float(lr), _stream()), "adam_state_set_lr")
+    _record_call("adam_state_set_lr", state, float(lr))
 
 
 def adam_multi_dev_(table_dev, n_tensors, max_numel, state):
@@ -2414,29 +2464,22 @@ def _max_norm_arg(max_norm):
 
 def grad_guard_state_new(device, max_norm=None):
     """Device-resident record {max_norm, norm, scale, skip, steps, skipped, clipped, pad} with the counters at zero."""
-    lib = _lib.load()
-    st = torch.empty(lib.srgan_grad_guard_state_bytes(), dtype=torch.uint8, device=device)
-    _lib.check(lib.srgan_grad_guard_state_init(_ptr(st), _max_norm_arg(max_norm), _stream()), "grad_guard_state_init")
-    return st
+    return _record_new(_lib.GuardState, device, "grad_guard_state_init", _max_norm_arg(max_norm))
 
 
 def grad_guard_state_set_max_norm(state, max_norm):
-    _lib.check(_lib.load().srgan_grad_guard_state_set_max_norm(_ptr(state), _max_norm_arg(max_norm), _stream()),
-               "grad_guard_state_set_max_norm")
+    _record_call("grad_guard_state_set_max_norm", state, _max_norm_arg(max_norm))
 
 
 def grad_guard_state_set_counters(state, steps, skipped, clipped):
     """Write the cumulative counters between steps (resume from a checkpoint); the threshold and the last step's decision stay."""
-    _lib.check(_lib.load().srgan_grad_guard_state_set_counters(_ptr(state), int(steps), int(skipped), int(clipped), _stream()),
-               "grad_guard_state_set_counters")
+    _record_call("grad_guard_state_set_counters", state, int(steps), int(skipped), int(clipped))
 
 
 def grad_guard_state_read(state):
     """The record as a dict; synchronises the current stream (the only host read of the guard)."""
-    torch.cuda.current_stream(state.device).synchronize()
-    max_norm, norm, scale, skip, steps, skipped, clipped, _ = struct.unpack("fffiiiii", state.cpu().numpy().tobytes()[:32])
-    return dict(max_norm=None if max_norm == float("inf") else max_norm, norm=norm, scale=scale, skip=bool(skip), steps=steps,
-                skipped=skipped, clipped=clipped)
+    rec = _record_read(_lib.GuardState, state)
+    return dict(rec, max_norm=None if rec["max_norm"] == float("inf") else rec["max_norm"], skip=bool(rec["skip"]))
 
 
 def grad_guard_workspace_bytes(total_chunks):
@@ -2481,19 +2524,21 @@ def adam_multi_dev_guard_(table_dev, n_tensors, max_numel, state, guard_state):
 # ---- exponential moving average of the sampling weights (srgan_amd.ema; extension, no counterpart in the reference) --------
 def ema_state_new(device, decay, ramp, n_done):
     """Device-resident record {n, ramp, decay, c} seeded with ``n_done`` completed updates."""
-    lib = _lib.load()
-    st = torch.empty(lib.srgan_ema_state_bytes(), dtype=torch.uint8, device=device)
-    ema_state_init(st, decay, ramp, n_done)
-    return st
+    return _record_new(_lib.EmaState, device, "ema_state_init", float(decay), int(bool(ramp)), int(n_done))
 
 
 def ema_state_init(state, decay, ramp, n_done):
     """(Re-)seed an existing record in place: a captured step that points at it keeps pointing at it."""
-    _lib.check(_lib.load().srgan_ema_state_init(_ptr(state), float(decay), int(bool(ramp)), int(n_done), _stream()), "ema_state_init")
+    _record_call("ema_state_init", state, float(decay), int(bool(ramp)), int(n_done))
 
 
 def ema_state_set_decay(state, decay):
-    _lib.check(_lib.load().srgan_ema_state_set_decay(_ptr(state), float(decay), _stream()), "ema_state_set_decay")
+    _record_call("ema_state_set_decay", state, float(decay))
+
+
+def ema_state_read(state):
+    """The record as a dict; synchronises the current stream."""
+    return _record_read(_lib.EmaState, state)
 
 
 def ema_chunk():
@@ -2636,36 +2681,28 @@ def diffaugment_cat(xs, table, flags, cut, gated=False):
 # ---- adaptive discriminator augmentation: p on the device (srgan_amd.ada; extension, no counterpart in the reference) -----------
 ADA_ROW = 16                   # floats per row the gate reads: [a stage's table row (slots 0..6), -, one uniform per gated group, ...]
 ADA_MAX_SCALES = 4
-_ADA_FMT = "ffffiiqqqif"       # the record (include/srgan_hip.h): 56 bytes
-_ADA_FIELDS = ("p", "target", "step", "p_max", "interval", "seen", "n_pos", "n_neg", "n_total", "adjustments", "last_r")
 
 
 def ada_state_new(device, p, target, step, p_max, interval):
     """Device-resident record {p, target, step, p_max, interval, seen, n_pos, n_neg, n_total, adjustments, last_r}, counters 0."""
-    lib = _lib.load()
-    st = torch.empty(lib.srgan_ada_state_bytes(), dtype=torch.uint8, device=device)
-    _lib.check(lib.srgan_ada_state_init(_ptr(st), float(p), float(target), float(step), float(p_max), int(interval), _stream()),
-               "ada_state_init")
-    return st
+    return _record_new(_lib.AdaState, device, "ada_state_init", float(p), float(target), float(step), float(p_max), int(interval))
 
 
 def ada_state_set(state, target, step, p_max, interval, p=None):
     """Rewrite target, step, p_max, interval and (``p`` given) p between steps; the counters stay (a recorded step reads the
     record)."""
-    _lib.check(_lib.load().srgan_ada_state_set(_ptr(state), float(target), float(step), float(p_max), int(interval),
-                                               0 if p is None else 1, 0.0 if p is None else float(p), _stream()), "ada_state_set")
+    _record_call("ada_state_set", state, float(target), float(step), float(p_max), int(interval), 0 if p is None else 1,
+                 0.0 if p is None else float(p))
 
 
 def ada_state_set_counters(state, seen, n_pos, n_neg, n_total, adjustments, last_r):
     """Write the heuristic's counters between steps (resume from a checkpoint); p and the settings stay."""
-    _lib.check(_lib.load().srgan_ada_state_set_counters(_ptr(state), int(seen), int(n_pos), int(n_neg), int(n_total),
-                                                        int(adjustments), float(last_r), _stream()), "ada_state_set_counters")
+    _record_call("ada_state_set_counters", state, int(seen), int(n_pos), int(n_neg), int(n_total), int(adjustments), float(last_r))
 
 
 def ada_state_read(state):
     """The record as a dict; synchronises the current stream."""
-    torch.cuda.current_stream(state.device).synchronize()
-    return dict(zip(_ADA_FIELDS, struct.unpack(_ADA_FMT, state.cpu().numpy().tobytes()[:struct.calcsize(_ADA_FMT)])))
+    return _record_read(_lib.AdaState, state)
 
 
 def ada_gate(rows, state, n_groups=3):
@@ -2760,33 +2797,24 @@ def geom_augment(x, table, flags, gated=False):
 R1_CHUNK = 4096                # floats of a sample per partial sum of |g|^2
 
 
-def _r1_args(gamma, every, n):
-    return float(gamma), int(every), int(n)
-
-
 def r1_state_new(device, gamma, every, n):
     """Device-resident record {gamma, every, c, penalty, mean_sq_norm, updates, n, pad}, c = gamma * every / n, counters at zero."""
-    lib = _lib.load()
-    st = torch.empty(lib.srgan_r1_state_bytes(), dtype=torch.uint8, device=device)
-    _lib.check(lib.srgan_r1_state_init(_ptr(st), *_r1_args(gamma, every, n), _stream()), "r1_state_init")
-    return st
+    return _record_new(_lib.R1State, device, "r1_state_init", float(gamma), int(every), int(n))
 
 
 def r1_state_set(state, gamma, every, n):
     """Rewrite gamma, every, n and c between steps; the counters stay (a recorded step reads the record)."""
-    _lib.check(_lib.load().srgan_r1_state_set(_ptr(state), *_r1_args(gamma, every, n), _stream()), "r1_state_set")
+    _record_call("r1_state_set", state, float(gamma), int(every), int(n))
 
 
 def r1_state_set_updates(state, updates):
     """Write the count of penalised updates between steps (resume from a checkpoint); everything else stays."""
-    _lib.check(_lib.load().srgan_r1_state_set_updates(_ptr(state), int(updates), _stream()), "r1_state_set_updates")
+    _record_call("r1_state_set_updates", state, int(updates))
 
 
 def r1_state_read(state):
     """The record as a dict; synchronises the current stream (the only host read of the penalty)."""
-    torch.cuda.current_stream(state.device).synchronize()
-    gamma, every, c, penalty, msn, updates, n, _ = struct.unpack("fifffiii", state.cpu().numpy().tobytes()[:32])
-    return dict(gamma=gamma, every=every, c=c, penalty=penalty, mean_sq_norm=msn, updates=updates, n=n)
+    return _record_read(_lib.R1State, state)
 
 
 def r1_workspace_bytes(n, h, w):
@@ -2857,27 +2885,22 @@ def cr_pairs(xs, table, flags):
 
 def cr_state_new(device, lambda_real, lambda_fake, every):
     """Device-resident record {lambda_real, lambda_fake, every, cr_real, cr_fake, updates, pad, pad}, counters at zero."""
-    lib = _lib.load()
-    st = torch.empty(lib.srgan_cr_state_bytes(), dtype=torch.uint8, device=device)
-    _lib.check(lib.srgan_cr_state_init(_ptr(st), float(lambda_real), float(lambda_fake), int(every), _stream()), "cr_state_init")
-    return st
+    return _record_new(_lib.CrState, device, "cr_state_init", float(lambda_real), float(lambda_fake), int(every))
 
 
 def cr_state_set(state, lambda_real, lambda_fake, every):
     """Rewrite the weights and every between steps; the counters stay (a recorded step reads the record)."""
-    _lib.check(_lib.load().srgan_cr_state_set(_ptr(state), float(lambda_real), float(lambda_fake), int(every), _stream()), "cr_state_set")
+    _record_call("cr_state_set", state, float(lambda_real), float(lambda_fake), int(every))
 
 
 def cr_state_set_updates(state, updates):
     """Write the count of penalised updates between steps (resume from a checkpoint); everything else stays."""
-    _lib.check(_lib.load().srgan_cr_state_set_updates(_ptr(state), int(updates), _stream()), "cr_state_set_updates")
+    _record_call("cr_state_set_updates", state, int(updates))
 
 
 def cr_state_read(state):
     """The record as a dict; synchronises the current stream."""
-    torch.cuda.current_stream(state.device).synchronize()
-    lr, lf, every, cr_real, cr_fake, updates = struct.unpack("ffiffi", state.cpu().numpy().tobytes()[:24])
-    return dict(lambda_real=lr, lambda_fake=lf, every=every, cr_real=cr_real, cr_fake=cr_fake, updates=updates)
+    return _record_read(_lib.CrState, state)
 
 
 class _DLossesCrFn(Function):
@@ -2942,28 +2965,22 @@ MS_CHUNK = 4096                # kMsChunk of csrc/diversity.hip: floats of one r
 
 def ms_state_new(device, weight, eps, tau):
     """Device-resident record {weight, eps, tau, ms, weighted, d_image, d_latent, updates}, the last five at zero."""
-    lib = _lib.load()
-    st = torch.empty(lib.srgan_ms_state_bytes(), dtype=torch.uint8, device=device)
-    _lib.check(lib.srgan_ms_state_init(_ptr(st), float(weight), float(eps), float(tau), _stream()), "ms_state_init")
-    return st
+    return _record_new(_lib.MsState, device, "ms_state_init", float(weight), float(eps), float(tau))
 
 
 def ms_state_set(state, weight, eps, tau):
     """Rewrite the settings between steps; the values and the counter stay (a recorded step reads the record)."""
-    _lib.check(_lib.load().srgan_ms_state_set(_ptr(state), float(weight), float(eps), float(tau), _stream()), "ms_state_set")
+    _record_call("ms_state_set", state, float(weight), float(eps), float(tau))
 
 
 def ms_state_restore(state, updates, ms, d_image, d_latent):
-    """Write a checkpoint's counter and last values between steps; the settings stay."""
-    _lib.check(_lib.load().srgan_ms_state_restore(_ptr(state), int(updates), float(ms), float(d_image), float(d_latent), _stream()),
-               "ms_state_restore")
+    """Write a checkpoint's counter and last values between steps; the settings (and ``weighted``, until the next loss) stay."""
+    _record_call("ms_state_restore", state, int(updates), float(ms), float(d_image), float(d_latent))
 
 
 def ms_state_read(state):
     """The record as a dict; synchronises the current stream."""
-    torch.cuda.current_stream(state.device).synchronize()
-    w, eps, tau, ms, wd, di, dz, updates = struct.unpack("fffffffi", state.cpu().numpy().tobytes()[:32])
-    return dict(weight=w, eps=eps, tau=tau, ms=ms, weighted=wd, d_image=di, d_latent=dz, updates=updates)
+    return _record_read(_lib.MsState, state)
 
 
 def _ms_rows_of(t, what):

@@ -66,7 +66,7 @@ class Adam(torch.optim.Optimizer):
     def _cohort(self, gi, params, group, steps_done):
         key = (gi,) + tuple(id(p) for p in params)
         co = self._cohorts.get(key)
-        capturing = torch.cuda.is_current_stream_capturing()
+        capturing = ops.capturing()
         if co is None or co.steps != steps_done:
             # first use, or the host-side count moved (load_state_dict / resume): (re)seed the device record
             if capturing:
@@ -132,9 +132,8 @@ class Adam(torch.optim.Optimizer):
         rows = sum(1 for g in grads if g.numel())
         chunks = sum(-(-g.numel() // ops.GRAD_GUARD_CHUNK) for g in grads)
         if guard.table is None or rows > guard.rows or chunks > guard.chunks:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("srgan_amd.optim.Adam: the gradient guard's table / workspace first appear (or grow) inside a "
-                                   "hipGraph capture -- run one eager train step with the guard enabled first")
+            ops.refuse_in_capture("srgan_amd.optim.Adam: the gradient guard's table / workspace first appear (or grow) inside a "
+                                  "hipGraph capture -- run one eager train step with the guard enabled first")
             if guard.table is not None:
                 ops.bump_structure_epoch()       # a captured step points at the buffers being replaced
             guard.rows, guard.chunks = max(rows, guard.rows), max(chunks, guard.chunks)
@@ -172,8 +171,7 @@ class Adam(torch.optim.Optimizer):
         forgotten, so the next ``step()`` seeds fresh device records at the loaded counts with the loaded hyper-parameters (a
         recording that points at the old ones is dropped by its owner: ``ops.bump_structure_epoch``).  Between steps only.  A
         parameter without saved state stays without state; the gradient guard is not part of the dict and stays as it is."""
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("srgan_amd.optim.Adam: load_state_dict inside a hipGraph capture")
+        ops.refuse_in_capture("srgan_amd.optim.Adam: load_state_dict inside a hipGraph capture")
         super().load_state_dict(state_dict)
         for group in self.param_groups:
             group["betas"] = tuple(float(b) for b in group["betas"])
@@ -200,8 +198,7 @@ class Adam(torch.optim.Optimizer):
         module docstring.  Between steps only; a hipGraph recording of the step made before is dropped by its owner
         (``grad_guard_fingerprint``).  Enabling again re-creates the record (counters at zero)."""
         max_norm = _check_max_norm(max_norm)
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("srgan_amd.optim.Adam: gradient guard enabled inside a hipGraph capture -- enable it between steps")
+        ops.refuse_in_capture("srgan_amd.optim.Adam: gradient guard enabled inside a hipGraph capture -- enable it between steps")
         params = [p for g in self.param_groups for p in g["params"]]
         if not params or params[0].device.type != "cuda":
             raise RuntimeError("srgan_amd.optim.Adam: the gradient guard is a HIP kernel; the parameters are not on the GPU "
@@ -212,7 +209,7 @@ class Adam(torch.optim.Optimizer):
         return self
 
     def disable_grad_guard(self):
-        if self._guard is not None and torch.cuda.is_current_stream_capturing():
+        if self._guard is not None and ops.capturing():
             raise RuntimeError("srgan_amd.optim.Adam: gradient guard disabled inside a hipGraph capture")
         self._guard = None
 
@@ -226,8 +223,7 @@ class Adam(torch.optim.Optimizer):
         from there and stays valid."""
         guard = self._need_guard("set_max_norm")
         max_norm = _check_max_norm(max_norm)
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("srgan_amd.optim.Adam: max_norm changed inside a hipGraph capture")
+        ops.refuse_in_capture("srgan_amd.optim.Adam: max_norm changed inside a hipGraph capture")
         ops.grad_guard_state_set_max_norm(guard.state, max_norm)
         guard.max_norm = max_norm
 
@@ -235,8 +231,7 @@ class Adam(torch.optim.Optimizer):
         """Resume: write a checkpoint's cumulative counters into the device record, between steps; the threshold and the last
         step's decision stay."""
         guard = self._need_guard("set_grad_guard_counters")
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("srgan_amd.optim.Adam: guard counters written inside a hipGraph capture")
+        ops.refuse_in_capture("srgan_amd.optim.Adam: guard counters written inside a hipGraph capture")
         ops.grad_guard_state_set_counters(guard.state, steps, skipped, clipped)
 
     def grad_guard_stats(self):

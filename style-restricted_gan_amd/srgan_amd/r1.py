@@ -25,10 +25,6 @@ from .ops import ACT_LRELU, ACT_NONE, PAD_REFLECT, PAD_ZERO
 __all__ = ["R1Penalty", "r1_accumulate"]
 
 
-def _capturing():
-    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-
-
 def check_gamma_every(gamma, every, what="R1Penalty"):
     """-> (float gamma, int every); ValueError for gamma < 0 (or not finite), every < 1 or not an integer."""
     try:
@@ -50,10 +46,12 @@ def schedule(k, every):
     return [i % every == 0 for i in range(k)]
 
 
-class R1Penalty:
+class R1Penalty(ops.RecordOwner):
     """``gamma``, ``every`` (lazy regularisation: the caller penalises every ``every``-th update, with ``gamma_eff = gamma *
     every``) and the device side of the penalty: the record, the constant seed tensors (``1 / P_s`` per head) and the partial-sum
     workspace, made at the first use of a batch geometry -- never inside a hipGraph capture."""
+
+    layout = _lib.R1State
 
     def __init__(self, gamma=10.0, every=1):
         self.gamma, self.every = check_gamma_every(gamma, every)
@@ -64,14 +62,10 @@ class R1Penalty:
     # -- device side -----------------------------------------------------------------------------------------------------------
     def _ensure(self, device, n):
         if self.state is None:
-            if _capturing():
-                raise RuntimeError("R1Penalty: the device record would be allocated inside a hipGraph capture; run one eager "
-                                   "step first")
-            self.state = ops.r1_state_new(device, self.gamma, self.every, n)
+            self._make_record(ops.r1_state_new, device, self.gamma, self.every, n)
             self._n = n
         elif self._n != n:
-            if _capturing():
-                raise RuntimeError("R1Penalty: the batch size changed inside a hipGraph capture; run one eager step first")
+            ops.refuse_in_capture("R1Penalty: the batch size changed inside a hipGraph capture; run one eager step first")
             ops.r1_state_set(self.state, self.gamma, self.every, n)
             self._n = n
 
@@ -79,9 +73,8 @@ class R1Penalty:
         key = (n, h, w)
         hit = self._bufs.get(key)
         if hit is None:
-            if _capturing():
-                raise RuntimeError("R1Penalty: workspaces of a new batch geometry would be allocated inside a hipGraph capture; "
-                                   "run one eager step first")
+            ops.refuse_in_capture("R1Penalty: workspaces of a new batch geometry would be allocated inside a hipGraph capture; "
+                                  "run one eager step first")
             ws = torch.empty(ops.r1_workspace_bytes(n, h, w), dtype=torch.uint8, device=device)
             seeds = []
             for ho, wo in head_hw:
@@ -93,16 +86,14 @@ class R1Penalty:
         """A new ``gamma`` (>= 0), written into the device record between steps: a recorded step reads it from there."""
         self.gamma, _ = check_gamma_every(gamma, self.every, "set_r1_gamma")
         if self.state is not None:
-            if _capturing():
-                raise RuntimeError("set_r1_gamma inside a hipGraph capture")
+            ops.refuse_in_capture("set_r1_gamma inside a hipGraph capture")
             ops.r1_state_set(self.state, self.gamma, self.every, self._n)
 
     def set_updates(self, updates, device=None, n=None):
         """Resume: write a checkpoint's count of penalised updates into the device record, between steps.  A penalty that has not
         run yet has no record; it is made here for batch size ``n`` on ``device`` (the step re-derives ``c`` should its batch
         differ).  Without a record and without ``n`` only a count of 0 can be taken: that is what a fresh record starts at."""
-        if _capturing():
-            raise RuntimeError("R1Penalty: updates written inside a hipGraph capture")
+        ops.refuse_in_capture("R1Penalty: updates written inside a hipGraph capture")
         updates = int(updates)
         if updates < 0:
             raise ValueError(f"R1Penalty: updates must be >= 0, got {updates}")
@@ -120,7 +111,7 @@ class R1Penalty:
 
     def penalty(self):
         """The last penalty as a device scalar (a copy of the record's field; no synchronisation)."""
-        return self.state.view(torch.float32)[3].clone()
+        return self._record_field("penalty")
 
     def stats(self):
         """The record as a dict (``gamma``, ``every``, ``c``, ``penalty``, ``mean_sq_norm``, ``updates``, ``n``); SYNCHRONISES."""
@@ -130,7 +121,7 @@ class R1Penalty:
 
     # -- hipGraph support -------------------------------------------------------------------------------------------------------
     def graph_keepalive(self):
-        out = [self.state] if self.state is not None else []
+        out = super().graph_keepalive()
         for ws, seeds in self._bufs.values():
             out += [ws] + list(seeds)
         return out
@@ -138,7 +129,7 @@ class R1Penalty:
     def fingerprint(self):
         """What a recording bakes in: the object, ``every`` (the schedule and the launches), the record and the buffers.  Not
         ``gamma``: it is device state."""
-        return (id(self), self.every, self.state.data_ptr() if self.state is not None else 0, self._n,
+        return (id(self), self.every, self._record_ptr(), self._n,
                 tuple((k, ws.data_ptr(), tuple(s.data_ptr() for s in seeds)) for k, (ws, seeds) in sorted(self._bufs.items())))
 
 

@@ -47,10 +47,6 @@ def find(net):
     return [(name, m.__dict__[_ATTR]) for name, m in net.named_modules() if _ATTR in m.__dict__]
 
 
-def _capturing():
-    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-
-
 class SpectralNorm:
     """Table, workspace and buffers of one marked network."""
 
@@ -108,8 +104,7 @@ class SpectralNorm:
     def _ensure(self):
         """A ``.to()`` / ``.data =`` that moved a tensor the table points at: rebuild it (never inside a capture)."""
         if self._ptrs != self._pointers():
-            if _capturing():
-                raise RuntimeError("spectral_norm: a tensor of a marked layer moved inside a hipGraph capture")
+            ops.refuse_in_capture("spectral_norm: a tensor of a marked layer moved inside a hipGraph capture")
             ops.bump_structure_epoch()
             self._build()
             self._dirty = True
@@ -129,8 +124,7 @@ class SpectralNorm:
     def flush(self):
         """After a state dict was loaded: sigma and ``weight`` from the loaded (weight_orig, u, v) without iterating, and the
         cached packed operands of ``weight`` re-packed (a recorded step replays without looking at the cache)."""
-        if _capturing():
-            raise RuntimeError("spectral_norm: a state dict was loaded inside a hipGraph capture")
+        ops.refuse_in_capture("spectral_norm: a state dict was loaded inside a hipGraph capture")
         self.refresh(iterate=False)
         ops.refresh_packed(self.leaves, force=True)
 
@@ -183,8 +177,7 @@ class SpectralNorm:
         return [p for p in params if id(p) not in self.orig_ids] + self.leaves
 
     def remove(self):
-        if _capturing():
-            raise RuntimeError("remove_spectral_norm inside a hipGraph capture")
+        ops.refuse_in_capture("remove_spectral_norm inside a hipGraph capture")
         self._ensure()
         for h in self._hooks:
             h.remove()
@@ -216,8 +209,7 @@ def spectral_norm(net, n_power_iterations=1, eps=1e-12):
         raise ValueError("spectral_norm: n_power_iterations must be >= 1")
     if not float(eps) > 0.0:
         raise ValueError("spectral_norm: eps must be > 0")
-    if _capturing():
-        raise RuntimeError("spectral_norm: applied inside a hipGraph capture -- apply it between steps")
+    ops.refuse_in_capture("spectral_norm: applied inside a hipGraph capture -- apply it between steps")
     if find(net) or any(hasattr(m, "weight_orig") for m in net.modules()):
         raise RuntimeError("spectral_norm: this network (or a part of it) is marked already; remove_spectral_norm first")
     bad = [n for n, m in net.named_modules() if isinstance(m, (_ConvTranspose2d, _Linear, nn.ConvTranspose2d, nn.Linear))]
