@@ -17,6 +17,7 @@
 // The loss kernel keeps the default fp contraction of losses.hip, and the front rows' statements are d_losses_kernel's own: with both
 // weights 0 its vals[0..3], d_o and dz of the front rows are that kernel's bits (tests/test_cr_kernels_gpu.py holds it to that).
 #include "common.h"
+#include "prof.h"
 #include "loss_math.h"
 #include "records.h"
 #include <algorithm>
@@ -272,10 +273,9 @@ extern "C" int srgan_cr_pairs_fwd(const float* x0, int n0, const float* x1, int 
   const long long items = 2LL * n * nitem;
   const int vec = (bits & 15) == 0 && (3LL * w) % 4 == 0;
   hipStream_t st = as_stream(stream);
-  ProfToken tok = prof_begin(40, 0.0, st);
+  ProfScope scope(PROF_CR_PAIRS, 0.0, st);
   hipLaunchKernelGGL(cr_pairs_kernel, dim3((unsigned)std::min<long long>(items, kCrGridCap)), dim3(256), 0, st, x0, n0, x1, n, table, y,
                      h, w, flags, nitem, items, vec);
-  prof_end(tok, st);
   return check_launch("cr_pairs_kernel");
 }
 
@@ -332,7 +332,7 @@ extern "C" int srgan_d_losses_cr(const float* const* o, const long long* per_row
                   "d_losses_cr: class head needs dz, labels, <= 16 classes");
   }
   hipStream_t st = as_stream(stream);
-  ProfToken tok = prof_begin(41, 0.0, st);
+  ProfScope scope(PROF_D_LOSSES_CR, 0.0, st);
   if (gan_kind == SRGAN_CRIT_MSE && class_kind == SRGAN_CRIT_MSE)
     hipLaunchKernelGGL((d_losses_cr_kernel<CRIT_MSE, CRIT_MSE>), dim3(1), dim3(256), 0, st, p);
   else if (gan_kind == SRGAN_CRIT_MSE)
@@ -341,6 +341,5 @@ extern "C" int srgan_d_losses_cr(const float* const* o, const long long* per_row
     hipLaunchKernelGGL((d_losses_cr_kernel<CRIT_BCE, CRIT_MSE>), dim3(1), dim3(256), 0, st, p);
   else
     hipLaunchKernelGGL((d_losses_cr_kernel<CRIT_BCE, CRIT_BCE>), dim3(1), dim3(256), 0, st, p);
-  prof_end(tok, st);
   return check_launch("d_losses_cr_kernel");
 }

@@ -28,7 +28,8 @@
 // [n tile][quarter][tap][chunk of the quarter][BN][32], kind 1 = taps rotated by 180 degrees with O and I swapped (conv_wino.hip: variant 4).
 #include <algorithm>
 #include <cstdlib>
-#include "common.h"
+#include "conv.h"
+#include "prof.h"
 #include "pack_device.h"
 
 namespace srgan {
@@ -430,7 +431,7 @@ __global__ __launch_bounds__(256) void halo16r_kernel(Halo16Params p) {
 // nine taps, the x fragment of (tap, K step) is the same read shifted by (ty * 34 + tx) halo pixels -- no staging per tap.
 // 72 MFMAs per wave and patch against 84 KB of fp32 input per workgroup; the next patch's 22 loads per thread are in flight
 // during the products (double-buffered LDS, one barrier per patch).  Split-K over patch ranges into [split][O][9 C] slabs, summed
-// by wgrad_reduce_kernel (conv_igemm.hip) like every other weight-gradient kernel.
+// by wgrad_reduce_kernel (conv_wgrad.hip) like every other weight-gradient kernel.
 struct Halo16WgradParams {
   const void* x;      // [NB][H][W][C] fp32, or bf16 (X16)
   const void* dy;     // [NB][H][W][O] fp32, or bf16 (D16)
@@ -592,7 +593,7 @@ __global__ __launch_bounds__(256) void halo16_wgrad_kernel(Halo16WgradParams p) 
 //     of a patch are read once and reused by the eight taps; 32 MFMAs per wave and patch, the next patch's 16 loads per thread
 //     in flight under them (double-buffered LDS, one barrier per patch);
 //   * split-K over patch ranges into [split][O][16 C] slabs (tap-major columns, as every weight-gradient kernel), summed by the
-//     deterministic slab reduce of conv_igemm.hip.
+//     deterministic slab reduce of conv_wgrad.hip.
 struct Halo16S2WgradParams {
   const void* x;      // [NB][2 Ho][2 Wo][C] fp32, or bf16 (X16)
   const void* dy;     // [NB][Ho][Wo][O] fp32, or bf16 (D16)
@@ -1232,11 +1233,10 @@ int halo16_run(const srgan_conv_desc* d, int kind, const void* src, const void* 
   p.tiles_y = d->Hi / 4; p.tiles_x = d->Wi / 32; p.n_tiles = 1; p.act = act; p.slope = slope;
   const long long grid = (long long)p.NB * p.tiles_y * p.tiles_x * p.n_tiles;
   SRGAN_REQUIRE(grid > 0 && grid < (1LL << 31), "halo16: grid");
-  ProfToken tok = prof_begin(24, flops, st);
+  ProfScope scope(PROF_HALO16, flops, st);
   if (d->I == 256) launch_r(p, in16, out16, grid, st);
   else if (d->I == 128) launch_c<128>(p, in16, out16, grid, st);
   else launch_c<64>(p, in16, out16, grid, st);
-  prof_end(tok, st);
   return check_launch("halo16_kernel");
 }
 
@@ -1259,7 +1259,7 @@ int halo16t_run(const srgan_conv_desc* d, const void* dy, const void* packed, vo
   p.NB = d->N; p.Hs = d->Ho; p.Ws = d->Wo; p.tiles_y = d->Ho / 4; p.tiles_x = d->Wo / 32;
   const long long grid = (long long)p.NB * p.tiles_y * p.tiles_x;
   SRGAN_REQUIRE(grid > 0 && grid < (1LL << 31), "halo16t: grid");
-  ProfToken tok = prof_begin(27, flops, st);
+  ProfScope scope(PROF_HALO16T, flops, st);
 #define SRGAN_H16T(C_, N_)                                                                                            \
   do {                                                                                                                \
     if (in16 && out16) hipLaunchKernelGGL((halo16t_kernel<C_, N_, true, true>), dim3((unsigned)grid), dim3(256), 0, st, p);        \
@@ -1270,7 +1270,6 @@ int halo16t_run(const srgan_conv_desc* d, const void* dy, const void* packed, vo
   if (d->O == 256) SRGAN_H16T(256, 128);
   else SRGAN_H16T(128, 64);
 #undef SRGAN_H16T
-  prof_end(tok, st);
   return check_launch("halo16t_kernel");
 }
 
@@ -1293,7 +1292,7 @@ int halo16s_run(const srgan_conv_desc* d, const void* x, const void* packed, con
   p.NB = d->N; p.Ho = d->Ho; p.Wo = d->Wo; p.tiles_y = d->Ho / 4; p.tiles_x = d->Wo / 32; p.act = act; p.slope = slope;
   const long long grid = (long long)p.NB * p.tiles_y * p.tiles_x;
   SRGAN_REQUIRE(grid > 0 && grid < (1LL << 31), "halo16s: grid");
-  ProfToken tok = prof_begin(29, flops, st);
+  ProfScope scope(PROF_HALO16S, flops, st);
 #define SRGAN_H16S(C_, N_)                                                                                            \
   do {                                                                                                                \
     if (in16 && out16) hipLaunchKernelGGL((halo16s_kernel<C_, N_, true, true>), dim3((unsigned)grid), dim3(256), 0, st, p);        \
@@ -1304,7 +1303,6 @@ int halo16s_run(const srgan_conv_desc* d, const void* x, const void* packed, con
   if (d->I == 64) SRGAN_H16S(64, 128);
   else SRGAN_H16S(128, 256);
 #undef SRGAN_H16S
-  prof_end(tok, st);
   return check_launch("halo16s_kernel");
 }
 
@@ -1365,7 +1363,7 @@ int halo16_wgrad_run(const srgan_conv_desc* d, const void* x, const void* dy, fl
     Halo16S2WgradParams q{};
     halo16s2_wgrad_plan(d, &q);
     q.x = x; q.dy = dy; q.slab = slab;
-    ProfToken tok = prof_begin(26, flops, st);
+    ProfScope scope(PROF_HALO16S2_WGRAD, flops, st);
     const dim3 grid((unsigned)(q.o_tiles * q.c_tiles * q.splits));
 #define SRGAN_S2W(PW_)                                                                                             \
   do {                                                                                                                \
@@ -1378,19 +1376,17 @@ int halo16_wgrad_run(const srgan_conv_desc* d, const void* x, const void* dy, fl
     else if (d->Wo == 16) SRGAN_S2W(16);
     else SRGAN_S2W(8);
 #undef SRGAN_S2W
-    prof_end(tok, st);
     return check_launch("halo16s2_wgrad_kernel");
   }
+  SRGAN_REQUIRE(!x16 || d16, "halo16 wgrad: bf16 x with fp32 dy is not instantiated");      // (refuse before the bracket opens)
   Halo16WgradParams p{};
   halo16_wgrad_plan(d, &p);
   p.x = x; p.dy = dy; p.slab = slab;
-  ProfToken tok = prof_begin(25, flops, st);
+  ProfScope scope(PROF_HALO16_WGRAD, flops, st);
   const dim3 grid((unsigned)(p.o_tiles * p.c_tiles * p.splits));
   if (!x16 && !d16) hipLaunchKernelGGL((halo16_wgrad_kernel<false, false>), grid, dim3(256), 0, st, p);
   else if (!x16 && d16) hipLaunchKernelGGL((halo16_wgrad_kernel<false, true>), grid, dim3(256), 0, st, p);
-  else if (x16 && d16) hipLaunchKernelGGL((halo16_wgrad_kernel<true, true>), grid, dim3(256), 0, st, p);
-  else { set_error("halo16 wgrad: bf16 x with fp32 dy is not instantiated"); return -1; }
-  prof_end(tok, st);
+  else hipLaunchKernelGGL((halo16_wgrad_kernel<true, true>), grid, dim3(256), 0, st, p);
   return check_launch("halo16_wgrad_kernel");
 }
 

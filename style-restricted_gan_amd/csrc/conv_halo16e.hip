@@ -15,7 +15,8 @@
 // Filter operand: the register image written by pack_weights_store (pack_device.h, PackParams::regimg):
 // [K step = (quarter * 9 + tap) * 4 + s][64-channel block of N][32-channel half][lane][8 bf16] -- 1 KB contiguous per fragment.
 #include <algorithm>
-#include "common.h"
+#include "conv.h"
+#include "prof.h"
 
 namespace srgan {
 namespace {
@@ -267,12 +268,11 @@ int halo16e_run(Halo16eParams p, double flops, hipStream_t st) {
   p.n_tiles = p.N / nwg;
   const long long grid = (long long)p.NB * p.tiles_y * p.tiles_x * p.n_tiles;
   SRGAN_REQUIRE(grid > 0 && grid < (1LL << 31), "halo16e: grid");
-  ProfToken tok = prof_begin(36, flops, st);      // (the profile slot of the implicit GEMM it replaces on these layers)
+  ProfScope scope(PROF_IGEMM16, flops, st);      // (the profile slot of the implicit GEMM it replaces on these layers)
   if (p.Cs == 64 && p.N == 64) launch_e<64, 4, 1>(p, (unsigned)grid, st);
   else if (p.Cs == 64) launch_e<64, 2, 2>(p, (unsigned)grid, st);
   else if (p.N == 128) launch_e<128, 2, 2>(p, (unsigned)grid, st);
   else launch_e<128, 1, 4>(p, (unsigned)grid, st);
-  prof_end(tok, st);
   return check_launch("halo16e_kernel");
 }
 

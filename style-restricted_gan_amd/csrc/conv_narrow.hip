@@ -9,7 +9,7 @@
 //   narrow_conv_wgrad  thread = (channel of the 16-chunk, tap group); accumulates dW over all tiles of its slice
 //                      in registers and writes one slab that wgrad_reduce_kernel sums (deterministic)
 #include <algorithm>
-#include "common.h"
+#include "conv.h"
 
 namespace srgan {
 
@@ -390,7 +390,7 @@ int narrow_fwd_packed(const srgan_conv_desc* d, const float* x, const float* wp,
   return check_launch("narrow_conv_fwd_kernel");
 }
 
-// One phase image of a stride-2 input gradient (conv_igemm.hip, narrow_s2_*): the generic kernel with separate row / column
+// One phase image of a stride-2 input gradient (conv_dispatch.hip, narrow_s2_*): the generic kernel with separate row / column
 // padding and its output pixels scattered with stride 2 into the Hd x Wd destination.  wp from narrow_pack(f, ...).
 int narrow_fwd_strided(const srgan_conv_desc* f, int pad_x, const float* x, const float* wp, float* y, int Hd, int Wd, int oy_off,
                        int ox_off, hipStream_t st) {

@@ -15,7 +15,8 @@
 //   * an accumulator lane is an output CHANNEL: every store instruction writes 2 pixels x 32 contiguous channels.
 #include <algorithm>
 #include <cstdlib>
-#include "common.h"
+#include "conv.h"
+#include "prof.h"
 
 namespace srgan {
 
@@ -266,7 +267,7 @@ __global__ void rgbin_pack_kernel(const float* w, float* dst, long long sO, long
 // the B fragment of (pixel, tap) is halo[pixel base (immediate) + tap offset (one register per 32-tap tile)]; the A fragment
 // (32 channels of two pixels) comes straight from global memory, 128 contiguous bytes per pixel, reloaded in place one
 // 32-pixel row ahead.  Every wave accumulates ALL 2 x 5 output tiles (160 registers) over its two rows of each tile; at
-// the end the eight partial results meet in LDS and one slab per workgroup goes to the split-K reduce of conv_igemm.hip.
+// the end the eight partial results meet in LDS and one slab per workgroup goes to the split-K reduce of conv_wgrad.hip.
 struct RgbWgradParams {
   const float* c64;   // [NB][H][W][64]
   const float* t3;    // [NB][H][W][3]
@@ -406,7 +407,7 @@ __global__ __launch_bounds__(512) void rgb_wgrad_kernel(RgbWgradParams p) {
 //   * the 3-channel tensor's (4 + 6) x (32 + 6) pixel halo is parked as bf16 [row][column][3]; the B fragment of (tap, 16 pixels) is
 //     eight 2-byte reads at  pixel base + tap offset + 3 j  (a lane = a tap, as in the fp32 kernel);
 //   * wave w owns patch row w: 2 K steps x (2 x 5) products per patch, all 2 x 5 output tiles in 160 accumulator registers; at the
-//     end the four partial results meet in LDS and one slab per workgroup goes to the split-K sum of conv_igemm.hip.
+//     end the four partial results meet in LDS and one slab per workgroup goes to the split-K sum of conv_wgrad.hip.
 struct RgbWgrad16Params {
   const void* c64;    // [NB][H][W][64] fp32, or bf16 (C16)
   const float* t3;    // [NB][H][W][3]
@@ -618,7 +619,7 @@ int rgb_wgrad_run(const srgan_conv_desc* d, const void* x, const void* dy, float
   p.ntiles = p.NB * p.tiles_x * p.tiles_y;
   int splits, cd, nn;
   rgb_wgrad_slab(d, &splits, &cd, &nn);
-  ProfToken tok = prof_begin(21, 2.0 * d->N * d->Ho * d->Wo * (double)d->O * d->kh * d->kw * d->I, st);
+  ProfScope scope(PROF_RGB_WGRAD, 2.0 * d->N * d->Ho * d->Wo * (double)d->O * d->kh * d->kw * d->I, st);
   if (rgb_wgrad16_on()) {
     RgbWgrad16Params q{};
     q.c64 = kind == 0 ? dy : x; q.t3 = p.t3; q.slab = slab;
@@ -632,7 +633,6 @@ int rgb_wgrad_run(const srgan_conv_desc* d, const void* x, const void* dy, float
     else hipLaunchKernelGGL((rgb_wgrad16_kernel<1, false>), dim3((unsigned)splits), dim3(256), 0, st, q);
   } else if (kind == 0) hipLaunchKernelGGL(rgb_wgrad_kernel<0>, dim3((unsigned)splits), dim3(512), 0, st, p);
   else hipLaunchKernelGGL(rgb_wgrad_kernel<1>, dim3((unsigned)splits), dim3(512), 0, st, p);
-  prof_end(tok, st);
   return check_launch("rgb_wgrad_kernel");
 }
 
@@ -682,7 +682,7 @@ int rgbin_run(const srgan_conv_desc* d, const float* x, const float* packed, con
   p.act = act; p.slope = slope;
   const long long grid = (long long)p.tiles_x * p.tiles_y * p.o_blocks * d->N;
   SRGAN_REQUIRE(grid < (1LL << 31), "rgb-input conv: grid too large");
-  ProfToken tok = prof_begin(20, 2.0 * d->N * d->Ho * d->Wo * (double)d->O * d->kh * d->kw * d->I, st);
+  ProfScope scope(PROF_RGBIN_CONV, 2.0 * d->N * d->Ho * d->Wo * (double)d->O * d->kh * d->kw * d->I, st);
   if (rgbin16_mode(d)) {
     Rgbin16Params q{};
     q.x = x; q.wp = reinterpret_cast<const unsigned short*>(packed); q.bias = bias; q.y = y;
@@ -690,13 +690,11 @@ int rgbin_run(const srgan_conv_desc* d, const float* x, const float* packed, con
     q.tiles_x = p.tiles_x; q.tiles_y = p.tiles_y; q.o_blocks = p.o_blocks; q.act = act; q.slope = slope;
     if (dst16) hipLaunchKernelGGL(rgbin16_conv_kernel<true>, dim3((unsigned)grid), dim3(512), 0, st, q);
     else hipLaunchKernelGGL(rgbin16_conv_kernel<false>, dim3((unsigned)grid), dim3(512), 0, st, q);
-    prof_end(tok, st);
     return check_launch("rgbin16_conv_kernel");
   }
   if (d->stride == 2 && d->kh == 4) hipLaunchKernelGGL((rgbin_conv_kernel<4, 4, 3, 2>), dim3((unsigned)grid), dim3(512), 0, st, p);
   else if (d->stride == 2) hipLaunchKernelGGL((rgbin_conv_kernel<7, 7, 3, 2>), dim3((unsigned)grid), dim3(512), 0, st, p);
   else hipLaunchKernelGGL((rgbin_conv_kernel<7, 7, 3>), dim3((unsigned)grid), dim3(512), 0, st, p);
-  prof_end(tok, st);
   return check_launch("rgbin_conv_kernel");
 }
 

@@ -2,7 +2,7 @@
 // (pyfiles/model.py:232, 247-248: conv7(64 -> 3) before tanh) and -- with the flipped, transposed filter -- the input gradient of
 // its 7x7 RGB input layer (model.py:212).  Round 3.
 //
-// Every 32-wide MFMA formulation pads the 3 output channels to 32 (the 7x1 row convolution + shift-add of conv_igemm.hip gets to
+// Every 32-wide MFMA formulation pads the 3 output channels to 32 (the 7x1 row convolution + shift-add of conv_rowconv.hip gets to
 // 21 / 32 by making (cout, kx) the N index, at the price of a 21-float-per-pixel intermediate through HBM: 1.63 GB per launch).
 // v_mfma_f32_4x4x1_16B_f32 is the matrix instruction with a 4-wide N: 16 independent 4x4 blocks per wave,
 //     D_b[i][j] += A_b[i] * B_b[j],   A_b[i] from lane 4b + i,  B_b[j] from lane 4b + j,  D_b[i][j] in VGPR i of lane 4b + j
@@ -27,7 +27,8 @@
 // 172 us against 237 for the row convolution + shift-add, +0.6 % on the step.
 #include <algorithm>
 #include <cstdlib>
-#include "common.h"
+#include "conv.h"
+#include "prof.h"
 
 #ifndef RGBOUT_EXP
 #define RGBOUT_EXP 0
@@ -448,7 +449,7 @@ int rgbout_run(const srgan_conv_desc* d, const void* xv, const float* packed, co
   p.tiles_x = (int)ceil_div(d->Wo, RO_TC); p.tiles_y = (int)ceil_div(d->Ho, RO_TR);
   const long long grid = (long long)p.tiles_x * p.tiles_y * d->N;
   SRGAN_REQUIRE(grid < (1LL << 31), "rgb-output conv: grid too large");
-  ProfToken tok = prof_begin(28, 2.0 * d->N * d->Ho * d->Wo * (double)d->O * d->kh * d->kw * d->I, st);
+  ProfScope scope(PROF_RGBOUT_CONV, 2.0 * d->N * d->Ho * d->Wo * (double)d->O * d->kh * d->kw * d->I, st);
   if (rgbout16_mode(d)) {
     Rgbout16Params q{};
     q.x = xv; q.wp = reinterpret_cast<const unsigned short*>(packed); q.bias = bias; q.y = y;
@@ -462,11 +463,9 @@ int rgbout_run(const srgan_conv_desc* d, const void* xv, const float* packed, co
     q.exp = (int)SRGAN_AB_INT("SRGAN_RGBOUT16_EXP", 0);
     if (src16) hipLaunchKernelGGL(rgbout16_conv_kernel<true>, dim3((unsigned)(q.strips_x * q.vsplit * d->N)), dim3(512), 0, st, q);
     else hipLaunchKernelGGL(rgbout16_conv_kernel<false>, dim3((unsigned)(q.strips_x * q.vsplit * d->N)), dim3(512), 0, st, q);
-    prof_end(tok, st);
     return check_launch("rgbout16_conv_kernel");
   }
   hipLaunchKernelGGL(rgbout_conv_kernel, dim3((unsigned)grid), dim3(512), 0, st, p);
-  prof_end(tok, st);
   return check_launch("rgbout_conv_kernel");
 }
 

@@ -24,7 +24,8 @@
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
-#include "common.h"
+#include "conv.h"
+#include "prof.h"
 #include "pack_device.h"
 
 #ifndef WINO_EXP
@@ -429,7 +430,7 @@ __global__ __launch_bounds__(512) void wino_kernel(WinoParams p) {
 //   * thread = (tile of the chunk, channel): 16 + 4 buffer loads, two register transforms, 32 LDS stores laid out
 //     [pos][tile half][channel][4 tiles] so that a lane's MFMA fragment (4 consecutive K = tiles) is one 16-B slot,
 //   * epilogue: positions meet in LDS, each thread applies G^T . G and writes the 3x3 taps of its (o, i) pairs into
-//     the split-K slab [split][O][9 * I] that wgrad_reduce_kernel (conv_igemm.hip) sums.
+//     the split-K slab [split][O][9 * I] that wgrad_reduce_kernel (conv_wgrad.hip) sums.
 struct WinoWgradParams {
   const float* x;     // [NB][H][W][C]
   const float* dy;    // [NB][Ho][Wo][O]
@@ -1013,7 +1014,7 @@ int wino_run(const srgan_conv_desc* d, int kind, const float* src, const float* 
     }
     return wino42_launch(p, kind, grid, kind == 1 && mask != nullptr, conv_flops_of(d), st);
   }
-  ProfToken tok = prof_begin(variant == 1 ? 14 : 16, conv_flops_of(d), st);
+  ProfScope scope(variant == 1 ? PROF_WINO : PROF_WINO_S2, conv_flops_of(d), st);
   if (variant == 1) hipLaunchKernelGGL(wino_kernel<0>, dim3((unsigned)grid), dim3(512), 0, st, p);
   else if (kind == 0) hipLaunchKernelGGL(wino_kernel<1>, dim3((unsigned)grid), dim3(512), 0, st, p);
   else if (mask) {
@@ -1021,7 +1022,6 @@ int wino_run(const srgan_conv_desc* d, int kind, const float* src, const float* 
     if (mask_done) *mask_done = true;
     hipLaunchKernelGGL((wino_kernel<2, true>), dim3((unsigned)grid, 4), dim3(512), 0, st, p);
   } else hipLaunchKernelGGL(wino_kernel<2>, dim3((unsigned)grid, 4), dim3(512), 0, st, p);
-  prof_end(tok, st);
   return check_launch("wino_kernel");
 }
 
@@ -1112,11 +1112,10 @@ int wino_wgrad_run(const srgan_conv_desc* d, const float* x, const float* dy, fl
   SRGAN_REQUIRE(variant != 0, "winograd wgrad: layer not applicable");
   p.x = x; p.dy = dy; p.slab = slab;
   p.xcd_splits = (p.splits % 8 == 0) ? 1 : 0;
-  ProfToken tok = prof_begin(variant == 1 ? 15 : 17, conv_flops_of(d), st);   // algorithmic FLOPs, as above
+  ProfScope scope(variant == 1 ? PROF_WINO_WGRAD : PROF_WINO_S2_WGRAD, conv_flops_of(d), st);   // algorithmic FLOPs, as above
   const dim3 grid((unsigned)(p.o_tiles * p.i_tiles * p.splits));
   if (variant == 1) hipLaunchKernelGGL(wino_wgrad_kernel<0>, grid, dim3(512), 0, st, p);
   else hipLaunchKernelGGL(wino_wgrad_kernel<1>, grid, dim3(512), 0, st, p);
-  prof_end(tok, st);
   return check_launch("wino_wgrad_kernel");
 }
 

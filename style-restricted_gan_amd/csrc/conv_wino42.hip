@@ -33,7 +33,8 @@
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
-#include "common.h"
+#include "conv.h"
+#include "prof.h"
 #include "pack_device.h"
 
 #ifndef WINO42_EXP
@@ -511,11 +512,10 @@ int wino42_launch(const WinoParams& p0, int kind, long long units, bool mask, do
   static const int cus = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
   p.ipw = kind == 1 ? (int)ceil_div(items, cus) : 1;
   const long long grid = ceil_div(items, p.ipw);
-  ProfToken tok = prof_begin(37, flops, st);
+  ProfScope scope(PROF_WINO42, flops, st);
   if (kind == 0) hipLaunchKernelGGL((wino42_kernel<1>), dim3((unsigned)grid), dim3(512), 0, st, p);
   else if (mask) hipLaunchKernelGGL((wino42_kernel<2, true>), dim3((unsigned)grid), dim3(512), 0, st, p);
   else hipLaunchKernelGGL((wino42_kernel<2>), dim3((unsigned)grid), dim3(512), 0, st, p);
-  prof_end(tok, st);
   return check_launch("wino42_kernel");
 }
 

@@ -21,7 +21,8 @@
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
-#include "common.h"
+#include "conv.h"
+#include "prof.h"
 #include "pack_device.h"
 
 namespace srgan {
@@ -226,10 +227,9 @@ __global__ __launch_bounds__(256, 2) void in_fwd_slab_v16_kernel(const float* __
 int in_fwd_slab_v_launch(const float* x, const float* scale, const float* shift, float* mean, float* rstd, float* vimg, int N,
                          int C, float eps, int act, float slope, hipStream_t st) {
   // algorithmic bytes: the 32 x 32 x C tensor read once, its transform image (2.25x) written once
-  ProfToken tok = prof_begin(38, 3.25 * 4.0 * N * 1024.0 * C, st);
+  ProfScope scope(PROF_IN_FWD_SLAB_V, 3.25 * 4.0 * N * 1024.0 * C, st);
   hipLaunchKernelGGL(in_fwd_slab_v16_kernel, dim3((unsigned)(N * (C / 16))), dim3(256), 0, st, x, scale, shift, mean, rstd, vimg, N,
                        C, eps, act, slope);
-  prof_end(tok, st);
   return check_launch("in_fwd_slab_v_kernel");
 }
 
@@ -361,10 +361,9 @@ int in_bwd_slab_vz_launch(const float* x, const float* gup, const float* scale, 
                           const float* rstd, float* dscale, float* dshift, float* vimg, float* zimg, int N, int C, int act,
                           float slope, hipStream_t st) {
   // algorithmic bytes: x and the upstream gradient read once, both transform images (2.25x each) written once
-  ProfToken tok = prof_begin(39, 6.5 * 4.0 * N * 1024.0 * C, st);
+  ProfScope scope(PROF_IN_BWD_SLAB_VZ, 6.5 * 4.0 * N * 1024.0 * C, st);
   hipLaunchKernelGGL(in_bwd_slab_vz_kernel, dim3((unsigned)(N * (C / 16))), dim3(256), 0, st, x, gup, scale, shift, mean, rstd, dscale,
                      dshift, vimg, zimg, N, C, act, slope);
-  prof_end(tok, st);
   return check_launch("in_bwd_slab_vz_kernel");
 }
 
@@ -808,15 +807,13 @@ int wino43_launch(const WinoParams& p, float* vimg, long long grid, double flops
   // SRGAN_W43_ONLY=1 / 2 (timing experiments only): launch just the input transform / just the multiply kernel
   static const int only = SRGAN_AB_INT("SRGAN_W43_ONLY", 0);
   if (only != 2 && !v_ready) {      // v_ready: the caller's V image already holds B^T d B (in_fwd_slab_v_kernel wrote it)
-    ProfToken tok = prof_begin(19, 0.0, st);
+    ProfScope scope(PROF_WINO43_INPUT, 0.0, st);
     hipLaunchKernelGGL(wino43_input_kernel, dim3((unsigned)(p.m_tiles * (p.C / 32))), dim3(512), 0, st, p, vimg);
-    prof_end(tok, st);
   }
   if (only != 1) {
-    ProfToken tok = prof_begin(18, flops, st);
+    ProfScope scope(PROF_WINO43, flops, st);
     if (p.res) hipLaunchKernelGGL(wino43_kernel<true>, dim3((unsigned)grid), dim3(512), 0, st, p, (const float*)vimg);
     else hipLaunchKernelGGL(wino43_kernel<false>, dim3((unsigned)grid), dim3(512), 0, st, p, (const float*)vimg);
-    prof_end(tok, st);
   }
   return 0;
 }
@@ -828,17 +825,15 @@ int wino43_wgrad_launch(const Wino43WgradGeom& g, const float* vimg, const float
   q.dy = dy; q.zimg = zimg; q.NB = g.NB; q.H = g.H; q.W = g.W; q.O = g.O; q.TH = g.H / 4; q.TW = g.W / 4;
   q.T = g.NB * q.TH * q.TW; q.ntc = g.ntc; q.o_blocks = g.O / 32;
   if (!z_ready) {      // z_ready: in_bwd_slab_vz_kernel already wrote Z
-    ProfToken tok = prof_begin(23, 0.0, st);
+    ProfScope scope(PROF_WINO43_DY, 0.0, st);
     hipLaunchKernelGGL(wino43_dy_kernel, dim3((unsigned)ceil_div((long long)q.ntc * q.o_blocks, 8)), dim3(512), 0, st, q);
-    prof_end(tok, st);
   }
   Wino43WgradParams p{};
   p.vimg = vimg; p.zimg = zimg; p.slab = slab; p.C = g.C; p.O = g.O; p.cchunks = g.C / 8; p.ntc = g.ntc;
   p.chunks_per_split = g.chunks_per_split; p.splits = g.splits; p.c_blocks = g.C / 64; p.o_blocks = g.O / 32;
   p.split_minor = 1;
-  ProfToken tok = prof_begin(22, flops, st);
+  ProfScope scope(PROF_WINO43_WGRAD, flops, st);
   hipLaunchKernelGGL(wino43_wgrad_kernel, dim3((unsigned)(p.o_blocks * p.c_blocks * p.splits)), dim3(512), 0, st, p);
-  prof_end(tok, st);
   return 0;
 }
 

@@ -20,6 +20,7 @@
 //
 // No atomics, plain stores, every sum has one owner and an order that depends on E, d and B only -- not on the grid.
 #include "common.h"
+#include "prof.h"
 #include "records.h"
 #include <algorithm>
 #include <cstdint>
@@ -247,10 +248,9 @@ extern "C" int srgan_ms_rows(const float* i1, const float* i2, int b, long long 
   const long long nchunk = srgan::ms_chunks(e), items = (long long)b * nchunk;
   const unsigned bx = (unsigned)std::min<long long>(items, srgan::kMsGridCap);
   hipStream_t st = as_stream(stream);
-  ProfToken tok = prof_begin(42, 8.0 * (double)b * (double)e, st);
+  ProfScope scope(PROF_MS_ROWS, 8.0 * (double)b * (double)e, st);
   hipLaunchKernelGGL(srgan::ms_rows_kernel, dim3(bx), dim3(srgan::kMsBlock), 0, st, i1, i2, static_cast<float*>(ws), (int)e,
                      (int)nchunk, items);
-  prof_end(tok, st);
   return check_launch("ms_rows_kernel");
 }
 
@@ -267,10 +267,9 @@ extern "C" int srgan_ms_finish(const void* ws, size_t ws_bytes, const float* z1,
   const char* base = static_cast<const char*>(ws);
   double* rows = reinterpret_cast<double*>(const_cast<char*>(base) + srgan::ms_part_bytes(b, e));
   hipStream_t st = as_stream(stream);
-  ProfToken tok = prof_begin(43, 0.0, st);
+  ProfScope scope(PROF_MS_FINISH, 0.0, st);
   hipLaunchKernelGGL(srgan::ms_finish_kernel, dim3(1), dim3(srgan::kMsBlock), 0, st, reinterpret_cast<const float*>(base), z1, z2,
                      rows, b, (int)e, d, (int)srgan::ms_chunks(e), form, static_cast<srgan::MsState*>(state), vals, coef);
-  prof_end(tok, st);
   return check_launch("ms_finish_kernel");
 }
 
@@ -284,9 +283,8 @@ extern "C" int srgan_ms_grad(const float* i1, const float* i2, const float* coef
   const long long nchunk = srgan::ms_chunks(e), items = (long long)b * nchunk;
   const unsigned bx = (unsigned)std::min<long long>(items, srgan::kMsGridCap);
   hipStream_t st = as_stream(stream);
-  ProfToken tok = prof_begin(44, 4.0 * (double)b * (double)e * (2.0 + (d1 ? 1.0 : 0.0) + (d2 ? 1.0 : 0.0)), st);
+  ProfScope scope(PROF_MS_GRAD, 4.0 * (double)b * (double)e * (2.0 + (d1 ? 1.0 : 0.0) + (d2 ? 1.0 : 0.0)), st);
   hipLaunchKernelGGL(srgan::ms_grad_kernel, dim3(bx), dim3(srgan::kMsBlock), 0, st, i1, i2, coef, g, d1, d2, (int)e, (int)nchunk,
                      items);
-  prof_end(tok, st);
   return check_launch("ms_grad_kernel");
 }

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "common.h"
+#include "prof.h"
 
 namespace srgan {
 
@@ -1031,23 +1032,21 @@ extern "C" int srgan_instnorm_fwd(const float* x, const float* scale, const floa
     const dim3 gs((unsigned)(C / 32), (unsigned)N);
     const int rows = (HW + 63) / 64;
 #define SRGAN_FWD_SLAB(R) hipLaunchKernelGGL(in_fwd_slab<R>, gs, dim3(512), 0, st, x, scale, shift, res, y, mean, rstd, HW, C, eps, act, slope, slab_remap())
-    ProfToken tok = prof_begin(34, (res ? 3.0 : 2.0) * tbytes, st);
+    ProfScope scope(PROF_IN_FWD_SLAB, (res ? 3.0 : 2.0) * tbytes, st);
     if (rows <= 1) SRGAN_FWD_SLAB(1);
     else if (rows <= 2) SRGAN_FWD_SLAB(2);
     else if (rows <= 4) SRGAN_FWD_SLAB(4);
     else if (rows <= 8) SRGAN_FWD_SLAB(8);
     else SRGAN_FWD_SLAB(16);
 #undef SRGAN_FWD_SLAB
-    prof_end(tok, st);
     return check_launch("instnorm_fwd (slab)");
   }
   float2* part = reinterpret_cast<float2*>(ws);
   dim3 g((C + NORM_CH - 1) / NORM_CH, S, N);
   {
-    ProfToken tok = prof_begin(30, tbytes, st);
+    ProfScope scope(PROF_IN_STATS_PARTIAL, tbytes, st);
     if ((C & 3) == 0) hipLaunchKernelGGL(in_stats_partial_v4<false>, g, dim3(256), 0, st, (const void*)x, part, HW, C, S, rps);
     else hipLaunchKernelGGL(in_stats_partial, g, dim3(256), 0, st, x, part, HW, C, S, rps);
-    prof_end(tok, st);
   }
   const long long total = (long long)N * HW * C;
   // the fused finish re-reads the shift sample x[n][pixel 0][c] in EVERY workgroup of the apply pass while workgroup 0 may
@@ -1056,10 +1055,9 @@ extern "C" int srgan_instnorm_fwd(const float* x, const float* scale, const floa
   if (pow2_fast(C, HW) && fuse_final) {
     const int hwc4 = HW * C / 4;
     dim3 g2((unsigned)apply_grid(hwc4, N), (unsigned)N);
-    ProfToken tok = prof_begin(31, (res ? 3.0 : 2.0) * tbytes, st);
+    ProfScope scope(PROF_IN_APPLY, (res ? 3.0 : 2.0) * tbytes, st);
     hipLaunchKernelGGL((in_apply_pow2<false, false>), g2, dim3(256), 0, st, (const void*)x, scale, shift, res, mean, rstd, (void*)y, hwc4, C, act, slope,
                        (const float2*)part, S, HW, eps);
-    prof_end(tok, st);
     return check_launch("instnorm_fwd");
   }
   hipLaunchKernelGGL(in_stats_final, dim3((N * C + 255) / 256), dim3(256), 0, st, x, (const float2*)part, mean, rstd, N, HW, C, S, eps);
@@ -1092,33 +1090,30 @@ extern "C" int srgan_instnorm_bwd(const float* x, const float* dy, const float* 
     const dim3 gs((unsigned)(C / 16), (unsigned)N);
     const int rows = (HW + 63) / 64;
 #define SRGAN_BWD_SLAB(R) hipLaunchKernelGGL(in_bwd_slab<R>, gs, dim3(256), 0, st, x, dy, scale, shift, mean, rstd, dx, dscale, dshift, HW, C, act, slope, slab_remap())
-    ProfToken tok = prof_begin(35, 3.0 * tbytes, st);
+    ProfScope scope(PROF_IN_BWD_SLAB, 3.0 * tbytes, st);
     if (rows <= 1) SRGAN_BWD_SLAB(1);
     else if (rows <= 2) SRGAN_BWD_SLAB(2);
     else if (rows <= 4) SRGAN_BWD_SLAB(4);
     else if (rows <= 8) SRGAN_BWD_SLAB(8);
     else SRGAN_BWD_SLAB(16);
 #undef SRGAN_BWD_SLAB
-    prof_end(tok, st);
     return check_launch("instnorm_bwd (slab)");
   }
   float2* part = reinterpret_cast<float2*>(ws);
   dim3 g((C + NORM_CH - 1) / NORM_CH, S, N);
   {
-    ProfToken tok = prof_begin(32, 2.0 * tbytes, st);
+    ProfScope scope(PROF_IN_BWD_PARTIAL, 2.0 * tbytes, st);
     if ((C & 3) == 0) hipLaunchKernelGGL((in_bwd_partial_v4<false, false>), g, dim3(256), 0, st, (const void*)x, (const void*)dy, scale, shift, mean, rstd, part, HW, C, S, rps, act, slope);
     else hipLaunchKernelGGL(in_bwd_partial, g, dim3(256), 0, st, x, dy, scale, shift, mean, rstd, part, HW, C, S, rps, act, slope);
-    prof_end(tok, st);
   }
   const long long total = (long long)N * HW * C;
   const float inv_hw = 1.f / (float)HW;
   if (pow2_fast(C, HW)) {      // (the backward's fused finish reads the partial sums only: in-place dx is an elementwise update)
     const int hwc4 = HW * C / 4;
     dim3 g2((unsigned)apply_grid(hwc4, N), (unsigned)N);
-    ProfToken tok = prof_begin(33, 3.0 * tbytes, st);
+    ProfScope scope(PROF_IN_BWD_APPLY, 3.0 * tbytes, st);
     hipLaunchKernelGGL((in_bwd_apply_pow2<false, false, false>), g2, dim3(256), 0, st, (const void*)x, (const void*)dy, scale, shift, mean, rstd, dshift, dscale, (void*)dx, hwc4, C, inv_hw, act,
                        slope, (const float2*)part, S);
-    prof_end(tok, st);
     return check_launch("instnorm_bwd");
   }
   hipLaunchKernelGGL(in_bwd_final, dim3((N * C + 255) / 256), dim3(256), 0, st, (const float2*)part, dshift, dscale, N * C, C, S);
@@ -1145,7 +1140,7 @@ extern "C" int srgan_instnorm_slab_fwd_io(const void* x, int x_bf16, const float
   hipStream_t st = as_stream(stream);
   const dim3 gs((unsigned)(C / 32), (unsigned)N);
   const double ebytes = (double)N * HW * C;
-  ProfToken tok = prof_begin(34, ebytes * ((x_bf16 ? 2 : 4) + (y_bf16 ? 2 : 4) + (res ? 4 : 0)), st);
+  ProfScope scope(PROF_IN_FWD_SLAB, ebytes * ((x_bf16 ? 2 : 4) + (y_bf16 ? 2 : 4) + (res ? 4 : 0)), st);
   if (x_bf16 || y_bf16) {
     // 16-bit tensor on a side: 8 channels per lane, 128 pixels per pass
     const int rows = (HW + 127) / 128;
@@ -1172,7 +1167,6 @@ extern "C" int srgan_instnorm_slab_fwd_io(const void* x, int x_bf16, const float
     else SRGAN_FWD_IO(16);
 #undef SRGAN_FWD_IO
   }
-  prof_end(tok, st);
   return check_launch("instnorm_slab_fwd_io");
 }
 
@@ -1185,7 +1179,7 @@ extern "C" int srgan_instnorm_slab_bwd_io(const void* x, int x_bf16, const void*
   SRGAN_REQUIRE((x_bf16 != 0) == (dx_bf16 != 0), "instnorm_slab_bwd_io: the input gradient has the input's type");
   hipStream_t st = as_stream(stream);
   const double ebytes = (double)N * HW * C;
-  ProfToken tok = prof_begin(35, ebytes * (2 * (x_bf16 ? 2 : 4) + (dy_bf16 ? 2 : 4)), st);
+  ProfScope scope(PROF_IN_BWD_SLAB, ebytes * (2 * (x_bf16 ? 2 : 4) + (dy_bf16 ? 2 : 4)), st);
   // (8 channels per lane with 32-channel slabs, as in the forward, was measured slower here: 23.4 against 15.7 us on the
   // 32 x 32 x 256 trunk -- the backward lives on two 256-thread workgroups per CU overlapping each other's phases)
   const dim3 gs((unsigned)(C / 16), (unsigned)N);
@@ -1205,7 +1199,6 @@ extern "C" int srgan_instnorm_slab_bwd_io(const void* x, int x_bf16, const void*
   else SRGAN_BWD_IO_R(false, false);
 #undef SRGAN_BWD_IO_R
 #undef SRGAN_BWD_IO
-  prof_end(tok, st);
   return check_launch("instnorm_slab_bwd_io");
 }
 
@@ -1233,22 +1226,20 @@ extern "C" int srgan_instnorm_fwd_io(const void* x, int x_bf16, const float* sca
   float2* part = reinterpret_cast<float2*>(ws);
   dim3 g((C + NORM_CH - 1) / NORM_CH, S, N);
   {
-    ProfToken tok = prof_begin(30, ebytes * (x_bf16 ? 2 : 4), st);
+    ProfScope scope(PROF_IN_STATS_PARTIAL, ebytes * (x_bf16 ? 2 : 4), st);
     if (x_bf16 && (C & 63) == 0) hipLaunchKernelGGL(in_stats_partial_v8, dim3(C / 64, S, N), dim3(256), 0, st, x, part, HW, C, S, rps);
     else if (x_bf16) hipLaunchKernelGGL(in_stats_partial_v4<true>, g, dim3(256), 0, st, x, part, HW, C, S, rps);
     else hipLaunchKernelGGL(in_stats_partial_v4<false>, g, dim3(256), 0, st, x, part, HW, C, S, rps);
-    prof_end(tok, st);
   }
   const int hwc4 = HW * C / 4;
   dim3 g2((unsigned)apply_grid(hwc4, N), (unsigned)N);
-  ProfToken tok = prof_begin(31, ebytes * ((x_bf16 ? 2 : 4) + (y_bf16 ? 2 : 4) + (res ? 4 : 0)), st);
+  ProfScope scope(PROF_IN_APPLY, ebytes * ((x_bf16 ? 2 : 4) + (y_bf16 ? 2 : 4) + (res ? 4 : 0)), st);
 #define SRGAN_APPLY_IO(A, B) hipLaunchKernelGGL((in_apply_pow2<A, B>), g2, dim3(256), 0, st, x, scale, shift, res, mean, rstd, y, hwc4, C, act, slope, (const float2*)part, S, HW, eps)
   if (x_bf16 && y_bf16) SRGAN_APPLY_IO(true, true);
   else if (x_bf16) SRGAN_APPLY_IO(true, false);
   else if (y_bf16) SRGAN_APPLY_IO(false, true);
   else SRGAN_APPLY_IO(false, false);
 #undef SRGAN_APPLY_IO
-  prof_end(tok, st);
   return check_launch("instnorm_fwd_io");
 }
 
@@ -1271,7 +1262,7 @@ extern "C" int srgan_instnorm_bwd_io(const void* x, int x_bf16, const void* dy, 
   float2* part = reinterpret_cast<float2*>(ws);
   dim3 g((C + NORM_CH - 1) / NORM_CH, S, N);
   {
-    ProfToken tok = prof_begin(32, ebytes * (xb + gb), st);
+    ProfScope scope(PROF_IN_BWD_PARTIAL, ebytes * (xb + gb), st);
 #define SRGAN_BPART_IO(A, B) hipLaunchKernelGGL((in_bwd_partial_v4<A, B>), g, dim3(256), 0, st, x, dy, scale, shift, mean, rstd, part, HW, C, S, rps, act, slope)
     if (x_bf16 && (C & 63) == 0) {
       if (dy_bf16) hipLaunchKernelGGL(in_bwd_partial_v8<true>, dim3(C / 64, S, N), dim3(256), 0, st, x, dy, scale, shift, mean, rstd, part, HW, C, S, rps, act, slope);
@@ -1281,19 +1272,17 @@ extern "C" int srgan_instnorm_bwd_io(const void* x, int x_bf16, const void* dy, 
     else if (dy_bf16) SRGAN_BPART_IO(false, true);
     else SRGAN_BPART_IO(false, false);
 #undef SRGAN_BPART_IO
-    prof_end(tok, st);
   }
   const int hwc4 = HW * C / 4;
   const float inv_hw = 1.f / (float)HW;
   dim3 g2((unsigned)apply_grid(hwc4, N), (unsigned)N);
-  ProfToken tok = prof_begin(33, ebytes * (2 * xb + gb), st);
+  ProfScope scope(PROF_IN_BWD_APPLY, ebytes * (2 * xb + gb), st);
 #define SRGAN_BAPPLY_IO(A, B) hipLaunchKernelGGL((in_bwd_apply_pow2<A, B, A>), g2, dim3(256), 0, st, x, dy, scale, shift, mean, rstd, dshift, dscale, dx, hwc4, C, inv_hw, act, slope, (const float2*)part, S)
   if (x_bf16 && dy_bf16) SRGAN_BAPPLY_IO(true, true);
   else if (x_bf16) SRGAN_BAPPLY_IO(true, false);
   else if (dy_bf16) SRGAN_BAPPLY_IO(false, true);
   else SRGAN_BAPPLY_IO(false, false);
 #undef SRGAN_BAPPLY_IO
-  prof_end(tok, st);
   return check_launch("instnorm_bwd_io");
 }
 

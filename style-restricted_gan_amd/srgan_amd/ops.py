@@ -1350,7 +1350,7 @@ class _ResBlockBf16Fn(Function):
 # gradients take the types of the tensors they belong to.  One Function (_ConvBf16Fn) serves every such convolution; a ROUTE names
 # the C entry family that runs it: the LDS-resident-patch kernels (csrc/conv_halo16.hip: halo16s / halo16t / halo16s2_wgrad with
 # IN16 / OUT16) for the generator, the implicit GEMM with 64-deep K tiles and the vector weight-gradient kernel (csrc/
-# conv_igemm.hip: igemm16_kernel; with fp32 tensors those layers are bound by their own result and by the fp32 -> bf16 conversion
+# conv_igemm.hip: igemm16_kernel, csrc/conv_wgrad.hip: wgrad_kernel<.., IO16>; with fp32 tensors those layers are bound by their own result and by the fp32 -> bf16 conversion
 # on the way into LDS, profiles/LOG.md round 4) for the encoder, whichever kernel serves the direction (srgan_conv2d_io_*) for the
 # discriminator and the RGB ends.  The norms are the instance-norm kernels with 16-bit I/O (srgan_instnorm_fwd_io / _bwd_io).
 STORAGE_BF16 = True               # tests switch it off to compare against the fp32-tensor chain

@@ -91,6 +91,25 @@ def test_invalid_arguments_are_reported_without_a_gpu(built_lib):
         assert lib.srgan_set_compute_mode(0) == 0
 
 
+def test_launch_timer_kernel_ids_and_names(built_lib):
+    """bench.py (is_hbm_kernel, executed_divisor), tests/step_bits_common.py and the scripts under scratch/ select timed kernels by
+    these names, and a launch site books its time by position in this list: number, spelling and order are part of the ABI."""
+    names = [
+        "igemm_kernel<128,128,2,2,gen>", "igemm_kernel<128,128,2,2,vec>", "igemm_kernel<128,64,2,2,gen>", "igemm_kernel<128,64,2,2,vec>",
+        "igemm_kernel<128,32,4,1,gen>", "igemm_kernel<128,32,4,1,vec>", "igemm_kernel<64,64,2,2,gen>", "igemm_kernel<64,64,2,2,vec>",
+        "wgrad_kernel<gen>", "wgrad_kernel<vec>", "igemm_kernel<256,128,4,2,gen>", "igemm_kernel<256,128,4,2,vec>",
+        "igemm_kernel<256,64,4,2,gen>", "igemm_kernel<256,64,4,2,vec>", "wino_kernel", "wino_wgrad_kernel", "wino_kernel<4x4s2>",
+        "wino_wgrad_kernel<4x4s2>", "wino43_kernel", "wino43_input_kernel", "rgbin_conv_kernel", "rgb_wgrad_kernel", "wino43_wgrad_kernel",
+        "wino43_dy_kernel", "halo16_kernel", "halo16_wgrad_kernel", "halo16s2_wgrad_kernel", "halo16t_kernel", "rgbout_conv_kernel",
+        "halo16s_kernel", "in_stats_partial", "in_apply", "in_bwd_partial", "in_bwd_apply", "in_fwd_slab", "in_bwd_slab", "igemm16_kernel",
+        "wino42_kernel", "in_fwd_slab_v", "in_bwd_slab_vz", "cr_pairs_kernel", "d_losses_cr_kernel", "ms_rows_kernel", "ms_finish_kernel",
+        "ms_grad_kernel"]
+    lib = built_lib.load()
+    assert lib.srgan_prof_num_kernels() == 45 == len(names)
+    assert [lib.srgan_prof_kernel_name(k).decode() for k in range(45)] == names
+    assert lib.srgan_prof_kernel_name(-1) == b"" and lib.srgan_prof_kernel_name(45) == b""
+
+
 def test_product_refuses_cpu_tensors(built_lib):
     import torch
     from srgan_amd import ops

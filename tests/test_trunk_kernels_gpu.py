@@ -219,3 +219,47 @@ def test_an_image_one_byte_short_is_refused_before_any_launch(ops, lib):
                                            P(images[2]), zz, 1, 0.0, st) != 0
             assert name in L.srgan_last_error()
     assert all(bool((s == 7.0).all()) for s in stats) and all(bool((b == PATTERN).all()) for b in images)
+
+
+def test_a_refused_weight_gradient_leaves_no_open_timer_bracket(ops, lib):
+    """srgan_halo16_wgrad refuses bf16 x with fp32 dy (halo16_wgrad_kernel has no such instantiation) before its launch-timer bracket
+    opens: the profiling session of the refused call holds no slot of that kernel and every kernel id collects; the accepted call
+    (bf16 x, bf16 dy) books exactly one launch with a finite, positive time.  The smallest layer halo16_applicable accepts."""
+    N, C, H, W = 1, 64, 4, 32
+    L, P, st = lib.load(), ops._ptr, ops._stream()
+    names = [L.srgan_prof_kernel_name(k).decode() for k in range(L.srgan_prof_num_kernels())]
+
+    def collect():
+        L.srgan_prof_enable(0)
+        torch.cuda.synchronize()
+        out = {}
+        for kid, name in enumerate(names):
+            ms, n, fl = ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double()
+            assert L.srgan_prof_collect(kid, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(fl)) == 0, (name, L.srgan_last_error())
+            out[name] = (n.value, ms.value)
+        return out
+
+    assert L.srgan_set_compute_mode(1) == 0
+    try:
+        dw = torch.zeros(C, C, 3, 3, device="cuda")
+        desc = ops._conv_desc(N, H, W, C, H, W, C, 3, 3, 1, 1, ops.PAD_ZERO, dw)
+        d = ctypes.byref(desc)
+        nbytes = L.srgan_conv2d_workspace(d)
+        assert nbytes > 0
+        ws = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        x16 = torch.randn(N, H, W, C, device="cuda").to(torch.bfloat16)
+        dy32 = torch.randn(N, H, W, C, device="cuda")
+        dy16 = dy32.to(torch.bfloat16)
+        L.srgan_prof_enable(1)
+        assert L.srgan_halo16_wgrad(d, P(x16), 1, P(dy32), 0, P(dw), P(ws), nbytes, st) != 0
+        assert b"not instantiated" in L.srgan_last_error()
+        got = collect()
+        assert got["halo16_wgrad_kernel"][0] == 0, got
+        L.srgan_prof_enable(1)
+        lib.check(L.srgan_halo16_wgrad(d, P(x16), 1, P(dy16), 1, P(dw), P(ws), nbytes, st), "srgan_halo16_wgrad")
+        got = collect()
+        n, ms = got["halo16_wgrad_kernel"]
+        assert n == 1 and ms > 0.0 and ms != float("inf") and ms == ms, got
+    finally:
+        L.srgan_prof_enable(0)
+        assert L.srgan_set_compute_mode(0) == 0

@@ -36,7 +36,7 @@ MAX_ELEMS = 2 << 20
 L = 16 + 4 + 4
 
 
-# ---- host geometry of csrc/conv_wino43.hip / conv_wino.hip / conv_igemm.hip, restated ------------------------------------------
+# ---- host geometry of csrc/conv_wino43.hip / conv_wino.hip / conv_dispatch.hip, restated ------------------------------------------
 W4T, W4C, W4BLK = 64, 8, 36 * 512       # tiles per workgroup, reduce channels per chunk, floats of one (tile block, chunk) image
 
 
