@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include "common.h"
 #include "prof.h"
 
@@ -1006,74 +1007,196 @@ void plan_split(int N, int HW, int C, int& S, int& rps) {
   while (blocks * S < 1024 && HW / (S * 2) >= 64) S *= 2;
   rps = (HW + S - 1) / S;
 }
-}  // namespace
-}  // namespace srgan
 
-using namespace srgan;
+// Every instantiation the dispatch below launches, in the order the code object lays them out (naming one here instantiates it
+// first): the fp32 entries' kernels, then the 16-bit pairings.  The dispatch picks among these and must add none.
+template <class K>
+const void* at(K* kernel) { return reinterpret_cast<const void*>(kernel); }
+[[maybe_unused]] const void* const instantiations[] = {
+    at(in_fwd_slab<1, 0, 0>), at(in_fwd_slab<2, 0, 0>), at(in_fwd_slab<4, 0, 0>), at(in_fwd_slab<8, 0, 0>), at(in_fwd_slab<16, 0, 0>),
+    at(in_stats_partial_v4<0>), at(in_apply_pow2<0, 0>), at(in_apply<true>), at(in_apply<false>),
+    at(in_bwd_slab<1, 0, 0, 0>), at(in_bwd_slab<2, 0, 0, 0>), at(in_bwd_slab<4, 0, 0, 0>), at(in_bwd_slab<8, 0, 0, 0>), at(in_bwd_slab<16, 0, 0, 0>),
+    at(in_bwd_partial_v4<0, 0>), at(in_bwd_apply_pow2<0, 0, 0>), at(in_bwd_apply<true>), at(in_bwd_apply<false>),
+    at(in_fwd_slab8<1, 1, 1>), at(in_fwd_slab8<2, 1, 1>), at(in_fwd_slab8<4, 1, 1>), at(in_fwd_slab8<8, 1, 1>),
+    at(in_fwd_slab8<1, 1, 0>), at(in_fwd_slab8<2, 1, 0>), at(in_fwd_slab8<4, 1, 0>), at(in_fwd_slab8<8, 1, 0>),
+    at(in_fwd_slab8<1, 0, 1>), at(in_fwd_slab8<2, 0, 1>), at(in_fwd_slab8<4, 0, 1>), at(in_fwd_slab8<8, 0, 1>),
+    at(in_bwd_slab<1, 1, 1, 1>), at(in_bwd_slab<2, 1, 1, 1>), at(in_bwd_slab<4, 1, 1, 1>), at(in_bwd_slab<8, 1, 1, 1>), at(in_bwd_slab<16, 1, 1, 1>),
+    at(in_bwd_slab<1, 1, 0, 1>), at(in_bwd_slab<2, 1, 0, 1>), at(in_bwd_slab<4, 1, 0, 1>), at(in_bwd_slab<8, 1, 0, 1>), at(in_bwd_slab<16, 1, 0, 1>),
+    at(in_bwd_slab<1, 0, 1, 0>), at(in_bwd_slab<2, 0, 1, 0>), at(in_bwd_slab<4, 0, 1, 0>), at(in_bwd_slab<8, 0, 1, 0>), at(in_bwd_slab<16, 0, 1, 0>),
+    at(in_stats_partial_v4<1>), at(in_apply_pow2<1, 1>), at(in_apply_pow2<1, 0>), at(in_apply_pow2<0, 1>),
+    at(in_bwd_partial_v8<1>), at(in_bwd_partial_v8<0>), at(in_bwd_partial_v4<1, 1>), at(in_bwd_partial_v4<1, 0>), at(in_bwd_partial_v4<0, 1>),
+    at(in_bwd_apply_pow2<1, 1, 1>), at(in_bwd_apply_pow2<1, 0, 1>), at(in_bwd_apply_pow2<0, 1, 0>),
+};
 
-extern "C" size_t srgan_instnorm_workspace(int N, int HW, int C) {
+size_t workspace_bytes(int N, int HW, int C) {
   int S, rps;
   plan_split(N, HW, C, S, rps);
   return (size_t)N * S * C * sizeof(float2);
 }
 
+// a runtime bool as a template argument: f(std::true_type) or f(std::false_type); with_bools: two of them, f(A, B)
+template <class F>
+void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <class F>
+void with_bools(bool a, bool b, F&& f) {
+  with_bool(a, [&](auto A) { with_bool(b, [&](auto B) { f(A, B); }); });
+}
+
+// the first R of the list that is >= rows, the last one if none is: f(std::integral_constant<int, R>)
+template <int R0, int... Rs, class F>
+void with_rows(int rows, F&& f) {
+  if constexpr (sizeof...(Rs) == 0) f(std::integral_constant<int, R0>{});
+  else if (rows <= R0) f(std::integral_constant<int, R0>{});
+  else with_rows<Rs...>(rows, f);
+}
+
+// Every launch of the forward, behind srgan_instnorm_fwd (x16 = y16 = false) and the two 16-bit entries, which have validated
+// the call: single-pass slab kernel, or partial statistics + a finish.  `what` labels a launch error.
+int instnorm_forward(const void* x, bool x16, const float* scale, const float* shift, const float* res, void* y, bool y16,
+                     float* mean, float* rstd, int N, int HW, int C, float eps, int act, float slope, void* ws, hipStream_t st,
+                     const char* what) {
+  const double ebytes = (double)N * HW * C;      // bench.py's roofline_hbm: bytes the passes must move
+  const int xb = x16 ? 2 : 4, yb = y16 ? 2 : 4;
+  const double apply_bytes = ebytes * (xb + yb + (res ? 4 : 0));
+  if (slab_fast(N, HW, C)) {
+    const dim3 gs((unsigned)(C / 32), (unsigned)N);
+    ProfScope scope(PROF_IN_FWD_SLAB, apply_bytes, st);
+    with_bools(x16, y16, [&](auto X, auto Y) {
+      constexpr bool X16 = X.value, Y16 = Y.value;
+      if constexpr (X16 || Y16) {      // 16-bit tensor on a side: 8 channels per lane, 128 pixels per pass
+        with_rows<1, 2, 4, 8>((HW + 127) / 128, [&](auto R) {
+          hipLaunchKernelGGL((in_fwd_slab8<R.value, X16, Y16>), gs, dim3(512), 0, st, x, scale, shift, res, y, mean, rstd, HW, C, eps, act, slope, slab_remap());
+        });
+      } else {
+        with_rows<1, 2, 4, 8, 16>((HW + 63) / 64, [&](auto R) {
+          hipLaunchKernelGGL((in_fwd_slab<R.value, false, false>), gs, dim3(512), 0, st, x, scale, shift, res, y, mean, rstd, HW, C, eps, act, slope, slab_remap());
+        });
+      }
+    });
+    return check_launch(what);
+  }
+  int S, rps;
+  plan_split(N, HW, C, S, rps);
+  float2* part = reinterpret_cast<float2*>(ws);
+  const dim3 g((C + NORM_CH - 1) / NORM_CH, S, N);
+  // the scalar kernels and the separate finalize take fp32 tensors: the fp32 entry alone gets there (the 16-bit entries serve
+  // C % 4 == 0 with the pow2 finish and refuse in-place calls)
+  const float* xf = static_cast<const float*>(x);
+  float* yf = static_cast<float*>(y);
+  {
+    ProfScope scope(PROF_IN_STATS_PARTIAL, ebytes * xb, st);
+    if (x16 && (C & 63) == 0) hipLaunchKernelGGL(in_stats_partial_v8, dim3(C / 64, S, N), dim3(256), 0, st, x, part, HW, C, S, rps);
+    else if ((C & 3) == 0) with_bool(x16, [&](auto X) { hipLaunchKernelGGL(in_stats_partial_v4<X.value>, g, dim3(256), 0, st, x, part, HW, C, S, rps); });
+    else hipLaunchKernelGGL(in_stats_partial, g, dim3(256), 0, st, xf, part, HW, C, S, rps);
+  }
+  const bool pow2 = pow2_fast(C, HW);
+  const int hwc4 = HW * C / 4;
+  const dim3 g2((unsigned)apply_grid(hwc4, N), (unsigned)N);      // (of in_apply_pow2)
+  // the fused finish re-reads the shift sample x[n][pixel 0][c] in EVERY workgroup of the apply pass while workgroup 0 may
+  // already be storing y there: an in-place call (y == x, or the skip tensor == y) takes the separate finalize launch instead
+  const bool fuse_final = (const void*)y != x && (const void*)y != (const void*)res;
+  if (pow2 && fuse_final) {
+    ProfScope scope(PROF_IN_APPLY, apply_bytes, st);
+    with_bools(x16, y16, [&](auto X, auto Y) {
+      hipLaunchKernelGGL((in_apply_pow2<X.value, Y.value>), g2, dim3(256), 0, st, x, scale, shift, res, mean, rstd, y, hwc4, C, act, slope, (const float2*)part, S, HW, eps);
+    });
+    return check_launch(what);
+  }
+  const long long total = (long long)N * HW * C;
+  hipLaunchKernelGGL(in_stats_final, dim3((N * C + 255) / 256), dim3(256), 0, st, xf, (const float2*)part, mean, rstd, N, HW, C, S, eps);
+  if (pow2) {
+    hipLaunchKernelGGL((in_apply_pow2<false, false>), g2, dim3(256), 0, st, x, scale, shift, res, mean, rstd, y, hwc4, C, act, slope,
+                       (const float2*)nullptr, 0, HW, eps);
+  } else if ((C & 3) == 0) {
+    unsigned blocks = (unsigned)std::min<long long>(ceil_div(total / 4, 256), 8192);
+    hipLaunchKernelGGL(in_apply<true>, dim3(blocks), dim3(256), 0, st, xf, scale, shift, res, mean, rstd, yf, total, HW * C, C, act, slope);
+  } else {
+    unsigned blocks = (unsigned)std::min<long long>(ceil_div(total, 256), 8192);
+    hipLaunchKernelGGL(in_apply<false>, dim3(blocks), dim3(256), 0, st, xf, scale, shift, res, mean, rstd, yf, total, HW * C, C, act, slope);
+  }
+  return check_launch(what);
+}
+
+// Every launch of the backward, as instnorm_forward; dx has x's type.
+int instnorm_backward(const void* x, bool x16, const void* dy, bool g16, const float* scale, const float* shift, const float* mean,
+                      const float* rstd, void* dx, float* dscale, float* dshift, int N, int HW, int C, int act, float slope,
+                      void* ws, hipStream_t st, const char* what) {
+  const double ebytes = (double)N * HW * C;
+  const int xb = x16 ? 2 : 4, gb = g16 ? 2 : 4;
+  if (slab_fast(N, HW, C)) {
+    // (8 channels per lane with 32-channel slabs, as in the forward, was measured slower here: 23.4 against 15.7 us on the
+    // 32 x 32 x 256 trunk -- the backward lives on two 256-thread workgroups per CU overlapping each other's phases)
+    const dim3 gs((unsigned)(C / 16), (unsigned)N);
+    ProfScope scope(PROF_IN_BWD_SLAB, ebytes * (2 * xb + gb), st);
+    with_bools(x16, g16, [&](auto X, auto G) {
+      constexpr bool X16 = X.value, G16 = G.value;
+      with_rows<1, 2, 4, 8, 16>((HW + 63) / 64, [&](auto R) {
+        hipLaunchKernelGGL((in_bwd_slab<R.value, X16, G16, X16>), gs, dim3(256), 0, st, x, dy, scale, shift, mean, rstd, dx, dscale, dshift, HW, C, act, slope, slab_remap());
+      });
+    });
+    return check_launch(what);
+  }
+  int S, rps;
+  plan_split(N, HW, C, S, rps);
+  float2* part = reinterpret_cast<float2*>(ws);
+  const dim3 g((C + NORM_CH - 1) / NORM_CH, S, N);
+  const float *xf = static_cast<const float*>(x), *gf = static_cast<const float*>(dy);      // (fp32 entry alone, as in the forward)
+  float* dxf = static_cast<float*>(dx);
+  {
+    ProfScope scope(PROF_IN_BWD_PARTIAL, ebytes * (xb + gb), st);
+    if (x16 && (C & 63) == 0) {
+      with_bool(g16, [&](auto G) {
+        hipLaunchKernelGGL(in_bwd_partial_v8<G.value>, dim3(C / 64, S, N), dim3(256), 0, st, x, dy, scale, shift, mean, rstd, part, HW, C, S, rps, act, slope);
+      });
+    } else if ((C & 3) == 0) {
+      with_bools(x16, g16, [&](auto X, auto G) {
+        hipLaunchKernelGGL((in_bwd_partial_v4<X.value, G.value>), g, dim3(256), 0, st, x, dy, scale, shift, mean, rstd, part, HW, C, S, rps, act, slope);
+      });
+    } else {
+      hipLaunchKernelGGL(in_bwd_partial, g, dim3(256), 0, st, xf, gf, scale, shift, mean, rstd, part, HW, C, S, rps, act, slope);
+    }
+  }
+  const float inv_hw = 1.f / (float)HW;
+  if (pow2_fast(C, HW)) {      // (the backward's fused finish reads the partial sums only: in-place dx is an elementwise update)
+    const int hwc4 = HW * C / 4;
+    const dim3 g2((unsigned)apply_grid(hwc4, N), (unsigned)N);
+    ProfScope scope(PROF_IN_BWD_APPLY, ebytes * (2 * xb + gb), st);
+    with_bools(x16, g16, [&](auto X, auto G) {
+      hipLaunchKernelGGL((in_bwd_apply_pow2<X.value, G.value, X.value>), g2, dim3(256), 0, st, x, dy, scale, shift, mean, rstd, dshift, dscale, dx, hwc4, C, inv_hw, act, slope, (const float2*)part, S);
+    });
+    return check_launch(what);
+  }
+  const long long total = (long long)N * HW * C;
+  hipLaunchKernelGGL(in_bwd_final, dim3((N * C + 255) / 256), dim3(256), 0, st, (const float2*)part, dshift, dscale, N * C, C, S);
+  if ((C & 3) == 0) {
+    unsigned blocks = (unsigned)std::min<long long>(ceil_div(total / 4, 256), 8192);
+    hipLaunchKernelGGL(in_bwd_apply<true>, dim3(blocks), dim3(256), 0, st, xf, gf, scale, shift, mean, rstd, dshift, dscale, dxf, total, HW * C, C, inv_hw, act, slope);
+  } else {
+    unsigned blocks = (unsigned)std::min<long long>(ceil_div(total, 256), 8192);
+    hipLaunchKernelGGL(in_bwd_apply<false>, dim3(blocks), dim3(256), 0, st, xf, gf, scale, shift, mean, rstd, dshift, dscale, dxf, total, HW * C, C, inv_hw, act, slope);
+  }
+  return check_launch(what);
+}
+}  // namespace
+}  // namespace srgan
+
+using namespace srgan;
+
+extern "C" size_t srgan_instnorm_workspace(int N, int HW, int C) { return workspace_bytes(N, HW, C); }
+
+// The fp32 entries serve every shape and ask for the workspace on every shape (the slab kernels do not use it).
 extern "C" int srgan_instnorm_fwd(const float* x, const float* scale, const float* shift, const float* res, float* y,
                                   float* mean, float* rstd, int N, int HW, int C, float eps, int act, float slope,
                                   void* ws, size_t ws_bytes, void* stream) {
   SRGAN_REQUIRE(x && y && mean && rstd, "instnorm_fwd: null pointer");
   SRGAN_REQUIRE(N > 0 && HW > 0 && C > 0, "instnorm_fwd: bad shape");
   SRGAN_REQUIRE((scale == nullptr) == (shift == nullptr), "instnorm_fwd: scale and shift go together");
-  hipStream_t st = as_stream(stream);
-  int S, rps;
-  plan_split(N, HW, C, S, rps);
-  SRGAN_REQUIRE(ws && ws_bytes >= (size_t)N * S * C * sizeof(float2), "instnorm_fwd: workspace too small");
-  const double tbytes = (double)N * HW * C * sizeof(float);      // bench.py's roofline_hbm: bytes the passes must move
-  if (slab_fast(N, HW, C)) {
-    const dim3 gs((unsigned)(C / 32), (unsigned)N);
-    const int rows = (HW + 63) / 64;
-#define SRGAN_FWD_SLAB(R) hipLaunchKernelGGL(in_fwd_slab<R>, gs, dim3(512), 0, st, x, scale, shift, res, y, mean, rstd, HW, C, eps, act, slope, slab_remap())
-    ProfScope scope(PROF_IN_FWD_SLAB, (res ? 3.0 : 2.0) * tbytes, st);
-    if (rows <= 1) SRGAN_FWD_SLAB(1);
-    else if (rows <= 2) SRGAN_FWD_SLAB(2);
-    else if (rows <= 4) SRGAN_FWD_SLAB(4);
-    else if (rows <= 8) SRGAN_FWD_SLAB(8);
-    else SRGAN_FWD_SLAB(16);
-#undef SRGAN_FWD_SLAB
-    return check_launch("instnorm_fwd (slab)");
-  }
-  float2* part = reinterpret_cast<float2*>(ws);
-  dim3 g((C + NORM_CH - 1) / NORM_CH, S, N);
-  {
-    ProfScope scope(PROF_IN_STATS_PARTIAL, tbytes, st);
-    if ((C & 3) == 0) hipLaunchKernelGGL(in_stats_partial_v4<false>, g, dim3(256), 0, st, (const void*)x, part, HW, C, S, rps);
-    else hipLaunchKernelGGL(in_stats_partial, g, dim3(256), 0, st, x, part, HW, C, S, rps);
-  }
-  const long long total = (long long)N * HW * C;
-  // the fused finish re-reads the shift sample x[n][pixel 0][c] in EVERY workgroup of the apply pass while workgroup 0 may
-  // already be storing y there: an in-place call (y == x, or the skip tensor == y) takes the separate finalize launch instead
-  const bool fuse_final = (const float*)y != x && (const float*)y != res;
-  if (pow2_fast(C, HW) && fuse_final) {
-    const int hwc4 = HW * C / 4;
-    dim3 g2((unsigned)apply_grid(hwc4, N), (unsigned)N);
-    ProfScope scope(PROF_IN_APPLY, (res ? 3.0 : 2.0) * tbytes, st);
-    hipLaunchKernelGGL((in_apply_pow2<false, false>), g2, dim3(256), 0, st, (const void*)x, scale, shift, res, mean, rstd, (void*)y, hwc4, C, act, slope,
-                       (const float2*)part, S, HW, eps);
-    return check_launch("instnorm_fwd");
-  }
-  hipLaunchKernelGGL(in_stats_final, dim3((N * C + 255) / 256), dim3(256), 0, st, x, (const float2*)part, mean, rstd, N, HW, C, S, eps);
-  if (pow2_fast(C, HW)) {
-    const int hwc4 = HW * C / 4;
-    dim3 g2((unsigned)apply_grid(hwc4, N), (unsigned)N);
-    hipLaunchKernelGGL((in_apply_pow2<false, false>), g2, dim3(256), 0, st, (const void*)x, scale, shift, res, mean, rstd, (void*)y, hwc4, C, act, slope,
-                       (const float2*)nullptr, 0, HW, eps);
-  } else if ((C & 3) == 0) {
-    unsigned blocks = (unsigned)std::min<long long>(ceil_div(total / 4, 256), 8192);
-    hipLaunchKernelGGL(in_apply<true>, dim3(blocks), dim3(256), 0, st, x, scale, shift, res, mean, rstd, y, total, HW * C, C, act, slope);
-  } else {
-    unsigned blocks = (unsigned)std::min<long long>(ceil_div(total, 256), 8192);
-    hipLaunchKernelGGL(in_apply<false>, dim3(blocks), dim3(256), 0, st, x, scale, shift, res, mean, rstd, y, total, HW * C, C, act, slope);
-  }
-  return check_launch("instnorm_fwd");
+  SRGAN_REQUIRE(ws && ws_bytes >= workspace_bytes(N, HW, C), "instnorm_fwd: workspace too small");
+  return instnorm_forward(x, false, scale, shift, res, y, false, mean, rstd, N, HW, C, eps, act, slope, ws, as_stream(stream),
+                          slab_fast(N, HW, C) ? "instnorm_fwd (slab)" : "instnorm_fwd");
 }
 
 extern "C" int srgan_instnorm_bwd(const float* x, const float* dy, const float* scale, const float* shift,
@@ -1081,50 +1204,9 @@ extern "C" int srgan_instnorm_bwd(const float* x, const float* dy, const float* 
                                   int N, int HW, int C, int act, float slope, void* ws, size_t ws_bytes, void* stream) {
   SRGAN_REQUIRE(x && dy && mean && rstd && dx && dscale && dshift, "instnorm_bwd: null pointer");
   SRGAN_REQUIRE((scale == nullptr) == (shift == nullptr), "instnorm_bwd: scale and shift go together");
-  hipStream_t st = as_stream(stream);
-  int S, rps;
-  plan_split(N, HW, C, S, rps);
-  SRGAN_REQUIRE(ws && ws_bytes >= (size_t)N * S * C * sizeof(float2), "instnorm_bwd: workspace too small");
-  const double tbytes = (double)N * HW * C * sizeof(float);
-  if (slab_fast(N, HW, C)) {
-    const dim3 gs((unsigned)(C / 16), (unsigned)N);
-    const int rows = (HW + 63) / 64;
-#define SRGAN_BWD_SLAB(R) hipLaunchKernelGGL(in_bwd_slab<R>, gs, dim3(256), 0, st, x, dy, scale, shift, mean, rstd, dx, dscale, dshift, HW, C, act, slope, slab_remap())
-    ProfScope scope(PROF_IN_BWD_SLAB, 3.0 * tbytes, st);
-    if (rows <= 1) SRGAN_BWD_SLAB(1);
-    else if (rows <= 2) SRGAN_BWD_SLAB(2);
-    else if (rows <= 4) SRGAN_BWD_SLAB(4);
-    else if (rows <= 8) SRGAN_BWD_SLAB(8);
-    else SRGAN_BWD_SLAB(16);
-#undef SRGAN_BWD_SLAB
-    return check_launch("instnorm_bwd (slab)");
-  }
-  float2* part = reinterpret_cast<float2*>(ws);
-  dim3 g((C + NORM_CH - 1) / NORM_CH, S, N);
-  {
-    ProfScope scope(PROF_IN_BWD_PARTIAL, 2.0 * tbytes, st);
-    if ((C & 3) == 0) hipLaunchKernelGGL((in_bwd_partial_v4<false, false>), g, dim3(256), 0, st, (const void*)x, (const void*)dy, scale, shift, mean, rstd, part, HW, C, S, rps, act, slope);
-    else hipLaunchKernelGGL(in_bwd_partial, g, dim3(256), 0, st, x, dy, scale, shift, mean, rstd, part, HW, C, S, rps, act, slope);
-  }
-  const long long total = (long long)N * HW * C;
-  const float inv_hw = 1.f / (float)HW;
-  if (pow2_fast(C, HW)) {      // (the backward's fused finish reads the partial sums only: in-place dx is an elementwise update)
-    const int hwc4 = HW * C / 4;
-    dim3 g2((unsigned)apply_grid(hwc4, N), (unsigned)N);
-    ProfScope scope(PROF_IN_BWD_APPLY, 3.0 * tbytes, st);
-    hipLaunchKernelGGL((in_bwd_apply_pow2<false, false, false>), g2, dim3(256), 0, st, (const void*)x, (const void*)dy, scale, shift, mean, rstd, dshift, dscale, (void*)dx, hwc4, C, inv_hw, act,
-                       slope, (const float2*)part, S);
-    return check_launch("instnorm_bwd");
-  }
-  hipLaunchKernelGGL(in_bwd_final, dim3((N * C + 255) / 256), dim3(256), 0, st, (const float2*)part, dshift, dscale, N * C, C, S);
-  if ((C & 3) == 0) {
-    unsigned blocks = (unsigned)std::min<long long>(ceil_div(total / 4, 256), 8192);
-    hipLaunchKernelGGL(in_bwd_apply<true>, dim3(blocks), dim3(256), 0, st, x, dy, scale, shift, mean, rstd, dshift, dscale, dx, total, HW * C, C, inv_hw, act, slope);
-  } else {
-    unsigned blocks = (unsigned)std::min<long long>(ceil_div(total, 256), 8192);
-    hipLaunchKernelGGL(in_bwd_apply<false>, dim3(blocks), dim3(256), 0, st, x, dy, scale, shift, mean, rstd, dshift, dscale, dx, total, HW * C, C, inv_hw, act, slope);
-  }
-  return check_launch("instnorm_bwd");
+  SRGAN_REQUIRE(ws && ws_bytes >= workspace_bytes(N, HW, C), "instnorm_bwd: workspace too small");
+  return instnorm_backward(x, false, dy, false, scale, shift, mean, rstd, dx, dscale, dshift, N, HW, C, act, slope, ws,
+                           as_stream(stream), slab_fast(N, HW, C) ? "instnorm_bwd (slab)" : "instnorm_bwd");
 }
 
 // ---- single-pass slab kernels with bf16 tensors on either side (statistics, scale / shift, sums in fp32) ----
@@ -1137,37 +1219,8 @@ extern "C" int srgan_instnorm_slab_fwd_io(const void* x, int x_bf16, const float
   SRGAN_REQUIRE((scale == nullptr) == (shift == nullptr), "instnorm_slab_fwd_io: scale and shift go together");
   SRGAN_REQUIRE(slab_fast(N, HW, C), "instnorm_slab_fwd_io: shape not served by the slab kernels (srgan_instnorm_slab_applicable)");
   SRGAN_REQUIRE(!(res && y_bf16), "instnorm_slab_fwd_io: the skip tensor is added to an fp32 result only");
-  hipStream_t st = as_stream(stream);
-  const dim3 gs((unsigned)(C / 32), (unsigned)N);
-  const double ebytes = (double)N * HW * C;
-  ProfScope scope(PROF_IN_FWD_SLAB, ebytes * ((x_bf16 ? 2 : 4) + (y_bf16 ? 2 : 4) + (res ? 4 : 0)), st);
-  if (x_bf16 || y_bf16) {
-    // 16-bit tensor on a side: 8 channels per lane, 128 pixels per pass
-    const int rows = (HW + 127) / 128;
-#define SRGAN_FWD_IO8(R, A, B) hipLaunchKernelGGL((in_fwd_slab8<R, A, B>), gs, dim3(512), 0, st, x, scale, shift, res, y, mean, rstd, HW, C, eps, act, slope, slab_remap())
-#define SRGAN_FWD_IO8_R(A, B)                  \
-  do {                                         \
-    if (rows <= 1) SRGAN_FWD_IO8(1, A, B);     \
-    else if (rows <= 2) SRGAN_FWD_IO8(2, A, B);\
-    else if (rows <= 4) SRGAN_FWD_IO8(4, A, B);\
-    else SRGAN_FWD_IO8(8, A, B);               \
-  } while (0)
-    if (x_bf16 && y_bf16) SRGAN_FWD_IO8_R(true, true);
-    else if (x_bf16) SRGAN_FWD_IO8_R(true, false);
-    else SRGAN_FWD_IO8_R(false, true);
-#undef SRGAN_FWD_IO8_R
-#undef SRGAN_FWD_IO8
-  } else {
-    const int rows = (HW + 63) / 64;
-#define SRGAN_FWD_IO(R) hipLaunchKernelGGL((in_fwd_slab<R, false, false>), gs, dim3(512), 0, st, x, scale, shift, res, y, mean, rstd, HW, C, eps, act, slope, slab_remap())
-    if (rows <= 1) SRGAN_FWD_IO(1);
-    else if (rows <= 2) SRGAN_FWD_IO(2);
-    else if (rows <= 4) SRGAN_FWD_IO(4);
-    else if (rows <= 8) SRGAN_FWD_IO(8);
-    else SRGAN_FWD_IO(16);
-#undef SRGAN_FWD_IO
-  }
-  return check_launch("instnorm_slab_fwd_io");
+  return instnorm_forward(x, x_bf16 != 0, scale, shift, res, y, y_bf16 != 0, mean, rstd, N, HW, C, eps, act, slope, nullptr,
+                          as_stream(stream), "instnorm_slab_fwd_io");
 }
 
 extern "C" int srgan_instnorm_slab_bwd_io(const void* x, int x_bf16, const void* dy, int dy_bf16, const float* scale,
@@ -1177,34 +1230,14 @@ extern "C" int srgan_instnorm_slab_bwd_io(const void* x, int x_bf16, const void*
   SRGAN_REQUIRE((scale == nullptr) == (shift == nullptr), "instnorm_slab_bwd_io: scale and shift go together");
   SRGAN_REQUIRE(slab_fast(N, HW, C), "instnorm_slab_bwd_io: shape not served by the slab kernels (srgan_instnorm_slab_applicable)");
   SRGAN_REQUIRE((x_bf16 != 0) == (dx_bf16 != 0), "instnorm_slab_bwd_io: the input gradient has the input's type");
-  hipStream_t st = as_stream(stream);
-  const double ebytes = (double)N * HW * C;
-  ProfScope scope(PROF_IN_BWD_SLAB, ebytes * (2 * (x_bf16 ? 2 : 4) + (dy_bf16 ? 2 : 4)), st);
-  // (8 channels per lane with 32-channel slabs, as in the forward, was measured slower here: 23.4 against 15.7 us on the
-  // 32 x 32 x 256 trunk -- the backward lives on two 256-thread workgroups per CU overlapping each other's phases)
-  const dim3 gs((unsigned)(C / 16), (unsigned)N);
-  const int rows = (HW + 63) / 64;
-#define SRGAN_BWD_IO(R, X, G) hipLaunchKernelGGL((in_bwd_slab<R, X, G, X>), gs, dim3(256), 0, st, x, dy, scale, shift, mean, rstd, dx, dscale, dshift, HW, C, act, slope, slab_remap())
-#define SRGAN_BWD_IO_R(X, G)                  \
-  do {                                        \
-    if (rows <= 1) SRGAN_BWD_IO(1, X, G);     \
-    else if (rows <= 2) SRGAN_BWD_IO(2, X, G);\
-    else if (rows <= 4) SRGAN_BWD_IO(4, X, G);\
-    else if (rows <= 8) SRGAN_BWD_IO(8, X, G);\
-    else SRGAN_BWD_IO(16, X, G);              \
-  } while (0)
-  if (x_bf16 && dy_bf16) SRGAN_BWD_IO_R(true, true);
-  else if (x_bf16) SRGAN_BWD_IO_R(true, false);
-  else if (dy_bf16) SRGAN_BWD_IO_R(false, true);
-  else SRGAN_BWD_IO_R(false, false);
-#undef SRGAN_BWD_IO_R
-#undef SRGAN_BWD_IO
-  return check_launch("instnorm_slab_bwd_io");
+  return instnorm_backward(x, x_bf16 != 0, dy, dy_bf16 != 0, scale, shift, mean, rstd, dx, dscale, dshift, N, HW, C, act, slope,
+                           nullptr, as_stream(stream), "instnorm_slab_bwd_io");
 }
 
 // ---- instance norm with 16-bit tensors on either side (round 4: bf16 activation storage outside the residual trunk) ----
-// Served shapes: the slab kernels' (maps of <= 1024 pixels) and the fast two-pass kernels' (C | 1024, C % 4 == 0); statistics,
-// scale / shift and the parameter-gradient sums stay fp32.  Reference: pyfiles/model.py:54-67, 178 (as srgan_instnorm_fwd / _bwd).
+// Served shapes: the slab kernels' (maps of <= 1024 pixels; the call is then the slab entry's, its messages included, and no
+// workspace is asked for) and the fast two-pass kernels' (C | 1024, C % 4 == 0); statistics, scale / shift and the
+// parameter-gradient sums stay fp32.  Reference: pyfiles/model.py:54-67, 178 (as srgan_instnorm_fwd / _bwd).
 extern "C" int srgan_instnorm_io_applicable(int N, int HW, int C) {
   return (N > 0 && HW > 0 && C > 0 && (slab_fast(N, HW, C) || ((C & 3) == 0 && pow2_fast(C, HW)))) ? 1 : 0;
 }
@@ -1218,29 +1251,9 @@ extern "C" int srgan_instnorm_fwd_io(const void* x, int x_bf16, const float* sca
   SRGAN_REQUIRE(!(res && y_bf16), "instnorm_fwd_io: the skip tensor is added to an fp32 result only");
   if (slab_fast(N, HW, C)) return srgan_instnorm_slab_fwd_io(x, x_bf16, scale, shift, res, y, y_bf16, mean, rstd, N, HW, C, eps, act, slope, stream);
   SRGAN_REQUIRE((scale == nullptr) == (shift == nullptr), "instnorm_fwd_io: scale and shift go together");
-  hipStream_t st = as_stream(stream);
-  int S, rps;
-  plan_split(N, HW, C, S, rps);
-  SRGAN_REQUIRE(ws && ws_bytes >= (size_t)N * S * C * sizeof(float2), "instnorm_fwd_io: workspace too small (srgan_instnorm_workspace)");
-  const double ebytes = (double)N * HW * C;
-  float2* part = reinterpret_cast<float2*>(ws);
-  dim3 g((C + NORM_CH - 1) / NORM_CH, S, N);
-  {
-    ProfScope scope(PROF_IN_STATS_PARTIAL, ebytes * (x_bf16 ? 2 : 4), st);
-    if (x_bf16 && (C & 63) == 0) hipLaunchKernelGGL(in_stats_partial_v8, dim3(C / 64, S, N), dim3(256), 0, st, x, part, HW, C, S, rps);
-    else if (x_bf16) hipLaunchKernelGGL(in_stats_partial_v4<true>, g, dim3(256), 0, st, x, part, HW, C, S, rps);
-    else hipLaunchKernelGGL(in_stats_partial_v4<false>, g, dim3(256), 0, st, x, part, HW, C, S, rps);
-  }
-  const int hwc4 = HW * C / 4;
-  dim3 g2((unsigned)apply_grid(hwc4, N), (unsigned)N);
-  ProfScope scope(PROF_IN_APPLY, ebytes * ((x_bf16 ? 2 : 4) + (y_bf16 ? 2 : 4) + (res ? 4 : 0)), st);
-#define SRGAN_APPLY_IO(A, B) hipLaunchKernelGGL((in_apply_pow2<A, B>), g2, dim3(256), 0, st, x, scale, shift, res, mean, rstd, y, hwc4, C, act, slope, (const float2*)part, S, HW, eps)
-  if (x_bf16 && y_bf16) SRGAN_APPLY_IO(true, true);
-  else if (x_bf16) SRGAN_APPLY_IO(true, false);
-  else if (y_bf16) SRGAN_APPLY_IO(false, true);
-  else SRGAN_APPLY_IO(false, false);
-#undef SRGAN_APPLY_IO
-  return check_launch("instnorm_fwd_io");
+  SRGAN_REQUIRE(ws && ws_bytes >= workspace_bytes(N, HW, C), "instnorm_fwd_io: workspace too small (srgan_instnorm_workspace)");
+  return instnorm_forward(x, x_bf16 != 0, scale, shift, res, y, y_bf16 != 0, mean, rstd, N, HW, C, eps, act, slope, ws,
+                          as_stream(stream), "instnorm_fwd_io");
 }
 
 extern "C" int srgan_instnorm_bwd_io(const void* x, int x_bf16, const void* dy, int dy_bf16, const float* scale, const float* shift,
@@ -1253,37 +1266,9 @@ extern "C" int srgan_instnorm_bwd_io(const void* x, int x_bf16, const void* dy, 
     return srgan_instnorm_slab_bwd_io(x, x_bf16, dy, dy_bf16, scale, shift, mean, rstd, dx, dx_bf16, dscale, dshift, N, HW, C, act, slope, stream);
   }
   SRGAN_REQUIRE((scale == nullptr) == (shift == nullptr), "instnorm_bwd_io: scale and shift go together");
-  hipStream_t st = as_stream(stream);
-  int S, rps;
-  plan_split(N, HW, C, S, rps);
-  SRGAN_REQUIRE(ws && ws_bytes >= (size_t)N * S * C * sizeof(float2), "instnorm_bwd_io: workspace too small (srgan_instnorm_workspace)");
-  const double ebytes = (double)N * HW * C;
-  const int xb = x_bf16 ? 2 : 4, gb = dy_bf16 ? 2 : 4;
-  float2* part = reinterpret_cast<float2*>(ws);
-  dim3 g((C + NORM_CH - 1) / NORM_CH, S, N);
-  {
-    ProfScope scope(PROF_IN_BWD_PARTIAL, ebytes * (xb + gb), st);
-#define SRGAN_BPART_IO(A, B) hipLaunchKernelGGL((in_bwd_partial_v4<A, B>), g, dim3(256), 0, st, x, dy, scale, shift, mean, rstd, part, HW, C, S, rps, act, slope)
-    if (x_bf16 && (C & 63) == 0) {
-      if (dy_bf16) hipLaunchKernelGGL(in_bwd_partial_v8<true>, dim3(C / 64, S, N), dim3(256), 0, st, x, dy, scale, shift, mean, rstd, part, HW, C, S, rps, act, slope);
-      else hipLaunchKernelGGL(in_bwd_partial_v8<false>, dim3(C / 64, S, N), dim3(256), 0, st, x, dy, scale, shift, mean, rstd, part, HW, C, S, rps, act, slope);
-    } else if (x_bf16 && dy_bf16) SRGAN_BPART_IO(true, true);
-    else if (x_bf16) SRGAN_BPART_IO(true, false);
-    else if (dy_bf16) SRGAN_BPART_IO(false, true);
-    else SRGAN_BPART_IO(false, false);
-#undef SRGAN_BPART_IO
-  }
-  const int hwc4 = HW * C / 4;
-  const float inv_hw = 1.f / (float)HW;
-  dim3 g2((unsigned)apply_grid(hwc4, N), (unsigned)N);
-  ProfScope scope(PROF_IN_BWD_APPLY, ebytes * (2 * xb + gb), st);
-#define SRGAN_BAPPLY_IO(A, B) hipLaunchKernelGGL((in_bwd_apply_pow2<A, B, A>), g2, dim3(256), 0, st, x, dy, scale, shift, mean, rstd, dshift, dscale, dx, hwc4, C, inv_hw, act, slope, (const float2*)part, S)
-  if (x_bf16 && dy_bf16) SRGAN_BAPPLY_IO(true, true);
-  else if (x_bf16) SRGAN_BAPPLY_IO(true, false);
-  else if (dy_bf16) SRGAN_BAPPLY_IO(false, true);
-  else SRGAN_BAPPLY_IO(false, false);
-#undef SRGAN_BAPPLY_IO
-  return check_launch("instnorm_bwd_io");
+  SRGAN_REQUIRE(ws && ws_bytes >= workspace_bytes(N, HW, C), "instnorm_bwd_io: workspace too small (srgan_instnorm_workspace)");
+  return instnorm_backward(x, x_bf16 != 0, dy, dy_bf16 != 0, scale, shift, mean, rstd, dx, dscale, dshift, N, HW, C, act, slope, ws,
+                           as_stream(stream), "instnorm_bwd_io");
 }
 
 extern "C" int srgan_cbin_affine_fwd(const float* c, const float* W, const float* b, const float* gamma,

@@ -772,23 +772,57 @@ def conv_transpose2d(x, weight, stride=2, padding=1):
 # ------------------------------------------------------------------------------------------
 # instance norm (+affine, activation, residual) and the CBIN affine
 # ------------------------------------------------------------------------------------------
+# The two entry families of csrc/norm.hip.  ``out_dtype`` / ``io`` select one: None / False = srgan_instnorm_fwd / _bwd (fp32
+# tensors, every shape); a dtype / True = srgan_instnorm_fwd_io / _bwd_io (fp32 or bf16 x, a result of that dtype, dx of x's
+# type; the shapes of srgan_instnorm_io_applicable).
+def _instnorm_fwd(x, scale, shift, res, act, slope, eps, out_dtype=None):
+    """-> (y, mean, rstd) of an NHWC-dense x (and skip tensor ``res``, fp32, or None)."""
+    n, c, h, w = x.shape
+    lib = _lib.load()
+    y = torch.empty_like(x, dtype=out_dtype)
+    mean = torch.empty(n * c, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    nb = lib.srgan_instnorm_workspace(n, h * w, c)
+    ws = workspace(x.device, nb)
+    tail = (_ptr(mean), _ptr(rstd), n, h * w, c, float(eps), act, float(slope), _ptr(ws), nb, _stream())
+    if out_dtype is None:
+        rc, what = lib.srgan_instnorm_fwd(_ptr(x), _ptr(scale), _ptr(shift), _ptr(res), _ptr(y), *tail), "instnorm_fwd"
+    else:
+        rc, what = lib.srgan_instnorm_fwd_io(_ptr(x), _is16(x), _ptr(scale), _ptr(shift), _ptr(res), _ptr(y), _is16(y), *tail), "instnorm_fwd_io"
+    _lib.check(rc, what)
+    return y, mean, rstd
+
+
+def _instnorm_bwd(x, gy, scale, shift, mean, rstd, act, slope, io=False):
+    """-> (dx, dscale, dshift) from the forward's NHWC-dense x and statistics and the NHWC-dense upstream gradient."""
+    n, c, h, w = x.shape
+    lib = _lib.load()
+    dx = torch.empty_like(x)
+    dscale = torch.empty(n, c, dtype=torch.float32, device=x.device)
+    dshift = torch.empty_like(dscale)
+    nb = lib.srgan_instnorm_workspace(n, h * w, c)
+    ws = workspace(x.device, nb)
+    tail = (_ptr(dscale), _ptr(dshift), n, h * w, c, act, float(slope), _ptr(ws), nb, _stream())
+    if io:
+        rc, what = lib.srgan_instnorm_bwd_io(_ptr(x), _is16(x), _ptr(gy), _is16(gy), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd),
+                                             _ptr(dx), _is16(dx), *tail), "instnorm_bwd_io"
+    else:
+        rc, what = lib.srgan_instnorm_bwd(_ptr(x), _ptr(gy), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), _ptr(dx), *tail), "instnorm_bwd"
+    _lib.check(rc, what)
+    return dx, dscale, dshift
+
+
 class _InstNormFn(Function):
+    """instance_norm_act (``out_dtype`` None) and instance_norm_act_io (a dtype: fp32 or bf16 input, a result of that type; dx
+    has x's type)."""
+
     @staticmethod
-    def forward(ctx, x, scale, shift, res, act, slope, eps):
+    def forward(ctx, x, scale, shift, res, act, slope, eps, out_dtype):
         x = to_nhwc(x)
-        n, c, h, w = x.shape
-        lib = _lib.load()
         if res is not None:
             res = to_nhwc(res)
-        y = torch.empty_like(x)
-        mean = torch.empty(n * c, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        nb = lib.srgan_instnorm_workspace(n, h * w, c)
-        ws = workspace(x.device, nb)
-        _lib.check(lib.srgan_instnorm_fwd(_ptr(x), _ptr(scale), _ptr(shift), _ptr(res), _ptr(y), _ptr(mean), _ptr(rstd),
-                                          n, h * w, c, float(eps), act, float(slope), _ptr(ws), nb, _stream()),
-                   "instnorm_fwd")
-        ctx.act, ctx.slope, ctx.has_res = act, slope, res is not None
+        y, mean, rstd = _instnorm_fwd(x, scale, shift, res, act, slope, eps, out_dtype)
+        ctx.act, ctx.slope, ctx.has_res, ctx.io = act, slope, res is not None, out_dtype is not None
         ctx.save_for_backward(x, scale, shift, mean, rstd)
         return y
 
@@ -796,24 +830,15 @@ class _InstNormFn(Function):
     def backward(ctx, gy):
         x, scale, shift, mean, rstd = ctx.saved_tensors
         gy = to_nhwc(gy)
-        n, c, h, w = x.shape
-        lib = _lib.load()
-        dx = torch.empty_like(x)
-        dscale = torch.empty(n, c, dtype=torch.float32, device=x.device)
-        dshift = torch.empty_like(dscale)
-        nb = lib.srgan_instnorm_workspace(n, h * w, c)
-        ws = workspace(x.device, nb)
-        _lib.check(lib.srgan_instnorm_bwd(_ptr(x), _ptr(gy), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), _ptr(dx),
-                                          _ptr(dscale), _ptr(dshift), n, h * w, c, ctx.act, float(ctx.slope), _ptr(ws), nb,
-                                          _stream()), "instnorm_bwd")
+        dx, dscale, dshift = _instnorm_bwd(x, gy, scale, shift, mean, rstd, ctx.act, ctx.slope, ctx.io)
         has_aff = scale is not None
         return (dx, dscale if has_aff else None, dshift if has_aff else None, (gy.clone() if _DEBUG_CLONE else gy) if ctx.has_res else None,
-                None, None, None)
+                None, None, None, None)
 
 
 def instance_norm_act(x, scale=None, shift=None, res=None, act=ACT_NONE, slope=0.0, eps=1e-5):
     """act((x - mean)/sqrt(var+eps) * scale[n,c] + shift[n,c]) (+ res)."""
-    return _InstNormFn.apply(x, scale, shift, res, act, slope, eps)
+    return _InstNormFn.apply(x, scale, shift, res, act, slope, eps, None)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1123,16 +1148,14 @@ class _NormActConvFn(Function):
     @staticmethod
     def backward(ctx, gy):
         x, scale, shift, mean, rstd = ctx.saved_tensors
-        lib = _lib.load()
         gy = to_nhwc(gy)
         weight = ctx.weight
-        n, c, h, w = x.shape
         dw = None
         if ctx.needs_input_grad[3]:
             def launch(dd, dw, db, ws, nb):
                 hx = None
                 if ctx.v_image is None:   # no V kept (layer outside the F(4x4,3x3) weight-gradient geometry): recompute the normalised input
-                    hx = _InstNormFn.apply(x.detach(), scale, shift, None, ctx.act, ctx.slope, ctx.eps)
+                    hx = _InstNormFn.apply(x.detach(), scale, shift, None, ctx.act, ctx.slope, ctx.eps, None)
                 _run_conv_wgrad(dd, hx, gy, dw, None, ws, nb, ctx.v_image)
 
             dw, _ = _wgrad_to_sink(ctx.desc, (weight,), launch)
@@ -1140,14 +1163,7 @@ class _NormActConvFn(Function):
         if ctx.needs_input_grad[0] or (scale is not None and ctx.needs_input_grad[1]):
             dh = torch.empty_like(x)
             _run_conv_dgrad(ctx.desc, gy, weight, dh)
-            dx = torch.empty_like(x)
-            dscale = torch.empty(n, c, dtype=torch.float32, device=x.device)
-            dshift = torch.empty_like(dscale)
-            nb = lib.srgan_instnorm_workspace(n, h * w, c)
-            ws = workspace(x.device, nb)
-            _lib.check(lib.srgan_instnorm_bwd(_ptr(x), _ptr(dh), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), _ptr(dx),
-                                              _ptr(dscale), _ptr(dshift), n, h * w, c, ctx.act, float(ctx.slope), _ptr(ws), nb,
-                                              _stream()), "instnorm_bwd")
+            dx, dscale, dshift = _instnorm_bwd(x, dh, scale, shift, mean, rstd, ctx.act, ctx.slope)
             if scale is None:
                 dscale = dshift = None
         return dx, dscale, dshift, dw, None, None, None
@@ -1190,14 +1206,7 @@ class _ResBlockFn(Function):
         y2 = nhwc_empty(n, w2.shape[0], h, w, dev)
         _lib.check(lib.srgan_conv2d_fwd_from_v(ctypes.byref(d2), _ptr(v1), _ptr(hit2.buf), None, _ptr(y2), ACT_NONE, 0.0, _stream()),
                    "conv2d_fwd_from_v")
-        c2 = w2.shape[0]
-        out = torch.empty_like(y2)
-        mean2 = torch.empty(n * c2, dtype=torch.float32, device=dev)
-        rstd2 = torch.empty_like(mean2)
-        nb = lib.srgan_instnorm_workspace(n, h * w, c2)
-        ws = workspace(dev, nb)
-        _lib.check(lib.srgan_instnorm_fwd(_ptr(y2), _ptr(s2), _ptr(h2), _ptr(x), _ptr(out), _ptr(mean2), _ptr(rstd2), n, h * w, c2,
-                                          float(eps), ACT_NONE, 0.0, _ptr(ws), nb, _stream()), "instnorm_fwd")
+        out, mean2, rstd2 = _instnorm_fwd(y2, s2, h2, x, ACT_NONE, 0.0, eps)
         ctx.d1, ctx.d2, ctx.w1, ctx.w2 = d1, d2, w1, w2
         ctx.v0, ctx.v1 = (v0, v1) if need_w else (None, None)
         ctx.save_for_backward(y1, y2, s1, h1, s2, h2, mean1, rstd1, mean2, rstd2)
@@ -1273,23 +1282,12 @@ class _ResBlockBf16Fn(Function):
         d2 = _conv_desc(n, h, w, c, h, w, c, 3, 3, 1, 1, PAD_ZERO, w2)
         hit1, _ = _packed(d, w1, 0, ACT_NONE)
         hit2, _ = _packed(d2, w2, 0, ACT_NONE)
-
-        def b16():
-            return torch.empty((n, h, w, c), dtype=torch.bfloat16, device=dev)
-
-        y1, hh, y2 = b16(), b16(), b16()
+        y1, y2 = (nhwc_empty(n, c, h, w, dev, torch.bfloat16) for _ in range(2))
         _lib.check(lib.srgan_halo16_conv(ctypes.byref(d), 0, _ptr(x), 0, _ptr(hit1.buf), None, _ptr(y1), 1, st), "halo16_conv")
-        mean1 = torch.empty(n * c, dtype=torch.float32, device=dev)
-        rstd1, mean2, rstd2 = torch.empty_like(mean1), torch.empty_like(mean1), torch.empty_like(mean1)
         # (the slab kernels on maps of <= 1024 pixels, the two-pass kernels with 16-bit I/O on the 64 x 64 trunk maps of 256 x 256)
-        nb = lib.srgan_instnorm_workspace(n, h * w, c)
-        ws = workspace(dev, nb)
-        _lib.check(lib.srgan_instnorm_fwd_io(_ptr(y1), 1, _ptr(s1), _ptr(h1), None, _ptr(hh), 1, _ptr(mean1), _ptr(rstd1),
-                                             n, h * w, c, float(eps), ACT_RELU, 0.0, _ptr(ws), nb, st), "instnorm_fwd_io")
+        hh, mean1, rstd1 = _instnorm_fwd(y1, s1, h1, None, ACT_RELU, 0.0, eps, torch.bfloat16)
         _lib.check(lib.srgan_halo16_conv(ctypes.byref(d2), 0, _ptr(hh), 1, _ptr(hit2.buf), None, _ptr(y2), 1, st), "halo16_conv")
-        out = torch.empty_like(x)
-        _lib.check(lib.srgan_instnorm_fwd_io(_ptr(y2), 1, _ptr(s2), _ptr(h2), _ptr(x), _ptr(out), 0, _ptr(mean2), _ptr(rstd2),
-                                             n, h * w, c, float(eps), ACT_NONE, 0.0, _ptr(ws), nb, st), "instnorm_fwd_io")
+        out, mean2, rstd2 = _instnorm_fwd(y2, s2, h2, x, ACT_NONE, 0.0, eps, torch.float32)
         ctx.d1, ctx.d2, ctx.w1, ctx.w2 = d, d2, w1, w2
         ctx.save_for_backward(x, y1, hh, y2, s1, h1, s2, h2, mean1, rstd1, mean2, rstd2)
         return out
@@ -1299,31 +1297,14 @@ class _ResBlockBf16Fn(Function):
         lib = _lib.load()
         x, y1, hh, y2, s1, h1, s2, h2, mean1, rstd1, mean2, rstd2 = ctx.saved_tensors
         g = to_nhwc(g)
-        n, c, h, w = x.shape
-        dev = g.device
         st = _stream()
         d1, d2, w1, w2 = ctx.d1, ctx.d2, ctx.w1, ctx.w2
-
-        def b16():
-            return torch.empty((n, h, w, c), dtype=torch.bfloat16, device=dev)
-
-        def norm_bwd(y, gup, gup16, sc, sh, mean, rstd, act):
-            dy = b16()
-            dsc = torch.empty(n, c, dtype=torch.float32, device=dev)
-            dsh = torch.empty_like(dsc)
-            nb = lib.srgan_instnorm_workspace(n, h * w, c)
-            ws = workspace(dev, nb)
-            _lib.check(lib.srgan_instnorm_bwd_io(_ptr(y), 1, _ptr(gup), gup16, _ptr(sc), _ptr(sh), _ptr(mean), _ptr(rstd),
-                                                 _ptr(dy), 1, _ptr(dsc), _ptr(dsh), n, h * w, c, act, 0.0, _ptr(ws), nb, st),
-                       "instnorm_bwd_io")
-            return dy, dsc, dsh
-
-        dy2, ds2, dh2 = norm_bwd(y2, g, 0, s2, h2, mean2, rstd2, ACT_NONE)
+        dy2, ds2, dh2 = _instnorm_bwd(y2, g, s2, h2, mean2, rstd2, ACT_NONE, 0.0, io=True)
         dw2 = _io_wgrad(_PatchRoute, d2, w2, hh, dy2) if ctx.needs_input_grad[6] else None
         hit2, _ = _packed(d2, w2, 1, ACT_NONE)
-        dh = b16()
+        dh = torch.empty_like(dy2)
         _lib.check(lib.srgan_halo16_conv(ctypes.byref(d2), 1, _ptr(dy2), 1, _ptr(hit2.buf), None, _ptr(dh), 1, st), "halo16_conv")
-        dy1, ds1, dh1 = norm_bwd(y1, dh, 1, s1, h1, mean1, rstd1, ACT_RELU)
+        dy1, ds1, dh1 = _instnorm_bwd(y1, dh, s1, h1, mean1, rstd1, ACT_RELU, 0.0, io=True)
         dw1 = _io_wgrad(_PatchRoute, d1, w1, x, dy1) if ctx.needs_input_grad[5] else None
         dx = None
         if ctx.needs_input_grad[0]:
@@ -1534,43 +1515,6 @@ class _ConvBf16Fn(Function):
         return dx, dw, None, None, None, None, None, None, None, None, None
 
 
-class _InstNormIoFn(Function):
-    """instance_norm_act with an fp32 or bf16 input and a bf16 or fp32 output (no residual); dx has x's type."""
-
-    @staticmethod
-    def forward(ctx, x, scale, shift, act, slope, eps, out_bf16):
-        x = to_nhwc(x)
-        n, c, h, w = x.shape
-        lib = _lib.load()
-        y = nhwc_empty(n, c, h, w, x.device, torch.bfloat16 if out_bf16 else torch.float32)
-        mean = torch.empty(n * c, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        nb = lib.srgan_instnorm_workspace(n, h * w, c)
-        ws = workspace(x.device, nb)
-        _lib.check(lib.srgan_instnorm_fwd_io(_ptr(x), _is16(x), _ptr(scale), _ptr(shift), None, _ptr(y), _is16(y), _ptr(mean), _ptr(rstd),
-                                             n, h * w, c, float(eps), act, float(slope), _ptr(ws), nb, _stream()), "instnorm_fwd_io")
-        ctx.act, ctx.slope = act, slope
-        ctx.save_for_backward(x, scale, shift, mean, rstd)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, scale, shift, mean, rstd = ctx.saved_tensors
-        gy = to_nhwc(gy)
-        n, c, h, w = x.shape
-        lib = _lib.load()
-        dx = torch.empty_like(x)
-        dscale = torch.empty(n, c, dtype=torch.float32, device=x.device)
-        dshift = torch.empty_like(dscale)
-        nb = lib.srgan_instnorm_workspace(n, h * w, c)
-        ws = workspace(x.device, nb)
-        _lib.check(lib.srgan_instnorm_bwd_io(_ptr(x), _is16(x), _ptr(gy), _is16(gy), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd),
-                                             _ptr(dx), _is16(dx), _ptr(dscale), _ptr(dshift), n, h * w, c, ctx.act, float(ctx.slope),
-                                             _ptr(ws), nb, _stream()), "instnorm_bwd_io")
-        has_aff = scale is not None
-        return dx, dscale if has_aff else None, dshift if has_aff else None, None, None, None, None
-
-
 def conv2d_s2_io(x, weight, out_bf16):
     return _ConvBf16Fn.apply(x, weight, _PatchRoute, False, (4, 4), 2, 1, PAD_ZERO, ACT_NONE, 0.0, bool(out_bf16))
 
@@ -1588,7 +1532,8 @@ def conv2d_act_io(x, weight, act, slope, out_bf16, k=4, stride=2, pad=1):
 
 
 def instance_norm_act_io(x, scale, shift, act=ACT_NONE, slope=0.0, eps=1e-5, out_bf16=False):
-    return _InstNormIoFn.apply(x, scale, shift, act, slope, eps, bool(out_bf16))
+    """instance_norm_act with an fp32 or bf16 input and a bf16 or fp32 output (no residual); dx has x's type."""
+    return _InstNormFn.apply(x, scale, shift, None, act, slope, eps, torch.bfloat16 if out_bf16 else torch.float32)
 
 
 class _AvgPool2IoFn(Function):

@@ -91,6 +91,107 @@ def test_invalid_arguments_are_reported_without_a_gpu(built_lib):
         assert lib.srgan_set_compute_mode(0) == 0
 
 
+def test_instance_norm_entries_refuse_what_they_refused(built_lib):
+    """Every refusal of the six instance-norm entries (csrc/norm.hip): -1, the entry's own message, and the order in which the
+    conditions are tested.  Fake pointers; every call here is refused before a launch."""
+    import ctypes
+    lib = built_lib.load()
+    x, y, r, g, d, m, s, a, b = (ctypes.cast((ctypes.c_char * 64)(), ctypes.c_void_p) for _ in range(9))
+    ws = (ctypes.c_char * 64)()
+    SLAB, TWO, ODD = (32, 63, 128), (2, 81, 16), (2, 81, 12)       # slab kernels; two-pass with the pow2 finish; fp32 entries only
+    assert lib.srgan_instnorm_slab_applicable(*SLAB) == 1 and lib.srgan_instnorm_slab_applicable(*TWO) == 0
+    assert lib.srgan_instnorm_io_applicable(*SLAB) == 1 and lib.srgan_instnorm_io_applicable(*TWO) == 1
+    assert lib.srgan_instnorm_io_applicable(*ODD) == 0
+    need = {shape: lib.srgan_instnorm_workspace(*shape) for shape in (SLAB, TWO, ODD)}
+    assert all(v > 64 for v in need.values())
+
+    def refused(rc, message):
+        assert rc == -1 and lib.srgan_last_error() == message.encode(), (rc, lib.srgan_last_error(), message)
+
+    # ---- forward ----
+    def fwd(shape, x=x, scale=a, shift=b, res=None, y=y, mean=m, rstd=s, ws=ws, nb=None):
+        return lib.srgan_instnorm_fwd(x, scale, shift, res, y, mean, rstd, *shape, 1e-5, 0, 0.0, ws, need[shape] if nb is None else nb, None)
+
+    def slab_fwd(shape, x=x, scale=a, shift=b, res=None, y=y, y16=0, mean=m, rstd=s):
+        return lib.srgan_instnorm_slab_fwd_io(x, 1, scale, shift, res, y, y16, mean, rstd, *shape, 1e-5, 0, 0.0, None)
+
+    def fwd_io(shape, x=x, scale=a, shift=b, res=None, y=y, y16=0, mean=m, rstd=s, ws=ws, nb=None):
+        return lib.srgan_instnorm_fwd_io(x, 1, scale, shift, res, y, y16, mean, rstd, *shape, 1e-5, 0, 0.0, ws,
+                                         need[shape] if nb is None else nb, None)
+
+    for name, call in (("instnorm_fwd", fwd), ("instnorm_slab_fwd_io", slab_fwd), ("instnorm_fwd_io", fwd_io)):
+        for shape in (SLAB, TWO) if call is not slab_fwd else (SLAB,):
+            for missing in ("x", "y", "mean", "rstd"):
+                refused(call(shape, **{missing: None}), name + ": null pointer")
+    for shape in ((0, 81, 16), (2, 0, 16), (2, 81, 0)):
+        need[shape] = 0
+        refused(fwd(shape), "instnorm_fwd: bad shape")
+        refused(fwd(shape, shift=None), "instnorm_fwd: bad shape")                         # (tested before the affine pair)
+    for shape in (SLAB, TWO, ODD):
+        refused(fwd(shape, shift=None), "instnorm_fwd: scale and shift go together")
+        refused(fwd(shape, scale=None, ws=None), "instnorm_fwd: scale and shift go together")
+        refused(fwd(shape, ws=None), "instnorm_fwd: workspace too small")                  # (on a slab shape too)
+        refused(fwd(shape, nb=need[shape] - 1), "instnorm_fwd: workspace too small")
+    refused(slab_fwd(SLAB, shift=None), "instnorm_slab_fwd_io: scale and shift go together")
+    refused(slab_fwd(TWO, scale=None), "instnorm_slab_fwd_io: scale and shift go together")  # (tested before the shape)
+    for shape in (TWO, ODD):
+        refused(slab_fwd(shape), "instnorm_slab_fwd_io: shape not served by the slab kernels (srgan_instnorm_slab_applicable)")
+        refused(slab_fwd(shape, res=r, y16=1), "instnorm_slab_fwd_io: shape not served by the slab kernels (srgan_instnorm_slab_applicable)")
+    refused(slab_fwd(SLAB, res=r, y16=1), "instnorm_slab_fwd_io: the skip tensor is added to an fp32 result only")
+    refused(fwd_io(ODD), "instnorm_fwd_io: shape not served (srgan_instnorm_io_applicable)")
+    refused(fwd_io(ODD, y=x), "instnorm_fwd_io: shape not served (srgan_instnorm_io_applicable)")
+    refused(fwd_io((0, 81, 16)), "instnorm_fwd_io: shape not served (srgan_instnorm_io_applicable)")
+    for shape in (SLAB, TWO):
+        refused(fwd_io(shape, y=x), "instnorm_fwd_io: in-place calls are not supported")
+        refused(fwd_io(shape, res=y), "instnorm_fwd_io: in-place calls are not supported")
+        refused(fwd_io(shape, res=y, y16=1), "instnorm_fwd_io: in-place calls are not supported")
+        refused(fwd_io(shape, res=r, y16=1), "instnorm_fwd_io: the skip tensor is added to an fp32 result only")
+        refused(fwd_io(shape, res=r, y16=1, shift=None, ws=None), "instnorm_fwd_io: the skip tensor is added to an fp32 result only")
+    # an io call on a slab shape is the slab entry's from here on: no workspace is asked for, and the slab entry's messages come back
+    refused(fwd_io(SLAB, shift=None, ws=None, nb=0), "instnorm_slab_fwd_io: scale and shift go together")
+    refused(fwd_io(TWO, shift=None, ws=None, nb=0), "instnorm_fwd_io: scale and shift go together")
+    refused(fwd_io(TWO, ws=None), "instnorm_fwd_io: workspace too small (srgan_instnorm_workspace)")
+    refused(fwd_io(TWO, nb=need[TWO] - 1), "instnorm_fwd_io: workspace too small (srgan_instnorm_workspace)")
+
+    # ---- backward ----
+    def bwd(shape, x=x, dy=g, scale=a, shift=b, mean=m, rstd=s, dx=d, dscale=y, dshift=r, ws=ws, nb=None):
+        return lib.srgan_instnorm_bwd(x, dy, scale, shift, mean, rstd, dx, dscale, dshift, *shape, 0, 0.0, ws,
+                                      need[shape] if nb is None else nb, None)
+
+    def slab_bwd(shape, x=x, x16=1, dy=g, scale=a, shift=b, mean=m, rstd=s, dx=d, dx16=1, dscale=y, dshift=r):
+        return lib.srgan_instnorm_slab_bwd_io(x, x16, dy, 0, scale, shift, mean, rstd, dx, dx16, dscale, dshift, *shape, 0, 0.0, None)
+
+    def bwd_io(shape, x=x, x16=1, dy=g, scale=a, shift=b, mean=m, rstd=s, dx=d, dx16=1, dscale=y, dshift=r, ws=ws, nb=None):
+        return lib.srgan_instnorm_bwd_io(x, x16, dy, 0, scale, shift, mean, rstd, dx, dx16, dscale, dshift, *shape, 0, 0.0, ws,
+                                         need[shape] if nb is None else nb, None)
+
+    for name, call in (("instnorm_bwd", bwd), ("instnorm_slab_bwd_io", slab_bwd), ("instnorm_bwd_io", bwd_io)):
+        for shape in (SLAB, TWO) if call is not slab_bwd else (SLAB,):
+            for missing in ("x", "dy", "mean", "rstd", "dx", "dscale", "dshift"):
+                refused(call(shape, **{missing: None}), name + ": null pointer")
+    for shape in (SLAB, TWO, ODD):
+        refused(bwd(shape, shift=None), "instnorm_bwd: scale and shift go together")
+        refused(bwd(shape, scale=None, ws=None), "instnorm_bwd: scale and shift go together")
+        refused(bwd(shape, ws=None), "instnorm_bwd: workspace too small")
+        refused(bwd(shape, nb=need[shape] - 1), "instnorm_bwd: workspace too small")
+    refused(slab_bwd(SLAB, shift=None), "instnorm_slab_bwd_io: scale and shift go together")
+    refused(slab_bwd(TWO, scale=None), "instnorm_slab_bwd_io: scale and shift go together")
+    for shape in (TWO, ODD):
+        refused(slab_bwd(shape), "instnorm_slab_bwd_io: shape not served by the slab kernels (srgan_instnorm_slab_applicable)")
+        refused(slab_bwd(shape, dx16=0), "instnorm_slab_bwd_io: shape not served by the slab kernels (srgan_instnorm_slab_applicable)")
+    refused(slab_bwd(SLAB, dx16=0), "instnorm_slab_bwd_io: the input gradient has the input's type")
+    refused(slab_bwd(SLAB, x16=0), "instnorm_slab_bwd_io: the input gradient has the input's type")
+    refused(bwd_io(ODD), "instnorm_bwd_io: shape not served (srgan_instnorm_io_applicable)")
+    refused(bwd_io(ODD, dx16=0), "instnorm_bwd_io: shape not served (srgan_instnorm_io_applicable)")
+    for shape in (SLAB, TWO):
+        refused(bwd_io(shape, dx16=0), "instnorm_bwd_io: the input gradient has the input's type")
+        refused(bwd_io(shape, x16=0, shift=None, ws=None), "instnorm_bwd_io: the input gradient has the input's type")
+    refused(bwd_io(SLAB, shift=None, ws=None, nb=0), "instnorm_slab_bwd_io: scale and shift go together")
+    refused(bwd_io(TWO, shift=None, ws=None, nb=0), "instnorm_bwd_io: scale and shift go together")
+    refused(bwd_io(TWO, ws=None), "instnorm_bwd_io: workspace too small (srgan_instnorm_workspace)")
+    refused(bwd_io(TWO, nb=need[TWO] - 1), "instnorm_bwd_io: workspace too small (srgan_instnorm_workspace)")
+
+
 def test_launch_timer_kernel_ids_and_names(built_lib):
     """bench.py (is_hbm_kernel, executed_divisor), tests/step_bits_common.py and the scripts under scratch/ select timed kernels by
     these names, and a launch site books its time by position in this list: number, spelling and order are part of the ABI."""

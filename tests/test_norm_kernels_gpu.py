@@ -139,6 +139,89 @@ def test_instance_norm_act_on_hostile_inputs(ops, shape, kind):
     _hold_fp32(ops, what, shape, x, True, True, nc.ACT_NONE)
 
 
+# ---- one launch path behind the six entries ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(32, 128, 7, 9), (2, 16, 9, 9)], ids=nc.hostile_id)      # slab R = 1; two-pass, pow2 finish, last block partial
+def test_fp32_and_io_entries_agree_bit_for_bit_on_fp32_tensors(ops, shape):
+    """ops.instance_norm_act (srgan_instnorm_fwd / _bwd) and ops.instance_norm_act_io with fp32 tensors on both sides
+    (srgan_instnorm_fwd_io / _bwd_io) launch the same instantiations with the same grids and arguments
+    (norm_common.launch_plan), and the kernels reduce in a fixed order: equal bits, not close values."""
+    assert nc.launch_plan(shape, False) == nc.launch_plan(shape, False, (False, False))
+    assert nc.launch_plan(shape, True) == nc.launch_plan(shape, True, (False, False))
+    x, gout = nc.default_input(shape), nc.upstream(shape)
+    for affine, act in nc.IO_COMBOS:
+        scale, shift, _ = nc.case_params(shape, affine, False)
+        got = []
+        for io in (False, True):
+            xd = _nhwc_dev(x, torch.float32).requires_grad_(True)
+            scd, shd = (t.cuda().requires_grad_(True) for t in (scale, shift)) if affine else (None, None)
+            y = (ops.instance_norm_act_io(xd, scd, shd, act, nc.SLOPE, nc.EPS, False) if io else
+                 ops.instance_norm_act(xd, scd, shd, None, act, nc.SLOPE, nc.EPS))
+            assert y.dtype == torch.float32
+            got.append([y.detach(), *torch.autograd.grad(y, [xd, scd, shd] if affine else [xd], _nhwc_dev(gout, torch.float32))])
+        for name, a, b in zip(("y", "dx", "dscale", "dshift"), *got):
+            assert bool(torch.isfinite(a).all()) and torch.equal(a, b), f"{shape} affine={int(affine)} act={act} {name}"
+
+
+def test_slab_entries_are_the_slab_branch_of_the_io_entries(ops):
+    """srgan_instnorm_slab_fwd_io / _slab_bwd_io called directly, bf16 x, y, dy and dx: the bits of srgan_instnorm_fwd_io /
+    _bwd_io on the same tensors."""
+    from srgan_amd import _lib
+    lib = _lib.load()
+    shape = (32, 128, 8, 16)
+    N, C, H, W = shape
+    assert nc.features(shape)["kind"] == "slab"
+    p, st = ops._ptr, ops._stream()
+    x = _nhwc_dev(nc.default_input(shape), torch.bfloat16)
+    dy = _nhwc_dev(nc.upstream(shape), torch.bfloat16)
+    scale, shift = (t.cuda() for t in nc.case_params(shape, True, False)[:2])
+    nb = lib.srgan_instnorm_workspace(N, H * W, C)
+    ws = ops.workspace(x.device, nb)
+
+    def blank(like=None):              # NaN everywhere: an element that no kernel wrote fails the comparison
+        return torch.full_like(like, float("nan")) if like is not None else torch.full((N * C,), float("nan"), device="cuda")
+
+    out = []
+    for slab in (True, False):
+        y, mean, rstd = blank(x), blank(), blank()
+        head = (p(x), 1, p(scale), p(shift), None, p(y), 1, p(mean), p(rstd), N, H * W, C, nc.EPS, nc.ACT_LRELU, nc.SLOPE)
+        _lib.check(lib.srgan_instnorm_slab_fwd_io(*head, st) if slab else lib.srgan_instnorm_fwd_io(*head, p(ws), nb, st), "forward")
+        dx, dscale, dshift = blank(x), blank(), blank()
+        head = (p(x), 1, p(dy), 1, p(scale), p(shift), p(mean), p(rstd), p(dx), 1, p(dscale), p(dshift), N, H * W, C, nc.ACT_LRELU, nc.SLOPE)
+        _lib.check(lib.srgan_instnorm_slab_bwd_io(*head, st) if slab else lib.srgan_instnorm_bwd_io(*head, p(ws), nb, st), "backward")
+        out.append((y, mean, rstd, dx, dscale, dshift))
+    for name, a, b in zip(("y", "mean", "rstd", "dx", "dscale", "dshift"), *out):
+        assert bool(torch.isfinite(a.float()).all()) and torch.equal(a, b), name
+
+
+@pytest.mark.parametrize("alias", ["y_is_x", "res_is_y"])
+def test_instance_norm_forward_in_place(ops, alias):
+    """srgan_instnorm_fwd with y == x, and with the skip tensor overwritten by the result: the fused finish of the pow2 apply
+    pass would re-read pixel 0 of x while another workgroup stores y there, so these calls take the separate finalize launch
+    and in_apply_pow2 without partial sums.  Same yardstick as the out-of-place call; the references use the inputs as they
+    were before the call."""
+    from srgan_amd import _lib
+    lib = _lib.load()
+    shape, act = (2, 16, 9, 9), nc.ACT_LRELU
+    N, C, H, W = shape
+    f = nc.features(shape)
+    assert f["kind"] == "two-pass" and f["finish"] == "pow2"
+    x = nc.default_input(shape)
+    scale, shift, res = nc.case_params(shape, True, alias == "res_is_y")
+    r64, r32 = nc.yardstick(nc.norm_ref(act), (x, scale, shift, res), (False,) * 4)
+    xd = _nhwc_dev(x, torch.float32)
+    y = xd if alias == "y_is_x" else _nhwc_dev(res, torch.float32)
+    resd = None if alias == "y_is_x" else y
+    scd, shd = scale.cuda(), shift.cuda()
+    mean = torch.empty(N * C, device="cuda")
+    rstd = torch.empty_like(mean)
+    nb = lib.srgan_instnorm_workspace(N, H * W, C)
+    ws = ops.workspace(xd.device, nb)
+    p = ops._ptr
+    _lib.check(lib.srgan_instnorm_fwd(p(xd), p(scd), p(shd), p(resd), p(y), p(mean), p(rstd), N, H * W, C, nc.EPS, act, nc.SLOPE,
+                                      p(ws), nb, ops._stream()), "instnorm_fwd")
+    nc.check("instnorm_fwd", f"in place ({alias}) y", y, r64[0], r32[0], nc.path_L(shape))
+
+
 # ---- CBIN affine -------------------------------------------------------------------------------------------------------------------------
 CBIN_NAMES = ("scale", "shift", "dc", "dW", "db", "dgamma", "dbeta")
 
