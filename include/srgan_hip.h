@@ -700,6 +700,38 @@ int srgan_d_losses_cr(const float* const* o, const long long* per_row, const flo
                       int n_class, const long long* label, float t_first, float t_rest, float w_class, int gan_kind, int class_kind,
                       float* vals, float* const* d_o, float* const* dz, int pairs, int pairs_first, void* state, void* stream);
 
+/* LeCam regularisation of the discriminator (Tseng et al., CVPR 2021, "Regularizing Generative Adversarial Networks under Limited
+ * Data").  Extension, no counterpart in the reference.  One launch per discriminator update, behind srgan_d_losses_crit or
+ * srgan_d_losses_cr, on the maps o[s] [rows, per_row[s]] and the d_o[s] that call wrote.  The front `pairs` rows are what D reads
+ * anyway: their first rows_first rows are real, the other pairs - rows_first generated; with rows = 2 * pairs the back rows (the
+ * consistency partners) and their d_o are never touched.  n1 = rows_first per_row[s], n2 = (pairs - rows_first) per_row[s].
+ * Record (srgan_lc_state_bytes() = 56 bytes, device memory): {float weight, float decay, int start, int updates, float a_real[4],
+ * float a_fake[4], float penalty, int applied}.  srgan_lc_state_init writes the three settings and zeroes the rest;
+ * srgan_lc_state_set rewrites the three settings between steps and keeps the rest (a recorded step reads them from the record);
+ * srgan_lc_state_restore writes updates and the anchors (two HOST arrays of 4 floats) and nothing else (resuming from a
+ * checkpoint).  One launch each.  -1 before any launch: a NULL record or array, weight < 0 or not finite, decay outside [0, 1),
+ * start < 0, updates < 0, an anchor not finite, NaN anywhere.
+ * srgan_lecam: ONE launch, one workgroup, no atomics, every sum in a fixed order (csrc/lecam.hip), no fused multiply-add.
+ *   means     m_R,s / m_F,s = the fp32 mean of o[s] over the real / generated elements.
+ *   anchors   with n = updates and d = (n == 0 ? 0 : decay): a_R,s <- d a_R,s + (1 - d) m_R,s, likewise a_F,s.  If any of the 2S means
+ *             is not finite no anchor moves and updates stays; otherwise updates += 1.  An empty group (rows_first == 0 or == pairs)
+ *             has no mean: its anchor stays and its half of the term is left out.
+ *   term      R = (1 / S) sum_s [ mean_real phi(o - a_F,s)^2 + mean_fake phi(a_R,s - o)^2 ] with the UPDATED anchors as constants;
+ *             phi = identity (clamp 0) or max(., 0) (clamp 1, NaN kept).
+ *   gradient  active = weight != 0 && n >= start.  Active: a real element's d_o += 2 weight / (S n1) phi(o - a_F,s), a generated one's
+ *             d_o -= 2 weight / (S n2) phi(a_R,s - o).  Not active: d_o is neither read nor written -- a select, not a product with 0.
+ *   vals[3] = {R, active ? weight R : 0, active ? *total_in + weight R : *total_in (its bits)}; the record's penalty = R, applied =
+ *   active.  total_in may point into the vals of the loss call before; it must not overlap this call's vals.
+ * 16-byte accesses on map s when o[s] and d_o[s] are 16-byte aligned and per_row[s] % 4 == 0, else 4-byte ones: same bits.
+ * -1 with srgan_last_error() before any launch: a NULL pointer, n_scales outside [1, 4], pairs < 1, rows neither pairs nor 2 * pairs,
+ * rows_first outside [0, pairs], clamp not 0 / 1, per_row[s] <= 0, rows * per_row[s] >= 2^31, a pointer not 4-byte aligned. */
+size_t srgan_lc_state_bytes(void);
+int srgan_lc_state_init(void* state, float weight, float decay, int start, void* stream);
+int srgan_lc_state_set(void* state, float weight, float decay, int start, void* stream);
+int srgan_lc_state_restore(void* state, int updates, const float* a_real, const float* a_fake, void* stream);
+int srgan_lecam(const float* const* o, const long long* per_row, int n_scales, int rows, int pairs, int rows_first, int clamp,
+                const float* total_in, float* vals, float* const* d_o, void* state, void* stream);
+
 /* Mode-seeking (diversity) regularisation of the generator: restates lossModeSeeking of MSGAN (Mao et al., CVPR 2019:
  * 1 / (mean|I1 - I2| / mean|z1 - z2| + eps)) and the per-sample clamped term of DSGAN (Yang et al., ICLR 2019:
  * -mean_i min(mean|I1_i - I2_i| / mean|z1_i - z2_i|, tau)).  Extension, no counterpart in the reference.

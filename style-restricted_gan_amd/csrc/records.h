@@ -8,7 +8,7 @@
 
 namespace srgan {
 
-constexpr int kRecordWords = 16;                      // 32-bit words of the image a write carries: the largest record has 14
+constexpr int kRecordWords = 16;                      // 32-bit words of the image a write carries: the largest of the eight records (AdaState, LcState) have 14
 struct RecordImage { unsigned int w[kRecordWords]; };
 
 // Bit i = word i of the record: a field of kSize bytes at kOffset yields kSize / 4 adjacent bits (two for a 64-bit field).
@@ -70,5 +70,13 @@ static_assert(sizeof(MsState) == 32, "MsState layout");
 constexpr unsigned kMsSet = SRGAN_WORDS(MsState, weight) | SRGAN_WORDS(MsState, eps) | SRGAN_WORDS(MsState, tau);
 constexpr unsigned kMsRestore = SRGAN_WORDS(MsState, updates) | SRGAN_WORDS(MsState, ms) | SRGAN_WORDS(MsState, d_image) |
                                 SRGAN_WORDS(MsState, d_latent);
+
+// weight, decay, start are written by the host between steps; updates counts the anchor updates, a_real / a_fake are the anchors
+// per scale (exponential moving averages of D's mean prediction), penalty the unweighted term and applied (0 / 1) whether its
+// gradient was added, both of the last srgan_lecam.  A restore writes the counter and the anchors.
+struct LcState { float weight; float decay; int start; int updates; float a_real[4]; float a_fake[4]; float penalty; int applied; };
+static_assert(sizeof(LcState) == 56, "LcState layout");
+constexpr unsigned kLcSet = SRGAN_WORDS(LcState, weight) | SRGAN_WORDS(LcState, decay) | SRGAN_WORDS(LcState, start);
+constexpr unsigned kLcRestore = SRGAN_WORDS(LcState, updates) | SRGAN_WORDS(LcState, a_real) | SRGAN_WORDS(LcState, a_fake);
 
 }  // namespace srgan

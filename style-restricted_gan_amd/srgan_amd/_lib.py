@@ -56,6 +56,8 @@ CrState = _record("CrState", lambda_real=c_float, lambda_fake=c_float, every=c_i
                   updates=c_int, _pad=c_int * 2)
 MsState = _record("MsState", weight=c_float, eps=c_float, tau=c_float, ms=c_float, weighted=c_float, d_image=c_float,
                   d_latent=c_float, updates=c_int)
+LcState = _record("LcState", weight=c_float, decay=c_float, start=c_int, updates=c_int, a_real=c_float * 4, a_fake=c_float * 4,
+                  penalty=c_float, applied=c_int)
 
 P = c_void_p
 _DESC = POINTER(ConvDesc)
@@ -241,6 +243,12 @@ SIGNATURES = {
     "srgan_cr_state_set_updates": (c_int, [P, c_int, P]),
     "srgan_d_losses_cr": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, c_float, c_float, c_float, c_int, c_int, P, P, P, c_int, c_int,
                                   P, P]),
+    # LeCam regularisation of the discriminator (csrc/lecam.hip)
+    "srgan_lc_state_bytes": (c_size_t, []),
+    "srgan_lc_state_init": (c_int, [P, c_float, c_float, c_int, P]),
+    "srgan_lc_state_set": (c_int, [P, c_float, c_float, c_int, P]),
+    "srgan_lc_state_restore": (c_int, [P, c_int, P, P, P]),
+    "srgan_lecam": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
     # mode-seeking regularisation of the generator (csrc/diversity.hip)
     "srgan_ms_state_bytes": (c_size_t, []),
     "srgan_ms_state_init": (c_int, [P, c_float, c_float, c_float, P]),

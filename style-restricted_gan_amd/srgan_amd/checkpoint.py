@@ -11,10 +11,10 @@ dict`` -- a file written from it loads with ``torch.load(path, weights_only=True
     optG/D/E, scheG/D/E      ``state_dict()`` of the optimisers and schedulers (lists where the trainer keeps lists)
     hist_target              the histogram-imitation target the constructor drew (``lbd["hist"] > 0``)
     ema, augment, geometry,  the step's extensions that are on: the averaged copies and their update count, DiffAugment's settings
-    ada, r1, bcr,            and generator, the geometric stage's settings and generator, the adaptive probability's settings and
+    ada, r1, bcr, lecam,     and generator, the geometric stage's settings and generator, the adaptive probability's settings and
     mode_seeking, grad_guard whole record (p, seen, the three counts, adjustments, last_r, the record's batch size n), R1's
                              gamma / every / updates (and the record's batch size n), consistency regularisation's weights / every /
-                             policy / translation / generator / updates, mode seeking's weight / form / eps / tau / generator /
+                             policy / translation / generator / updates, LeCam's weight / decay / start / clamp / anchors / updates, mode seeking's weight / form / eps / tau / generator /
                              updates and last ms / d_image / d_latent, per guarded net max_norm and the cumulative steps / skipped /
                              clipped
     rng                      the CPU default generator (style and reparametrisation noise) and numpy's global one (``get_target``)
@@ -45,7 +45,7 @@ LoadReport.__doc__ = """Sections the trainer has but the checkpoint lacks (they 
 use for (skipped)."""
 
 _NETS = ("G", "D", "E")
-_EXTENSIONS = ("ema", "augment", "geometry", "ada", "r1", "bcr", "mode_seeking", "grad_guard")
+_EXTENSIONS = ("ema", "augment", "geometry", "ada", "r1", "bcr", "lecam", "mode_seeking", "grad_guard")
 # the augmentation stages (srgan_amd.augment): (section, the trainer attribute the stage lives in, the switch that makes one, the keys
 # of a saved section the switch takes, in its order), in the order of application
 _STAGES = (("augment", "augment", "enable_diffaugment", ("policy", "translation", "cutout")),
@@ -137,7 +137,7 @@ class Checkpointing:
         if getattr(self, "hi", None) is not None:
             out.append("hist_target")
         for name, attr in (("ema", "_ema"), *(s[:2] for s in _STAGES), ("ada", "_ada"), ("r1", "_r1"), ("bcr", "bcr"),
-                           ("mode_seeking", "_ms")):
+                           ("lecam", "_lecam"), ("mode_seeking", "_ms")):
             if getattr(self, attr, None) is not None:
                 out.append(name)
         out += [f"grad_guard.{n}" for n in self._ckpt_guards()]
@@ -163,7 +163,7 @@ class Checkpointing:
     # ---- save ---------------------------------------------------------------------------------------------------------------------
     def state_dict(self, rng=True):
         """A snapshot of everything the next ``train()`` depends on (module docstring): CPU clones and plain values.  Between steps
-        only; reads the adaptive-probability, R1, consistency, mode-seeking and gradient-guard records, so it SYNCHRONISES the stream.  ``rng=False`` leaves the two host
+        only; reads the adaptive-probability, R1, consistency, LeCam, mode-seeking and gradient-guard records, so it SYNCHRONISES the stream.  ``rng=False`` leaves the two host
         generators out.  Per process: no collective."""
         self._ckpt_between_steps("state_dict")
         sd = {"version": VERSION, "config": self._ckpt_config()}
@@ -189,6 +189,8 @@ class Checkpointing:
                         "n": None if st["n"] is None else int(st["n"])}
         if getattr(self, "bcr", None) is not None:
             sd["bcr"] = _plain(self.bcr.state_dict(), "bcr")
+        if getattr(self, "_lecam", None) is not None:
+            sd["lecam"] = _plain(self._lecam.state_dict(), "lecam")
         if getattr(self, "_ms", None) is not None:
             sd["mode_seeking"] = _plain(self._ms.state_dict(), "mode_seeking")
         guards = self._ckpt_guards()
@@ -247,7 +249,7 @@ class Checkpointing:
         fields BEFORE anything is written.  A recording of the step and the warm-up of its input shape are forgotten (torch's
         optimiser load replaces the moment tensors a recording points at): the next step runs eagerly, the one after records
         again; graph mode stays enabled.  Cached packed operands of every network and of the averaged copies are marked stale.
-        ``ema_updates``, ``grad_guard_stats()``, ``r1_stats()``, ``bcr_stats()`` and ``mode_seeking_stats()`` continue from the saved
+        ``ema_updates``, ``grad_guard_stats()``, ``r1_stats()``, ``bcr_stats()``, ``lecam_stats()`` and ``mode_seeking_stats()`` continue from the saved
         counts."""
         self._ckpt_between_steps("load_state_dict")
         who = type(self).__name__
@@ -325,6 +327,11 @@ class Checkpointing:
             if self.bcr is None or self.bcr.every != int(c["every"]):
                 self.enable_bcr(c["lambda_real"], c["lambda_fake"], int(c["every"]), c["policy"], c["translation"])
             self.bcr.load_state_dict(c, next(dp.unwrap(self.D).parameters()).device)
+        if use("lecam"):
+            c = sd["lecam"]
+            if self._lecam is None or self._lecam.clamp != bool(c["clamp"]):
+                self.enable_lecam(c["weight"], c["decay"], int(c["start"]), bool(c["clamp"]))
+            self._lecam.load_state_dict(c, next(dp.unwrap(self.D).parameters()).device)
         if use("mode_seeking"):
             m = sd["mode_seeking"]
             if self._ms is None or self._ms.form != m["form"]:

@@ -2180,9 +2180,60 @@ def crit_pair(a, b, weight=1.0, kind=CRIT_MSE):
     return _CritPairFn.apply(a, b, weight, _crit_kind(kind, "crit_pair"))
 
 
+# ---- LeCam regularisation of the discriminator (srgan_amd.lecam; extension, no counterpart in the reference) ----
+LC_MAX_SCALES = 4              # anchors per group in the record
+
+
+def lc_state_new(device, weight, decay, start):
+    """Device-resident record {weight, decay, start, updates, a_real[4], a_fake[4], penalty, applied}, all but the settings at zero."""
+    return _record_new(_lib.LcState, device, "lc_state_init", float(weight), float(decay), int(start))
+
+
+def lc_state_set(state, weight, decay, start):
+    """Rewrite the three settings between steps; the counter and the anchors stay (a recorded step reads the record)."""
+    _record_call("lc_state_set", state, float(weight), float(decay), int(start))
+
+
+def lc_state_restore(state, updates, a_real, a_fake):
+    """Write a checkpoint's count of anchor updates and the anchors (four per group) between steps; everything else stays."""
+    a_real, a_fake = [float(v) for v in a_real], [float(v) for v in a_fake]
+    if len(a_real) != LC_MAX_SCALES or len(a_fake) != LC_MAX_SCALES:
+        raise _lib.SrganHipError(f"lc_state_restore: {len(a_real)} / {len(a_fake)} anchors ({LC_MAX_SCALES} per group)")
+    arr = ctypes.c_float * LC_MAX_SCALES
+    _record_call("lc_state_restore", state, int(updates), arr(*a_real), arr(*a_fake))
+
+
+def lc_state_read(state):
+    """The record as a dict (the anchors as lists of four floats); synchronises the current stream."""
+    rec = _record_read(_lib.LcState, state)
+    rec["a_real"], rec["a_fake"] = list(rec["a_real"]), list(rec["a_fake"])
+    return rec
+
+
+def _lecam_arg(lecam, who):
+    """``None``, or ``(record, clamp)`` as ``(record, 0 / 1)``"""
+    if lecam is None:
+        return None
+    state, clamp = lecam
+    if not torch.is_tensor(state) or state.dtype != torch.uint8 or state.numel() != ctypes.sizeof(_lib.LcState):
+        raise _lib.SrganHipError(f"{who}: lecam = (record, clamp) with a record of lc_state_new")
+    return state, int(bool(clamp))
+
+
+def _lecam_launch(lib, lecam, o, d_o, per, rows, pairs, rows_first, vals, i_total, i_out):
+    """``srgan_lecam`` behind a loss launch that left its total at ``vals[i_total]`` and ``d_o``: three values to ``vals[i_out:]``"""
+    state, clamp = lecam
+    if state.device != vals.device:
+        raise _lib.SrganHipError("lecam: the record lives on another device than the maps")
+    S = len(o)
+    arr = ctypes.c_void_p * S
+    _lib.check(lib.srgan_lecam(arr(*[t.data_ptr() for t in o]), per, S, rows, pairs, rows_first, clamp, vals.data_ptr() + 4 * i_total,
+                               vals.data_ptr() + 4 * i_out, arr(*[t.data_ptr() for t in d_o]), _ptr(state), _stream()), "lecam")
+
+
 class _DLossesFn(Function):
     @staticmethod
-    def forward(ctx, label, rows_first, t_first, t_rest, w_class, n_scales, gan_kind, class_kind, *tensors):
+    def forward(ctx, label, rows_first, t_first, t_rest, w_class, n_scales, gan_kind, class_kind, lecam, *tensors):
         outs, logits = tensors[:n_scales], tensors[n_scales:]
         lib = _lib.load()
         dev = outs[0].device
@@ -2196,7 +2247,7 @@ class _DLossesFn(Function):
         nc = z[0].shape[1] if z else 0
         d_o = [torch.empty_like(t) for t in o]
         dz = [torch.empty_like(t) for t in z]
-        vals = torch.empty(4, dtype=torch.float32, device=dev)
+        vals = torch.empty(4 if lecam is None else 7, dtype=torch.float32, device=dev)
         S = n_scales
         arr = ctypes.c_void_p * S
         per = (ctypes.c_longlong * S)(*[t.numel() // rows for t in o])
@@ -2207,24 +2258,32 @@ class _DLossesFn(Function):
                                            float(w_class), gan_kind, class_kind, _ptr(vals), arr(*[t.data_ptr() for t in d_o]),
                                            arr(*[t.data_ptr() for t in dz]) if z else None, _stream()), "d_losses")
         ctx.save_for_backward(*d_o, *dz)
-        total, parts = vals[3], vals[:3]
+        if lecam is not None:
+            # the LeCam term on the same maps, its gradient added into d_o: vals[4:7] = [R, weight R, total + weight R]
+            _lecam_launch(lib, lecam, o, d_o, per, rows, rows, int(rows_first), vals, 3, 4)
+            total, parts = vals[6], vals[:6]
+        else:
+            total, parts = vals[3], vals[:3]
         ctx.mark_non_differentiable(parts)
         return total, parts
 
     @staticmethod
     def backward(ctx, g, _gp):
         grads = torch._foreach_mul(list(ctx.saved_tensors), g)      # one multi-tensor launch
-        return (None,) * 8 + tuple(grads)
+        return (None,) * 9 + tuple(grads)
 
 
-def d_losses(outs, logits, label, rows_first, t_first, t_rest, w_class, gan_kind=CRIT_MSE, class_kind=CRIT_MSE):
+def d_losses(outs, logits, label, rows_first, t_first, t_rest, w_class, gan_kind=CRIT_MSE, class_kind=CRIT_MSE, lecam=None):
     """Every loss of one discriminator evaluation in one launch -> (total, tensor([gan_first, class, gan_rest])):
     the first ``rows_first`` rows against ``t_first`` (+ softmax / class loss against ``label``), the rest against ``t_rest``;
     total = gan_first + w_class * class + gan_rest, each term the mean over the scales (util.py:457-468).  ``gan_kind``:
-    nn.MSELoss (LSGAN, the default) or nn.BCEWithLogitsLoss on the maps; ``class_kind``: nn.MSELoss or nn.BCELoss on softmax(z)."""
+    nn.MSELoss (LSGAN, the default) or nn.BCEWithLogitsLoss on the maps; ``class_kind``: nn.MSELoss or nn.BCELoss on softmax(z).
+    ``lecam``: ``(record, clamp)`` (``lc_state_new``) adds the LeCam term in a second launch inside the same autograd node:
+    -> (total + weight R while the term is applied, tensor([gan_first, class, gan_rest, total, R, weight R or 0])); the first rows
+    are the real ones, its gradient rides the buffers the backward scales anyway."""
     logits = list(logits) if logits else []
     return _DLossesFn.apply(label, rows_first, t_first, t_rest, w_class, len(outs), _crit_kind(gan_kind, "d_losses"),
-                            _crit_kind(class_kind, "d_losses"), *outs, *logits)
+                            _crit_kind(class_kind, "d_losses"), _lecam_arg(lecam, "d_losses"), *outs, *logits)
 
 
 class _LincombFn(Function):
@@ -2850,7 +2909,7 @@ def cr_state_read(state):
 
 class _DLossesCrFn(Function):
     @staticmethod
-    def forward(ctx, label, rows_first, t_first, t_rest, w_class, n_scales, gan_kind, class_kind, state, pairs_first, *tensors):
+    def forward(ctx, label, rows_first, t_first, t_rest, w_class, n_scales, gan_kind, class_kind, state, pairs_first, lecam, *tensors):
         outs, logits = tensors[:n_scales], tensors[n_scales:]
         lib = _lib.load()
         dev = outs[0].device
@@ -2866,7 +2925,7 @@ class _DLossesCrFn(Function):
         nc = z[0].shape[1] if z else 0
         d_o = [torch.empty_like(t) for t in o]
         dz = [torch.empty_like(t) for t in z]
-        vals = torch.empty(7, dtype=torch.float32, device=dev)
+        vals = torch.empty(7 if lecam is None else 10, dtype=torch.float32, device=dev)
         S = n_scales
         arr = ctypes.c_void_p * S
         per = (ctypes.c_longlong * S)(*[t.numel() // rows for t in o])
@@ -2878,29 +2937,36 @@ class _DLossesCrFn(Function):
                                          arr(*[t.data_ptr() for t in dz]) if z else None, rows // 2, int(pairs_first), _ptr(state),
                                          _stream()), "d_losses_cr")
         ctx.save_for_backward(*d_o, *dz)
-        total_cr, parts = vals[6], vals[:6]
+        if lecam is not None:
+            # the LeCam term on the front rows, on top of total_with_cr: vals[7:10] = [R, weight R, total_with_cr + weight R]
+            _lecam_launch(lib, lecam, o, d_o, per, rows, rows // 2, int(rows_first), vals, 6, 7)
+            total_cr, parts = vals[9], vals[:9]
+        else:
+            total_cr, parts = vals[6], vals[:6]
         ctx.mark_non_differentiable(parts)
         return total_cr, parts
 
     @staticmethod
     def backward(ctx, g, _gp):
         grads = torch._foreach_mul(list(ctx.saved_tensors), g)      # one multi-tensor launch
-        return (None,) * 10 + tuple(grads)
+        return (None,) * 11 + tuple(grads)
 
 
 def d_losses_cr(outs, logits, label, rows_first, t_first, t_rest, w_class, state, gan_kind=CRIT_MSE, class_kind=CRIT_MSE,
-                pairs_first=None):
+                pairs_first=None, lecam=None):
     """``d_losses`` of a consistency-regularised discriminator evaluation, in one launch: the maps hold ``2 P`` rows, row ``r + P``
     the partner ``cr_pairs`` made of row ``r``.  The front ``P`` rows get what ``d_losses`` computes for ``P`` rows; on top come
     ``cr_g = mean_s mean_{r in g} (m_s(r) - m_s(r + P))^2`` over the pairs ``[0, pairs_first)`` (g = first, weight ``lambda_real *
     every`` of the device record ``state``) and the rest (``lambda_fake * every``), ``m_s`` the patch mean of scale s's map
     (``pairs_first``: ``rows_first`` by default).  -> (total_with_cr, tensor([gan_first, class, gan_rest, total, cr_first,
     cr_rest])): the first is what to back-propagate, the six others carry no gradient.  The record takes the two unweighted terms
-    and counts the call."""
+    and counts the call.  ``lecam``: ``(record, clamp)`` adds the LeCam term of the front ``P`` rows (``rows_first`` of them real)
+    in a second launch inside the same autograd node: the first result gains ``weight R`` while the term is applied, the values
+    become the six above followed by ``[total_with_cr, R, weight R or 0]``; the back rows' gradient is not touched."""
     logits = list(logits) if logits else []
     return _DLossesCrFn.apply(label, rows_first, t_first, t_rest, w_class, len(outs), _crit_kind(gan_kind, "d_losses_cr"),
                               _crit_kind(class_kind, "d_losses_cr"), state, rows_first if pairs_first is None else pairs_first,
-                              *outs, *logits)
+                              _lecam_arg(lecam, "d_losses_cr"), *outs, *logits)
 
 
 # ---- mode-seeking regularisation of the generator (srgan_amd.diversity; extension, no counterpart in the reference) ----

@@ -35,6 +35,7 @@ from . import ada as _adamod
 from .augment import DiffAugment, GeometricAugment
 from . import consistency as _crmod
 from . import diversity as _msmod
+from . import lecam as _lcmod
 from .checkpoint import Checkpointing
 from . import r1 as _r1mod
 from .losses import class_encode, criterion_kind, get_domainloss_D, get_loss_D, has_fused_kind, histogram_imitation
@@ -105,6 +106,7 @@ class SRGAN_training(Checkpointing):
         self._ada = None               # adaptive augmentation probability on the device (enable_ada)
         self._r1 = None                # R1 gradient penalty on the real rows (enable_r1)
         self.bcr = None                # balanced consistency regularisation of D (enable_bcr)
+        self._lecam = None             # LeCam regularisation of D (enable_lecam)
         self._ms = None                # mode-seeking regularisation of G (enable_mode_seeking)
         self._label_cache = {}         # (kind, which) -> (label tensor, its device form): _cached
         self._d_pending = None         # an update_D left its all-reduce / optimiser step to _finish_D: the reducer, or True
@@ -253,7 +255,7 @@ class SRGAN_training(Checkpointing):
         return (self.optG, self.optD, self.optE)
 
     def _extensions(self):
-        return [x for x in (self._ema, self._sn(), *self._stages(), self._ada, self._r1, self.bcr, self._ms) if x is not None]
+        return [x for x in (self._ema, self._sn(), *self._stages(), self._ada, self._r1, self.bcr, self._lecam, self._ms) if x is not None]
 
     def _mirrors(self):
         """who mirrors, on the host, a device-side count that the step advances: Adam's step counts, the EMA's update count"""
@@ -445,6 +447,9 @@ class SRGAN_training(Checkpointing):
         cr = self.bcr if self.bcr is not None and _index % self.bcr.every == 0 else None
         if self.bcr is not None:
             self._bcr_check()
+        lc = self._lecam
+        if lc is not None:
+            self._lecam_check()
         if self._fused_paths():
             # real and fake halves through D as ONE batch (per-sample network: exact; 2x the rows per GEMM launch)
             B = self.source_image.shape[0]
@@ -477,16 +482,27 @@ class SRGAN_training(Checkpointing):
                 self._ada.observe(outs, B, _adamod.threshold(self._kinds()[0]))
                 self.loss_terms["ada_p"] = self._ada.p_tensor()
             # criterion(real, 1) + class loss * lbd + criterion(fake, 0) over both scales, values and gradients: one launch
-            if cr is None:
+            if cr is None and lc is not None:
+                # the same launch, then the LeCam term on the same maps (anchors, settings and the warm-up count from its device
+                # record), its gradient added into the buffers the backward scales; errD stays the value without it
+                loss_D, parts = ops.d_losses(outs, logits, self._label_dev("source"), B, 1., 0., self.lbd["class"], *self._kinds(),
+                                             lecam=lc.arg(outs[0].device))
+                errD = parts[3]
+                self.loss_terms["errD_lecam"] = parts[4]
+            elif cr is None:
                 errD, parts = ops.d_losses(outs, logits, self._label_dev("source"), B, 1., 0., self.lbd["class"], *self._kinds())
                 loss_D = errD
             else:
                 # the same over the front 2B rows, plus the consistency terms between row n and row n + 2B and their gradients
                 # (weights from the device record), still one launch; errD stays the value without them
+                # (LeCam, if on, follows on the front 2B rows)
                 loss_D, parts = ops.d_losses_cr(outs, logits, self._label_dev("source"), B, 1., 0., self.lbd["class"],
-                                                cr._ensure(outs[0].device), *self._kinds())
+                                                cr._ensure(outs[0].device), *self._kinds(),
+                                                lecam=lc.arg(outs[0].device) if lc is not None else None)
                 errD = parts[3]
                 self.loss_terms.update(errD_cr_real=parts[4], errD_cr_fake=parts[5])
+                if lc is not None:
+                    self.loss_terms["errD_lecam"] = parts[7]
             errD_real, errD_class, errD_fake = parts[0], parts[1], parts[2]
         else:
             d_real = self._aug(self.source_image)
@@ -1088,6 +1104,60 @@ class SRGAN_training(Checkpointing):
         return self.bcr.stats() if self.bcr is not None else None
 
     # ------------------------------------------------------------------------------------------
+    # LeCam regularisation of D (extension, no counterpart in the reference; srgan_amd.lecam)
+    def _lecam_check(self):
+        if dp.world_size() > 1:
+            raise NotImplementedError(f"SRGAN_training: LeCam regularisation is on and the process group has {dp.world_size()} ranks; "
+                                      "the anchors are averages of the global batch's predictions and would need a cross-rank mean "
+                                      "(run one process, or disable_lecam())")
+        if not self._fused_paths():
+            raise NotImplementedError("SRGAN_training: LeCam regularisation is wired into the fused discriminator pass only (this "
+                                      "package's own G / D / E modules with forward_logits, a one-hot ref_label, criteria with a "
+                                      "fused kernel); use those, or disable_lecam()")
+
+    def enable_lecam(self, weight=0.3, decay=0.99, start=0, clamp=False):
+        """LeCam regularisation (Tseng et al., 2021): from now on EVERY discriminator update back-propagates ``errD + weight * R``,
+        ``R = mean over the scales of [ mean_real phi(D(x) - a_F)^2 + mean_fake phi(a_R - D(G(z)))^2 ]`` on the raw GAN maps (scores
+        under ``nn.MSELoss``, logits under ``nn.BCEWithLogitsLoss``), ``a_R`` / ``a_F`` exponential moving averages (``decay``) of
+        the maps' means over the real / generated rows, per scale, updated BEFORE the term and constants of it; ``phi``: identity
+        (the paper's equation), ``clamp=True``: relu (the one-sided form of the authors' released code).  The first update sets
+        the anchors to the batch means; an update with a non-finite mean moves none.  The gradient is added from anchor update
+        ``start`` on (a warm-up of the averages); ``R`` is computed and reported from the first.  One small launch per update
+        behind the fused loss launch (``csrc/lecam.hip``); no extra rows through D, no launch in the backward; with consistency
+        regularisation on, the term is taken on the front 2B rows only.  ``errD`` and the returned losses are unchanged;
+        ``loss_terms["errD_lecam"]`` is the unweighted ``R`` of the step's last update (a device scalar).  Anchors, the count of
+        updates and the three settings are device state (``set_lecam`` keeps a recording; a replayed step crosses ``start`` by
+        itself); ``clamp`` is structural.  The defaults are this project's choice for LSGAN targets 0 / 1 and are not taken from
+        any release; a criterion on the logit scale wants a much smaller weight.  Enabling drops a recording made before.  Off: no
+        launch, no allocation, the step is bit-identical to the plain one.  Refused: more than one rank, the generic (non-fused)
+        discriminator path."""
+        state = _lcmod.LeCam(weight, decay, start, clamp)
+        prev, self._lecam = self._lecam, state
+        try:
+            self._lecam_check()
+        except NotImplementedError:
+            self._lecam = prev
+            raise
+        self._guard_changed()
+        return self
+
+    def disable_lecam(self):
+        self._lecam = None
+        self._guard_changed()
+
+    def set_lecam(self, weight=None, decay=None, start=None):
+        """Write new settings (those given) into the regulariser's device record, between steps; a recorded step reads them from
+        there and stays valid."""
+        if self._lecam is None:
+            raise RuntimeError("set_lecam: LeCam regularisation is off (enable_lecam)")
+        self._lecam.set(weight, decay, start)
+
+    def lecam_stats(self):
+        """``weight``, ``decay``, ``start``, ``clamp`` and the device record's ``updates``, ``a_real``, ``a_fake`` (four per group, one
+        per scale in use), ``penalty``, ``applied`` as a dict, or None with the feature off.  SYNCHRONISES the stream."""
+        return self._lecam.stats() if self._lecam is not None else None
+
+    # ------------------------------------------------------------------------------------------
     # mode-seeking regularisation of G (extension, no counterpart in the reference; srgan_amd.diversity)
     def _ms_check(self):
         if dp.world_size() > 1:
@@ -1313,6 +1383,10 @@ class SingleGAN_training(Checkpointing):
         raise NotImplementedError("SingleGAN_training: consistency regularisation is not wired into this trainer's discriminator "
                                   "passes (per-domain sub-batches); use SRGAN_training.enable_bcr, or consistency.BalancedCR in a "
                                   "loop of your own")
+
+    def enable_lecam(self, *args, **kwargs):
+        raise NotImplementedError("SingleGAN_training: LeCam regularisation is not wired into this trainer's discriminator passes "
+                                  "(per-domain sub-batches); use SRGAN_training.enable_lecam, or lecam.LeCam in a loop of your own")
 
     def enable_mode_seeking(self, *args, **kwargs):
         raise NotImplementedError("SingleGAN_training: mode seeking is not wired into this trainer's generator update (per-domain "
