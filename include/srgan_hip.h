@@ -459,7 +459,8 @@ int srgan_soft_histogram_bwd(const float* x, const float* g, long long n, int bi
                              float* dx, void* stream);
 
 /* optim.Adam.step, torch 1.4 arithmetic (util_notebook.py:500-506) on flat buffers.
- * step_count is the 1-based step number t.  Writes through raw pointers (no autograd version bump). */
+ * step_count is the 1-based step number t.  Writes through raw pointers (no autograd version bump).  n = 0 does nothing and
+ * accepts null pointers. */
 int srgan_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1,
                     float beta2, float eps, int step_count, void* stream);
 

@@ -352,6 +352,10 @@ int record_write(void* rec, const void* image, size_t bytes, unsigned mask, hipS
 // AdamState (records.h): the step counter lives on the device so that a captured train step (hipGraph) advances it on every
 // replay; the host mirrors the count for checkpoints only.
 // torch 1.4: p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)   (bias corrections in double, as the host path did)
+// The betas enter as the float32 numbers of the record: 1 - b^t here and 1.f - b in the update come from b = float32(beta), where
+// torch 1.4 takes float32(1 - beta) and 1 - beta^t from the Python doubles.  On the update that is a relative difference of at most
+// c = |float32(beta) - beta| / (1 - beta) per beta (1.29e-5 for beta2 = 0.999, 0 for beta1 = 0.5);
+// tests/test_adam_kernels_gpu.py::test_distance_to_torch14_stays_inside_c holds it there (derivation: tests/adam_common.py).
 __global__ void adam_tick_kernel(AdamState* s) {
   const int t = s->step + 1;
   s->step = t;
@@ -745,8 +749,9 @@ extern "C" int srgan_nhwc_to_nchw(const float* x, float* y, int N, int C, int H,
 
 extern "C" int srgan_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1,
                                float beta2, float eps, int step_count, void* stream) {
-  SRGAN_REQUIRE(p && g && m && v && n >= 0 && step_count >= 1, "adam_step: bad argument");
-  if (n == 0) return 0;
+  SRGAN_REQUIRE(n >= 0 && step_count >= 1, "adam_step: bad argument");
+  if (n == 0) return 0;                  // an empty tensor: nothing to do (torch hands out null pointers for those)
+  SRGAN_REQUIRE(p && g && m && v, "adam_step: bad argument");
   // torch 1.4: p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
   const double bc1 = 1.0 - std::pow((double)beta1, step_count);
   const double bc2 = 1.0 - std::pow((double)beta2, step_count);

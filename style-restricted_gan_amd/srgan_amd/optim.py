@@ -1,5 +1,11 @@
-"""Fused Adam on the HIP path with the arithmetic of the reference's pinned torch==1.4.0
+"""Fused Adam on the HIP path with the formula of the reference's pinned torch==1.4.0
 (``optim.Adam(lr, betas=(0.5, 0.999))`` built at util_notebook.py:498-507; formula SURVEY.md F.6).
+
+One difference in the arithmetic: the betas enter as the float32 numbers of the device record, and the kernels derive ``1.f - b``
+and the bias corrections ``1 - b^t`` from ``b = float32(beta)``; torch 1.4 takes ``float32(1 - beta)`` and ``1 - beta^t`` from the
+Python doubles.  On the update this is a relative difference of at most ``c = |float32(beta) - beta| / (1 - beta)`` per beta --
+1.29e-5 for ``beta2 = 0.999``, 0 for ``beta1 = 0.5`` -- and ``tests/test_adam_kernels_gpu.py::test_distance_to_torch14_stays_inside_c``
+holds it there (derivation in ``tests/adam_common.py``).
 
 Parameters are updated through raw device pointers: the autograd version counters are NOT bumped,
 which is what lets phase 2 of ``update_GandE`` back-propagate a graph recorded before the step
