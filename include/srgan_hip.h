@@ -767,6 +767,52 @@ int srgan_ms_finish(const void* ws, size_t ws_bytes, const float* z1, const floa
 int srgan_ms_grad(const float* i1, const float* i2, const float* coef, const float* g, float* d1, float* d2, int b, long long e,
                   void* stream);
 
+/* Structural similarity (Wang et al., 2004, "Image quality assessment: from error visibility to structural similarity") as a
+ * loss term with its gradient and as a metric, and PSNR.  Extension, no counterpart in the reference.  csrc/ssim.hip.
+ * x, y: fp32 [n, c, h, w] stored NHWC-dense, c in 1..3, 4-byte aligned.  The window has `window` taps per axis (odd, 3..11), `taps`
+ * a HOST array of window fp32 weights (srgan_ssim_taps: the Gaussian of sigma, normalised in double, rounded to fp32); they travel
+ * by value in the launch packet.  Valid positions only: ho x wo = (h - window + 1) x (w - window + 1) per plane, no padding.  Per
+ * position and channel, E[.] the sum over the window with the product taps: mu_x = E[x], s_x = E[x^2] - mu_x^2, s_xy = E[xy] - mu_x
+ * mu_y (no clamp), SSIM = (2 mu_x mu_y + c1)(2 s_xy + c2) / ((mu_x^2 + mu_y^2 + c1)(s_x + s_y + c2)); value_i = the mean over sample
+ * i's positions and channels; term = 1 - mean_i value_i.  The kernels take the moments of x - x[i, :, 0, 0], y - y[i, :, 0, 0] (one
+ * pivot per plane; the definition's value, with the cancellation of E[x^2] - mu_x^2 moved to numbers of the size of the contrast).
+ * Record (srgan_ssim_state_bytes() = 32 bytes, device memory): {float weight, float c1, float c2, float term, float weighted,
+ * int updates, int pad[2]}.  srgan_ssim_state_init writes the three settings and zeroes the rest; srgan_ssim_state_set rewrites the
+ * settings between steps and keeps the rest (a recorded step reads them from the record); srgan_ssim_state_restore writes updates
+ * and the two last values and nothing else (resuming from a checkpoint).  One launch each.  -1 before any launch: a NULL record,
+ * weight < 0, c1 < 0, c2 <= 0, updates < 0, a value not finite (NaN refused).
+ * srgan_ssim_workspace(...): bytes of the workspace of the three launches below -- the tile partials, then 0 (no gradient), 3 (one
+ * of dx / dy) or 4 (both) coefficient maps of n ho wo c floats -- or 0 on bad geometry.
+ * srgan_ssim_map: ONE launch, one workgroup per (sample, tile of 8 x 32 positions): ws takes the fp32 sum of each tile's values, in
+ *   a fixed order, and with want_dx / want_dy the coefficient maps.  c1, c2 are READ from the record; state may be NULL: the
+ *   arguments c1, c2 count then.
+ * srgan_ssim_finish: ONE launch, one workgroup, float64: values[i] (n floats), vals[2] = {weight * term, term}; the record takes
+ *   term, weight * term and updates += 1; weight is READ from the record (state NULL: 1, nothing stored).
+ * srgan_ssim_grad: ONE launch, one workgroup per (sample, tile of 8 x 32 input pixels): dx and / or dy (NULL: nothing is written
+ *   for it; not both NULL) = the gradient of weight * term times *g (g a device scalar, NULL: 1; state NULL: weight 1), from the maps
+ *   of a srgan_ssim_map call with want_dx == (dx != NULL) and want_dy == (dy != NULL) on the same workspace.
+ * No atomics; every sum has a fixed order.
+ * srgan_psnr: TWO launches; out[i] (n doubles) = 10 log10(data_range^2 / mse_i), +inf at mse_i == 0, mse_i the mean of (x - y)^2 over
+ *   the e floats of row i: fp32 partial sums of 4096 terms, added and divided in float64.  ws of srgan_psnr_workspace(n, e) bytes.
+ * -1 with srgan_last_error() before any launch: a NULL pointer, n <= 0, c outside 1..3, window even or outside 3..11, h or w below
+ * window, n c h w >= 2^31 (n e for PSNR), a tap or a setting negative or not finite (NaN refused), a workspace too small or
+ * misaligned (16 bytes; PSNR: 8), a pointer not 4-byte aligned, an output of srgan_ssim_grad aliasing an input or the other output. */
+size_t srgan_ssim_state_bytes(void);
+int srgan_ssim_state_init(void* state, float weight, float c1, float c2, void* stream);
+int srgan_ssim_state_set(void* state, float weight, float c1, float c2, void* stream);
+int srgan_ssim_state_restore(void* state, int updates, float term, float weighted, void* stream);
+int srgan_ssim_taps(int window, double sigma, float* taps);
+size_t srgan_ssim_workspace(int n, int c, int h, int w, int window, int want_dx, int want_dy);
+int srgan_ssim_map(const float* x, const float* y, int n, int c, int h, int w, int window, const float* taps, const void* state,
+                   float c1, float c2, int want_dx, int want_dy, void* ws, size_t ws_bytes, void* stream);
+int srgan_ssim_finish(const void* ws, size_t ws_bytes, int n, int c, int h, int w, int window, void* state, float* vals,
+                      float* values, void* stream);
+int srgan_ssim_grad(const float* x, const float* y, int n, int c, int h, int w, int window, const float* taps, const void* ws,
+                    size_t ws_bytes, const void* state, const float* g, float* dx, float* dy, void* stream);
+size_t srgan_psnr_workspace(int n, long long e);
+int srgan_psnr(const float* x, const float* y, int n, long long e, float data_range, double* out, void* ws, size_t ws_bytes,
+               void* stream);
+
 /* Small host -> device upload (pointer tables: <= 1 MiB, multiple of 4 bytes) carried in kernel arguments: nothing to keep
  * alive on the host after the call returns, and a captured hipGraph stores the bytes in its node instead of re-reading a host
  * address at replay (no reference counterpart; plumbing of the multi-tensor ops above). */

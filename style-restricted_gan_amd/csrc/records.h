@@ -8,7 +8,7 @@
 
 namespace srgan {
 
-constexpr int kRecordWords = 16;                      // 32-bit words of the image a write carries: the largest of the eight records (AdaState, LcState) have 14
+constexpr int kRecordWords = 16;                      // 32-bit words of the image a write carries: the largest of the nine records (AdaState, LcState) have 14
 struct RecordImage { unsigned int w[kRecordWords]; };
 
 // Bit i = word i of the record: a field of kSize bytes at kOffset yields kSize / 4 adjacent bits (two for a 64-bit field).
@@ -78,5 +78,12 @@ struct LcState { float weight; float decay; int start; int updates; float a_real
 static_assert(sizeof(LcState) == 56, "LcState layout");
 constexpr unsigned kLcSet = SRGAN_WORDS(LcState, weight) | SRGAN_WORDS(LcState, decay) | SRGAN_WORDS(LcState, start);
 constexpr unsigned kLcRestore = SRGAN_WORDS(LcState, updates) | SRGAN_WORDS(LcState, a_real) | SRGAN_WORDS(LcState, a_fake);
+
+// weight, c1 = (k1 L)^2, c2 = (k2 L)^2 are written by the host between steps; term = 1 - mean SSIM and weighted = weight * term are
+// those of the last ssim_finish_kernel, updates counts them.  A restore writes the counter and the two last values.
+struct SsState { float weight; float c1; float c2; float term; float weighted; int updates; int pad[2]; };
+static_assert(sizeof(SsState) == 32, "SsState layout");
+constexpr unsigned kSsSet = SRGAN_WORDS(SsState, weight) | SRGAN_WORDS(SsState, c1) | SRGAN_WORDS(SsState, c2);
+constexpr unsigned kSsRestore = SRGAN_WORDS(SsState, updates) | SRGAN_WORDS(SsState, term) | SRGAN_WORDS(SsState, weighted);
 
 }  // namespace srgan

@@ -58,6 +58,7 @@ MsState = _record("MsState", weight=c_float, eps=c_float, tau=c_float, ms=c_floa
                   d_latent=c_float, updates=c_int)
 LcState = _record("LcState", weight=c_float, decay=c_float, start=c_int, updates=c_int, a_real=c_float * 4, a_fake=c_float * 4,
                   penalty=c_float, applied=c_int)
+SsState = _record("SsState", weight=c_float, c1=c_float, c2=c_float, term=c_float, weighted=c_float, updates=c_int, _pad=c_int * 2)
 
 P = c_void_p
 _DESC = POINTER(ConvDesc)
@@ -258,6 +259,18 @@ SIGNATURES = {
     "srgan_ms_rows": (c_int, [P, P, c_int, c_longlong, P, c_size_t, P]),
     "srgan_ms_finish": (c_int, [P, c_size_t, P, P, c_int, c_longlong, c_int, c_int, P, P, P, P]),
     "srgan_ms_grad": (c_int, [P, P, P, P, P, P, c_int, c_longlong, P]),
+    # structural similarity and PSNR (csrc/ssim.hip)
+    "srgan_ssim_state_bytes": (c_size_t, []),
+    "srgan_ssim_state_init": (c_int, [P, c_float, c_float, c_float, P]),
+    "srgan_ssim_state_set": (c_int, [P, c_float, c_float, c_float, P]),
+    "srgan_ssim_state_restore": (c_int, [P, c_int, c_float, c_float, P]),
+    "srgan_ssim_taps": (c_int, [c_int, ctypes.c_double, P]),
+    "srgan_ssim_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "srgan_ssim_map": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, c_float, c_int, c_int, P, c_size_t, P]),
+    "srgan_ssim_finish": (c_int, [P, c_size_t, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "srgan_ssim_grad": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P, P, P, P, P]),
+    "srgan_psnr_workspace": (c_size_t, [c_int, c_longlong]),
+    "srgan_psnr": (c_int, [P, P, c_int, c_longlong, c_float, P, P, c_size_t, P]),
     "srgan_upload_small": (c_int, [P, P, c_size_t, P]),
     "srgan_maxpool2_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "srgan_pairwise_dist": (c_int, [P, c_int, P, c_int, c_int, P, P]),

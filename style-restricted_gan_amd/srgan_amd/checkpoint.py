@@ -12,11 +12,12 @@ dict`` -- a file written from it loads with ``torch.load(path, weights_only=True
     hist_target              the histogram-imitation target the constructor drew (``lbd["hist"] > 0``)
     ema, augment, geometry,  the step's extensions that are on: the averaged copies and their update count, DiffAugment's settings
     ada, r1, bcr, lecam,     and generator, the geometric stage's settings and generator, the adaptive probability's settings and
-    mode_seeking, grad_guard whole record (p, seen, the three counts, adjustments, last_r, the record's batch size n), R1's
+    mode_seeking, ssim,      whole record (p, seen, the three counts, adjustments, last_r, the record's batch size n), R1's
                              gamma / every / updates (and the record's batch size n), consistency regularisation's weights / every /
                              policy / translation / generator / updates, LeCam's weight / decay / start / clamp / anchors / updates, mode seeking's weight / form / eps / tau / generator /
-                             updates and last ms / d_image / d_latent, per guarded net max_norm and the cumulative steps / skipped /
-                             clipped
+    grad_guard               updates and last ms / d_image / d_latent, the SSIM term's weight / on / window / sigma / k1 / k2 /
+                             data_range / updates and last term / weighted, per guarded net max_norm and the cumulative steps /
+                             skipped / clipped
     rng                      the CPU default generator (style and reparametrisation noise) and numpy's global one (``get_target``)
 
 Not saved: the last step's images, ``loss_terms``, the label cache, workspaces, packed operands, the guard's decision and R1's
@@ -45,7 +46,7 @@ LoadReport.__doc__ = """Sections the trainer has but the checkpoint lacks (they 
 use for (skipped)."""
 
 _NETS = ("G", "D", "E")
-_EXTENSIONS = ("ema", "augment", "geometry", "ada", "r1", "bcr", "lecam", "mode_seeking", "grad_guard")
+_EXTENSIONS = ("ema", "augment", "geometry", "ada", "r1", "bcr", "lecam", "mode_seeking", "ssim", "grad_guard")
 # the augmentation stages (srgan_amd.augment): (section, the trainer attribute the stage lives in, the switch that makes one, the keys
 # of a saved section the switch takes, in its order), in the order of application
 _STAGES = (("augment", "augment", "enable_diffaugment", ("policy", "translation", "cutout")),
@@ -137,7 +138,7 @@ class Checkpointing:
         if getattr(self, "hi", None) is not None:
             out.append("hist_target")
         for name, attr in (("ema", "_ema"), *(s[:2] for s in _STAGES), ("ada", "_ada"), ("r1", "_r1"), ("bcr", "bcr"),
-                           ("lecam", "_lecam"), ("mode_seeking", "_ms")):
+                           ("lecam", "_lecam"), ("mode_seeking", "_ms"), ("ssim", "_ssim")):
             if getattr(self, attr, None) is not None:
                 out.append(name)
         out += [f"grad_guard.{n}" for n in self._ckpt_guards()]
@@ -163,7 +164,7 @@ class Checkpointing:
     # ---- save ---------------------------------------------------------------------------------------------------------------------
     def state_dict(self, rng=True):
         """A snapshot of everything the next ``train()`` depends on (module docstring): CPU clones and plain values.  Between steps
-        only; reads the adaptive-probability, R1, consistency, LeCam, mode-seeking and gradient-guard records, so it SYNCHRONISES the stream.  ``rng=False`` leaves the two host
+        only; reads the adaptive-probability, R1, consistency, LeCam, mode-seeking, SSIM and gradient-guard records, so it SYNCHRONISES the stream.  ``rng=False`` leaves the two host
         generators out.  Per process: no collective."""
         self._ckpt_between_steps("state_dict")
         sd = {"version": VERSION, "config": self._ckpt_config()}
@@ -193,6 +194,8 @@ class Checkpointing:
             sd["lecam"] = _plain(self._lecam.state_dict(), "lecam")
         if getattr(self, "_ms", None) is not None:
             sd["mode_seeking"] = _plain(self._ms.state_dict(), "mode_seeking")
+        if getattr(self, "_ssim", None) is not None:
+            sd["ssim"] = _plain(dict(self._ssim.state_dict(), on=list(self._ssim_on)), "ssim")
         guards = self._ckpt_guards()
         if guards:
             sd["grad_guard"] = {}
@@ -249,7 +252,7 @@ class Checkpointing:
         fields BEFORE anything is written.  A recording of the step and the warm-up of its input shape are forgotten (torch's
         optimiser load replaces the moment tensors a recording points at): the next step runs eagerly, the one after records
         again; graph mode stays enabled.  Cached packed operands of every network and of the averaged copies are marked stale.
-        ``ema_updates``, ``grad_guard_stats()``, ``r1_stats()``, ``bcr_stats()``, ``lecam_stats()`` and ``mode_seeking_stats()`` continue from the saved
+        ``ema_updates``, ``grad_guard_stats()``, ``r1_stats()``, ``bcr_stats()``, ``lecam_stats()``, ``mode_seeking_stats()`` and ``ssim_stats()`` continue from the saved
         counts."""
         self._ckpt_between_steps("load_state_dict")
         who = type(self).__name__
@@ -274,6 +277,16 @@ class Checkpointing:
 
         def use(name):
             return name in sd and name not in unexpected
+
+        if use("ssim"):
+            # what enable_ssim would refuse further down, refused here: nothing has been written yet
+            from .structural import check_settings as _ssim_settings
+            m = sd["ssim"]
+            _ssim_settings(m["weight"], int(m["window"]), m["sigma"], m["k1"], m["k2"], m["data_range"], f"{who}.load_state_dict: ssim")
+            if "idt" in m["on"] and not self.lbd["idt"] > 0:
+                raise ValueError(f"{who}.load_state_dict: the checkpoint's SSIM term is taken on the identity reconstruction and this "
+                                 "trainer's lbd['idt'] is 0, so its step makes no identity image (build the trainer with lbd['idt'] > "
+                                 "0, or load with the section removed)")
 
         # a recording points at the moment tensors and device records replaced below, and the graphs the last step kept pin them
         graph = getattr(self, "_graph", None)
@@ -337,6 +350,12 @@ class Checkpointing:
             if self._ms is None or self._ms.form != m["form"]:
                 self.enable_mode_seeking(m["weight"], m["form"], m["eps"], m["tau"])
             self._ms.load_state_dict(m, next(dp.unwrap(self.G).parameters()).device)
+        if use("ssim"):
+            m = sd["ssim"]
+            structure = (int(m["window"]), float(m["sigma"]), float(m["k1"]), float(m["k2"]), float(m["data_range"]))
+            if self._ssim is None or self._ssim.structure() != structure or self._ssim_on != tuple(m["on"]):
+                self.enable_ssim(m["weight"], tuple(m["on"]), *structure)
+            self._ssim.load_state_dict(m, next(dp.unwrap(self.G).parameters()).device)
         for n, g in (sd.get("grad_guard") or {}).items():
             if f"grad_guard.{n}" in unexpected:
                 continue

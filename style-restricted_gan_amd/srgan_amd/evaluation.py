@@ -29,7 +29,8 @@ from .losses import weights_init
 from .ops import ACT_NONE, ACT_RELU, PAD_ZERO
 
 __all__ = ["VGG19_bn", "vgg19_bn", "vgg_model", "GAN_evaluation", "evaluation_init", "compute_prdc", "maxpool2",
-           "compute_frechet_distance", "compute_kid", "kid_subsets", "FD_MAX_SIDE", "compute_style_diversity"]
+           "compute_frechet_distance", "compute_kid", "kid_subsets", "FD_MAX_SIDE", "compute_style_diversity", "compute_ssim",
+           "compute_psnr"]
 
 VGG19_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512, "M"]
 
@@ -330,6 +331,51 @@ def compute_style_diversity(images):
     return math.fsum(values) / len(values)
 
 
+def _image_pair(a, b, who):
+    """two image sets [N, C, H, W] of one shape as CPU or device fp32 tensors (numpy arrays or tensors go in)"""
+    a, b = torch.as_tensor(a), torch.as_tensor(b)
+    if a.dim() != 4 or a.shape != b.shape or a.shape[0] < 1:
+        raise ValueError(f"{who}: two image sets [N, C, H, W] of one shape expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    return a.to(torch.float32), b.to(torch.float32)
+
+
+def _pair_chunks(a, b, chunk, who):
+    """slices of at most ``chunk`` samples; by default as many as keep one call under 2^31 floats (the kernels' offset limit)"""
+    per = int(a[0].numel())
+    limit = ((1 << 31) - 1) // per
+    if limit < 1:
+        raise ValueError(f"{who}: one image of {per} values is past the kernels' 2^31 limit")
+    if chunk is None:
+        chunk = limit
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f"{who}: chunk must be a positive integer, got {chunk!r}")
+    chunk = min(chunk, limit)
+    for i in range(0, a.shape[0], chunk):
+        yield a[i:i + chunk], b[i:i + chunk]
+
+
+def compute_ssim(a, b, window=11, sigma=1.5, k1=0.01, k2=0.03, data_range=2.0, device="cuda", chunk=None):
+    """Per-sample structural similarity of two image sets [N, C, H, W] (C <= 3; numpy arrays or tensors, paired by index) as a
+    float32 numpy array [N]: Gaussian window of ``window`` taps and ``sigma``, valid positions only, the mean over a sample's
+    positions and channels (``srgan_amd.structural``; the kernels of ``csrc/ssim.hip``).  ``data_range`` 2 fits images in [-1, 1].
+    The sets go through the device in slices of ``chunk`` samples (default: as many as stay under the kernels' 2^31 values)."""
+    from .structural import SSIM
+    a, b = _image_pair(a, b, "compute_ssim")
+    metric = SSIM(1.0, window, sigma, k1, k2, data_range)
+    out = [metric.value(x.to(device), y.to(device)).cpu().numpy() for x, y in _pair_chunks(a, b, chunk, "compute_ssim")]
+    return np.concatenate(out)
+
+
+def compute_psnr(a, b, data_range=2.0, device="cuda", chunk=None):
+    """Per-sample ``10 log10(data_range^2 / mse)`` of two image sets of one shape (numpy arrays or tensors, paired by index) as a
+    float64 numpy array [N]; ``inf`` where a pair is equal.  Chunked as ``compute_ssim``."""
+    a, b = _image_pair(a, b, "compute_psnr")
+    if not (isinstance(data_range, (int, float)) and not isinstance(data_range, bool) and 0 < data_range < float("inf")):
+        raise ValueError(f"compute_psnr: data_range must be finite and > 0, got {data_range!r}")
+    out = [ops.psnr(x.to(device), y.to(device), data_range).cpu().numpy() for x, y in _pair_chunks(a, b, chunk, "compute_psnr")]
+    return np.concatenate(out)
+
+
 class GAN_evaluation():
     """evaluation.py:38-110.  ``feature_extractor``: "vgg-initialization" (default-initialised VGG19-bn, as the reference's
     ``models.vgg19_bn(pretrained=False)`` + the no-op ``weights_init``), or "vgg-ImageNet" / "vgg-CelebA" with ``weights=`` a
@@ -411,17 +457,32 @@ class GAN_evaluation():
         """Pixel-space style diversity of ``images[S, N, ...]`` (``compute_style_diversity``): no feature extraction."""
         return compute_style_diversity(torch.as_tensor(images).to(self.device))
 
+    def get_ssim(self, true, pred, **kw):
+        """Per-sample SSIM of ``pred`` against ``true``, paired by index, on the raw images (``compute_ssim``): no feature extraction."""
+        return compute_ssim(true, pred, device=self.device, **kw)
+
+    def get_psnr(self, true, pred, **kw):
+        """Per-sample PSNR of ``pred`` against ``true``, paired by index, on the raw images (``compute_psnr``)."""
+        return compute_psnr(true, pred, device=self.device, **kw)
+
     def get_metrics(self, true, pred, metrics=("prdc", "fd", "kid"), nearest_k=5, num_subsets=100, max_subset_size=1000, seed=0,
                     preprocess=True, styles=None):
         """The chosen metrics from ONE extraction of each set, as one flat dict: precision / recall / density / coverage
-        ("prdc"), ``fd``, ``kid``; ``diversity`` only when asked for, from ``styles[S, N, ...]`` (``get_diversity``)."""
-        unknown = [m for m in metrics if m not in ("prdc", "fd", "kid", "diversity")]
+        ("prdc"), ``fd``, ``kid``; ``diversity`` only when asked for, from ``styles[S, N, ...]`` (``get_diversity``); ``ssim`` and
+        ``psnr`` only when asked for: the means over the pairs ``(true[i], pred[i])`` of the raw images (``get_ssim``, ``get_psnr``)."""
+        unknown = [m for m in metrics if m not in ("prdc", "fd", "kid", "diversity", "ssim", "psnr")]
         if unknown:
-            raise ValueError(f"get_metrics: unknown metrics {unknown} (prdc, fd, kid, diversity)")
+            raise ValueError(f"get_metrics: unknown metrics {unknown} (prdc, fd, kid, diversity, ssim, psnr)")
         if "diversity" in metrics and styles is None:
             raise ValueError("get_metrics: 'diversity' needs styles=[S, N, ...], S translations of each of N sources")
-        f1, f2 = self._features_of(true, pred, preprocess)
         out = {}
+        if "ssim" in metrics:
+            out["ssim"] = float(np.mean(self.get_ssim(true, pred), dtype=np.float64))
+        if "psnr" in metrics:
+            out["psnr"] = float(np.mean(self.get_psnr(true, pred)))
+        if out and all(m in ("ssim", "psnr") for m in metrics):
+            return out                         # pixel-space metrics alone: no feature extraction
+        f1, f2 = self._features_of(true, pred, preprocess)
         if "prdc" in metrics:
             out.update(compute_prdc(real_features=f1, fake_features=f2, nearest_k=nearest_k, device=self.device))
         if "fd" in metrics:

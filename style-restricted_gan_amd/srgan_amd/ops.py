@@ -3080,3 +3080,122 @@ def rowwise_l1(a, b):
         part = ws[:rows * nchunk * 4].view(torch.float32).view(rows, nchunk)
         # (a tensor divisor: dividing by a Python scalar multiplies by its rounded reciprocal on the device)
         return part.to(torch.float64).sum(1) / torch.full((), float(e), dtype=torch.float64, device=a.device)
+
+
+# ---- structural similarity and PSNR (srgan_amd.structural; extension, no counterpart in the reference) ----
+SSIM_MIN_WINDOW, SSIM_MAX_WINDOW = 3, 11       # kSsMinWindow, kSsMaxWindow of csrc/ssim_math.h
+SSIM_MAX_CHANNELS = 3                          # kSsMaxC of csrc/ssim.hip
+SSIM_TILE = (8, 32)                            # kSsTH, kSsTW: valid positions (forward) / input pixels (gradient) per workgroup
+
+
+def ssim_taps(window, sigma):
+    """The ``window`` taps of the Gaussian of ``sigma`` as Python floats that hold fp32 values: computed and normalised in double on
+    the host, rounded to fp32 (csrc/ssim_math.h).  Needs no GPU."""
+    if isinstance(window, bool) or not isinstance(window, int):
+        raise _lib.SrganHipError(f"ssim_taps: window must be an odd integer in [{SSIM_MIN_WINDOW}, {SSIM_MAX_WINDOW}], got {window!r}")
+    arr = (ctypes.c_float * SSIM_MAX_WINDOW)()
+    _lib.check(_lib.load().srgan_ssim_taps(window, float(sigma), arr), "ssim_taps")
+    return tuple(float(v) for v in arr[:window])
+
+
+def ss_state_new(device, weight, c1, c2):
+    """Device-resident record {weight, c1, c2, term, weighted, updates}, the last three at zero."""
+    return _record_new(_lib.SsState, device, "ssim_state_init", float(weight), float(c1), float(c2))
+
+
+def ss_state_set(state, weight, c1, c2):
+    """Rewrite the settings between steps; the last values and the counter stay (a recorded step reads the record)."""
+    _record_call("ssim_state_set", state, float(weight), float(c1), float(c2))
+
+
+def ss_state_restore(state, updates, term, weighted):
+    """Write a checkpoint's counter and last values between steps; the settings stay."""
+    _record_call("ssim_state_restore", state, int(updates), float(term), float(weighted))
+
+
+def ss_state_read(state):
+    """The record as a dict; synchronises the current stream."""
+    return _record_read(_lib.SsState, state)
+
+
+def _ssim_pair(x, y, what):
+    for t in (x, y):
+        if not torch.is_tensor(t) or t.dim() != 4:
+            raise _lib.SrganHipError(f"{what}: images [N, C, H, W] expected")
+        if t.dtype != torch.float32:
+            raise _lib.SrganHipError(f"{what}: fp32 images only, got {t.dtype} (the generator's RGB output is fp32 in both compute "
+                                     "modes; convert anything else with .float())")
+        _require_gpu(t, what)
+    if x.shape != y.shape or x.device != y.device:
+        raise _lib.SrganHipError(f"{what}: images of shape {tuple(x.shape)} and {tuple(y.shape)}")
+    return to_nhwc(x), to_nhwc(y)
+
+
+class _SsimFn(Function):
+    @staticmethod
+    def forward(ctx, x, y, state, taps, c1, c2):
+        x, y = _ssim_pair(x, y, "ssim")
+        if state is not None and (not torch.is_tensor(state) or state.dtype != torch.uint8
+                                  or state.numel() != ctypes.sizeof(_lib.SsState) or state.device != x.device):
+            raise _lib.SrganHipError("ssim: the record is None or one of ss_state_new on the images' device")
+        lib = _lib.load()
+        n, c, h, w = x.shape
+        window = len(taps)
+        need_x, need_y = int(ctx.needs_input_grad[0]), int(ctx.needs_input_grad[1])
+        nb = lib.srgan_ssim_workspace(n, c, h, w, window, need_x, need_y)
+        if nb == 0:
+            raise _lib.SrganHipError(f"ssim: images of shape {tuple(x.shape)} under a window of {window} taps: "
+                                     + lib.srgan_last_error().decode(errors="replace"))
+        ws = workspace(x.device, nb)
+        tarr = (ctypes.c_float * window)(*taps)
+        vals = torch.empty(2, dtype=torch.float32, device=x.device)
+        values = torch.empty(n, dtype=torch.float32, device=x.device)
+        _lib.check(lib.srgan_ssim_map(_ptr(x), _ptr(y), n, c, h, w, window, tarr, _ptr(state), float(c1), float(c2), need_x, need_y,
+                                      _ptr(ws), nb, _stream()), "ssim_map")
+        _lib.check(lib.srgan_ssim_finish(_ptr(ws), nb, n, c, h, w, window, _ptr(state), _ptr(vals), _ptr(values), _stream()),
+                   "ssim_finish")
+        # the gradient of weight * term here, with the maps still in the workspace; the backward scales it (as l1_mean)
+        dx = torch.empty_like(x) if need_x else None
+        dy = torch.empty_like(y) if need_y else None
+        if need_x or need_y:
+            _lib.check(lib.srgan_ssim_grad(_ptr(x), _ptr(y), n, c, h, w, window, tarr, _ptr(ws), nb, _ptr(state), None, _ptr(dx),
+                                           _ptr(dy), _stream()), "ssim_grad")
+        ctx.save_for_backward(dx, dy)
+        weighted, term = vals[0], vals[1]
+        ctx.mark_non_differentiable(term, values)
+        return weighted, term, values
+
+    @staticmethod
+    def backward(ctx, g, _gt, _gv):
+        dx, dy = ctx.saved_tensors
+        return (dx * g if dx is not None else None, dy * g if dy is not None else None, None, None, None, None)
+
+
+def ssim(x, y, state, taps, c1=4e-4, c2=3.6e-3):
+    """Structural similarity of two fp32 image batches [N, C, H, W] (C <= 3) under the separable window ``taps`` (``ssim_taps``), valid
+    positions only -> (weight * term, term, per-sample values [N]) with ``term = 1 - mean SSIM``: the first is differentiable in
+    ``x`` and ``y`` independently (either may not require a gradient: nothing is computed for it), the other two carry none.
+    ``weight``, ``c1`` and ``c2`` are read from the device record ``state`` (``ss_state_new``), which takes the values and counts the
+    call; ``state=None``: weight 1, the arguments ``c1``, ``c2`` (defaults: k1 = 0.01, k2 = 0.03, data range 2).  Two launches
+    without a gradient, three with (the gradient is formed in the forward; the backward multiplies by the incoming scalar); no
+    atomics, a fixed order of every sum.  hipGraph-capturable.  Any dtype but fp32 is refused."""
+    return _SsimFn.apply(x, y, state, tuple(taps), c1, c2)
+
+
+def psnr(x, y, data_range=2.0):
+    """Per-sample ``10 log10(data_range^2 / mse)`` of two fp32 batches of one shape -> float64 ``[N]`` on the device (``+inf`` where the
+    rows are equal): fp32 partial sums of 4096 squared differences, added and divided in float64.  No gradient."""
+    with torch.no_grad():
+        for t in (x, y):
+            _require_gpu(t, "psnr")
+        if x.shape != y.shape or x.dim() < 2:
+            raise _lib.SrganHipError(f"psnr: operands of shape {tuple(x.shape)} and {tuple(y.shape)}")
+        a, b, rows, e = _ms_pair(x.detach(), y.detach(), "psnr")
+        lib = _lib.load()
+        nb = lib.srgan_psnr_workspace(rows, e)
+        if nb == 0:
+            raise _lib.SrganHipError(f"psnr: {rows} rows of {e} floats: " + lib.srgan_last_error().decode(errors="replace"))
+        ws = workspace(a.device, nb)
+        out = torch.empty(rows, dtype=torch.float64, device=a.device)
+        _lib.check(lib.srgan_psnr(_ptr(a), _ptr(b), rows, e, float(data_range), _ptr(out), _ptr(ws), nb, _stream()), "psnr")
+        return out

@@ -36,6 +36,7 @@ from .augment import DiffAugment, GeometricAugment
 from . import consistency as _crmod
 from . import diversity as _msmod
 from . import lecam as _lcmod
+from . import structural as _ssmod
 from .checkpoint import Checkpointing
 from . import r1 as _r1mod
 from .losses import class_encode, criterion_kind, get_domainloss_D, get_loss_D, has_fused_kind, histogram_imitation
@@ -108,6 +109,8 @@ class SRGAN_training(Checkpointing):
         self.bcr = None                # balanced consistency regularisation of D (enable_bcr)
         self._lecam = None             # LeCam regularisation of D (enable_lecam)
         self._ms = None                # mode-seeking regularisation of G (enable_mode_seeking)
+        self._ssim = None              # structural-similarity term of the reconstructions (enable_ssim)
+        self._ssim_on = ()             # which of ("cycle", "idt") it is taken on
         self._label_cache = {}         # (kind, which) -> (label tensor, its device form): _cached
         self._d_pending = None         # an update_D left its all-reduce / optimiser step to _finish_D: the reducer, or True
         self._sn_cache = (None, None)  # (key, spectral controller or None): _sn
@@ -255,7 +258,7 @@ class SRGAN_training(Checkpointing):
         return (self.optG, self.optD, self.optE)
 
     def _extensions(self):
-        return [x for x in (self._ema, self._sn(), *self._stages(), self._ada, self._r1, self.bcr, self._lecam, self._ms) if x is not None]
+        return [x for x in (self._ema, self._sn(), *self._stages(), self._ada, self._r1, self.bcr, self._lecam, self._ms, self._ssim) if x is not None]
 
     def _mirrors(self):
         """who mirrors, on the host, a device-side count that the step advances: Adam's step counts, the EMA's update count"""
@@ -610,6 +613,13 @@ class SRGAN_training(Checkpointing):
             g_terms.append((errG_cycle, L["cycle"]))
             rep_terms.append((errG_cycle, L["cycle"]))
             terms = dict(errG_dis=errG_dis, errG_class=errG_class, errG_cycle=errG_cycle)
+            ss_terms = []
+            if self._ssim is not None and "cycle" in self._ssim_on:
+                # weight * (1 - SSIM(src, recon_image)) from the device record, optimised with weight 1 beside the L1 term; the
+                # gradient reaches the reconstruction only (src is data).  errG and errE_output stay the reference's sums.
+                ss_weighted, ss_term = self._ssim.loss(src.detach(), recon_image)
+                ss_terms.append((ss_weighted, 1.0))
+                terms["errG_ssim_cycle"] = ss_term
 
             _, mu, logvar, _, _ = source_enc_info
             if L["KL"] > 0:
@@ -631,6 +641,12 @@ class SRGAN_training(Checkpointing):
                 g_terms.append((errG_idt, L["idt"]))
                 rep_terms.append((errG_idt, L["idt"]))
                 terms["errG_idt"] = errG_idt
+                if self._ssim is not None and "idt" in self._ssim_on:
+                    ss_weighted, ss_term = self._ssim.loss(src.detach(), identity_image)
+                    ss_terms.append((ss_weighted, 1.0))
+                    terms["errG_ssim_idt"] = ss_term
+            elif self._ssim is not None and "idt" in self._ssim_on:
+                raise RuntimeError(self._SSIM_IDT_OFF)
 
             if L["batch_KL"] > 0:
                 w_corr = L["corr_enc"] if L["corr_enc"] > 0 else 0.0
@@ -651,7 +667,7 @@ class SRGAN_training(Checkpointing):
                 ms_weighted, ms_value = ms.loss(t_img, i2, self.c_rand, z2)
                 ms_terms.append((ms_weighted, 1.0))
                 terms["errG_ms"] = ms_value
-            total_p1 = ops.lincomb(g_terms + ms_terms + e_terms)
+            total_p1 = ops.lincomb(g_terms + ms_terms + ss_terms + e_terms)
             with torch.no_grad():
                 errG = ops.lincomb(g_terms)
                 errE_output = ops.lincomb(rep_terms)
@@ -1219,6 +1235,56 @@ class SRGAN_training(Checkpointing):
         return self._ms.stats() if self._ms is not None else None
 
     # ------------------------------------------------------------------------------------------
+    # structural-similarity term of the reconstructions (extension, no counterpart in the reference; srgan_amd.structural)
+    _SSIM_IDT_OFF = ("SRGAN_training: the SSIM term is asked for on the identity reconstruction and lbd['idt'] is 0, so the step makes "
+                     "no identity image (set lbd['idt'] > 0, or enable_ssim(on=('cycle',)))")
+
+    def enable_ssim(self, weight=1.0, on=("cycle",), window=11, sigma=1.5, k1=0.01, k2=0.03, data_range=2.0):
+        """A structural-similarity term beside the L1 reconstruction terms (Wang et al., 2004; as a loss: Zhao et al., 2017): from
+        now on phase 1 of ``update_GandE`` back-propagates ``weight * (1 - SSIM(source, recon_image))`` on top of the phase's loss
+        (``"cycle"`` in ``on``), and the same for ``identity_image`` (``"idt"`` in ``on``; needs ``lbd["idt"] > 0``).  SSIM: Gaussian
+        window of ``window`` taps (odd, 3..11) and ``sigma``, valid positions only, ``C1 = (k1 data_range)^2``, ``C2 = (k2
+        data_range)^2``, the mean over positions, channels and samples (``srgan_amd.structural``).  The gradient reaches the
+        reconstruction only, never the source.  Three launches of ``csrc/ssim.hip`` per term in the forward, none in the backward
+        beyond one scaling.  The returned ``errG`` and ``errE_output`` are unchanged; ``loss_terms["errG_ssim_cycle"]`` /
+        ``["errG_ssim_idt"]`` are the unweighted terms.  Captured with the step in graph mode; the weight is device state
+        (``set_ssim_weight`` keeps a recording), the other settings are structural: enabling, disabling or other settings drop a
+        recording made before.  With both reconstructions the record holds the last term taken (the identity's).  Off: no
+        launch, no allocation, the step is bit-identical to the plain one.  Data parallel: the term is a mean over the rank's own
+        rows like ``errG_cycle``, so the gradient all-reduce averages it as it averages that; untested beyond one process."""
+        if isinstance(on, str):
+            on = (on,)
+        on = tuple(on)
+        if not on or any(o not in ("cycle", "idt") for o in on) or len(set(on)) != len(on):
+            raise ValueError(f"enable_ssim: on must be a non-empty subset of ('cycle', 'idt'), got {on!r}")
+        if "idt" in on and not self.lbd["idt"] > 0:
+            raise ValueError(self._SSIM_IDT_OFF)
+        self._ssim = _ssmod.SSIM(weight, window, sigma, k1, k2, data_range)
+        self._ssim_on = tuple(o for o in ("cycle", "idt") if o in on)
+        self._guard_changed()
+        return self
+
+    def disable_ssim(self):
+        self._ssim = None
+        self._ssim_on = ()
+        self._guard_changed()
+
+    def set_ssim_weight(self, weight):
+        """Write a new weight into the term's device record, between steps; a recorded step reads it from there and stays valid."""
+        if self._ssim is None:
+            raise RuntimeError("set_ssim_weight: the SSIM term is off (enable_ssim)")
+        self._ssim.set_weight(weight)
+
+    def ssim_stats(self):
+        """The settings, ``on`` and the device record's ``term``, ``weighted``, ``updates`` as a dict, or None with the feature off.
+        SYNCHRONISES the stream."""
+        if self._ssim is None:
+            return None
+        out = self._ssim.stats()
+        out["on"] = self._ssim_on
+        return out
+
+    # ------------------------------------------------------------------------------------------
     # device-side gradient guard (extension, no counterpart in the reference; srgan_amd.optim.Adam.enable_grad_guard)
     _GUARD_NETS = ("G", "D", "E")
 
@@ -1387,6 +1453,10 @@ class SingleGAN_training(Checkpointing):
     def enable_lecam(self, *args, **kwargs):
         raise NotImplementedError("SingleGAN_training: LeCam regularisation is not wired into this trainer's discriminator passes "
                                   "(per-domain sub-batches); use SRGAN_training.enable_lecam, or lecam.LeCam in a loop of your own")
+
+    def enable_ssim(self, *args, **kwargs):
+        raise NotImplementedError("SingleGAN_training: the SSIM term is not wired into this trainer's generator update (per-domain "
+                                  "sub-batches); use SRGAN_training.enable_ssim, or structural.SSIM in a loop of your own")
 
     def enable_mode_seeking(self, *args, **kwargs):
         raise NotImplementedError("SingleGAN_training: mode seeking is not wired into this trainer's generator update (per-domain "
